@@ -3,6 +3,7 @@
 22-joint AMASS targets) on N MI355X of one node.
 
     python bench.py --gpus N --steps K --warmup W [--total-frames T | --frames F] [--iters I] [--model smpl|smplx]
+                    [--full] [--dump-outputs DIR]
 
 ``--gpus N > 1`` without a launcher (no WORLD_SIZE in the environment) starts its own N ranks with
 ``python -m torch.distributed.run`` before touching the GPU and relays rank 0's line; under a launcher
@@ -16,10 +17,14 @@ total work is fixed, N = 1 fits all 4096 frames on one GPU).  ``--frames F`` swi
 independent frames: the fused fit kernel (all Adam iterations), the all-gather of the fitted parameters
 over RCCL (N > 1: enqueued behind the fit, on RCCL's stream), the final LBS forward over the rank's OWN
 block (joints + all vertices per frame), the all-gather of the joints, the wait for both.  Inputs are
-resident in HBM before the timed region.  Rank 0 prints ONE JSON line; BASELINE configs[1] (1024 frames
-per GPU), configs[2] (10 000-frame sequence, sharded) and configs[3] (SMPL-X, 1024 frames per GPU) ride
-along under ``weak_1024`` / ``seq_10000`` / ``smplx_1024`` (measured in the same process after the timed
-region, same K / W / repeats).  See DESIGN.md "Measurement" for `roofline` / `cpu_baseline`.
+resident in HBM before the timed region, which is exactly K steps.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline alone.  ``--full`` adds what takes extra work: HIP events around the
+fit, forward and exchange of sampled steps (`roofline`, `roofline_lbs`, `exchange_ms`), the `quality`
+figures, BASELINE configs[1] (1024 frames per GPU), configs[2] (10 000-frame sequence, sharded) and
+configs[3] (SMPL-X, 1024 frames per GPU) under ``weak_1024`` / ``seq_10000`` / ``smplx_1024`` (measured in
+the same process after the timed region, same K / W / repeats) and the `cpu_baseline`.  See DESIGN.md
+"Measurement".  ``--dump-outputs DIR`` writes the outputs of the last timed step as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -49,8 +54,10 @@ PREWARM_S = 0.3        # seconds of untimed load before the warm-up steps (devic
 # HIP events around the fit launch, the forward and the exchange are recorded on every EVENT_EVERY-th step of the timed region
 # (they are what `roofline.avg_launch_ms` averages: 5 of the default 20 steps of each of the nine blocks).  Four timing events per
 # step cost ~10 us of a 0.57 ms step (same box, back to back: 0.5727 / 0.5746 ms with events on every step, 0.5587 / 0.5653 on
-# every fourth) - instrumentation, not work of the path.  K2B_BENCH_EVENT_EVERY=1 records them on every step.
+# every fourth) - instrumentation, not work of the path, so only --full records them.  K2B_BENCH_EVENT_EVERY=1 records them on
+# every step.
 EVENT_EVERY = max(1, int(os.environ.get("K2B_BENCH_EVENT_EVERY", "4")))
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of arrays (a seeded sample of frames beyond it)
 
 
 def lbs_bytes_per_frame(model) -> int:
@@ -70,21 +77,47 @@ def lbs_flop_per_frame(model) -> float:
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # (a fresh process starts at a low device clock: see PREWARM_S; the timed block of K steps is repeated, see --repeats)
-    ap.add_argument("--steps", type=int, default=20)
+    # (a fresh process starts at a low device clock: see PREWARM_S; the K timed steps are split into blocks, see --repeats)
+    ap.add_argument("--steps", type=int, default=180, help="timed steps K")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=9, help="timed blocks of K steps each; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=9,
+                    help="blocks the K timed steps are split into (at most K); the median block is reported")
     ap.add_argument("--total-frames", type=int, default=4096,
                     help="frames of the ONE sequence sharded over all ranks (strong scaling; north-star: 4096)")
     ap.add_argument("--frames", type=int, default=None,
                     help="weak scaling instead: this many frames per GPU (BASELINE configs[1]: 1024)")
     ap.add_argument("--iters", type=int, default=100, help="Adam iterations per frame")
     ap.add_argument("--model", choices=("smpl", "smplx"), default="smpl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also record the per-kernel HIP events (roofline, quality) and measure the secondary lines and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-weak-line", action="store_true",
-                    help="skip the secondary measurements (weak_1024, seq_10000, smplx_1024)")
+                    help="with --full: skip the secondary measurements (weak_1024, seq_10000, smplx_1024)")
     ap.add_argument("--cpu-runs", type=int, default=5, help="timed B=1 fits per thread setting of the CPU baseline")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0's block) as DIR/<name>.npy, float32; beyond "
+                         f"{DUMP_BYTES >> 20} MiB a seeded sample of frames")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    return args
+
+
+def dump_outputs(path, out, joints, verts):
+    """What the caller of the timed path receives for its frames: the fitted parameters and per-frame loss (``out``), the
+    joints and the vertices, one float32 .npy per array.  All arrays keep the same frames: every frame when they fit in
+    DUMP_BYTES, otherwise a sample drawn with seed 0 (sorted frame indices), so two builds write the same rows."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    arrays["joints"], arrays["vertices"] = joints, verts
+    frames = verts.shape[0]
+    bytes_per_frame = sum(4 * int(np.prod(v.shape[1:])) for v in arrays.values())
+    n = min(frames, DUMP_BYTES // bytes_per_frame)
+    rows = np.arange(frames) if n == frames else np.sort(np.random.default_rng(0).choice(frames, n, replace=False))
+    rows = torch.as_tensor(rows, device=verts.device)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), v.index_select(0, rows).to(torch.float32).cpu().numpy())
 
 
 def build_problem(total_frames, start, stop, seed, device, model_kind="smpl"):
@@ -285,10 +318,9 @@ def main():
 
     ev = lambda: torch.cuda.Event(enable_timing=True)
 
-    repeats = max(1, int(args.repeats))
-
-    def measure(total, weak, steps, warmup, model_kind):
-        """Time `steps` passes over this rank's share of `total` frames (weak: `total` = frames per GPU)."""
+    def measure(total, weak, steps, warmup, model_kind, events):
+        """Time `steps` passes over this rank's share of `total` frames (weak: `total` = frames per GPU); `events`: HIP events
+        around the fit, the forward and the exchange of sampled steps, and the quality figures of the last step."""
         if weak:
             T, start, stop, per = total * world, rank * total, (rank + 1) * total, total
         else:
@@ -348,22 +380,25 @@ def main():
             torch.cuda.synchronize()
         for _ in range(warmup):
             step()
-        # The timed region: EXACTLY `steps` steps between barrier + synchronize on both sides, maximum over the ranks - taken
-        # `repeats` times back to back, and the MEDIAN block is the reported one (`repeats`, `block_ms` in the JSON line).  The
-        # device shows transient slow phases of 20-40 ms in which every kernel takes about twice as long (clock / power state
-        # transitions; seen on some boxes and not on others: the same 4096-frame fit launch 0.50 ms, then 0.94 ms for one chunk
-        # of 50 launches, then 0.50 ms again - tools/dev_fit_sustained.py).  One window of any length either contains such a
-        # phase or not (single windows of this workload read 3.3, 4.5 and 5.7 M frames/s within a minute on one box); the
-        # median of nine short windows does not depend on it.
+        # The timed region: EXACTLY `steps` steps, split into `repeats` blocks back to back (as equal as the division allows),
+        # each between barrier + synchronize on both sides, maximum over the ranks; the block with the MEDIAN time per step is
+        # the reported one (`repeats`, `block_steps`, `block_ms` in the JSON line).  The device shows transient slow phases of
+        # 20-40 ms in which every kernel takes about twice as long (clock / power state transitions; seen on some boxes and not
+        # on others: the same 4096-frame fit launch 0.50 ms, then 0.94 ms for one chunk of 50 launches, then 0.50 ms again -
+        # tools/dev_fit_sustained.py).  One window of any length either contains such a phase or not (single windows of this
+        # workload read 3.3, 4.5 and 5.7 M frames/s within a minute on one box); the median of nine short windows does not
+        # depend on it.
+        nblocks = min(args.repeats, steps)
+        sizes = [steps // nblocks + (1 if b < steps % nblocks else 0) for b in range(nblocks)]
         blocks = []
-        for rep in range(repeats):
+        for size in sizes:
             del fit_ev[:], lbs_ev[:], xch_ev[:]
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for i in range(steps):
-                out, joints, verts = step(record=i % EVENT_EVERY == 0)
+            for i in range(size):
+                out, joints, verts = step(record=events and i % EVENT_EVERY == 0)
             torch.cuda.synchronize()
             if dist is not None:
                 dist.barrier()
@@ -372,19 +407,22 @@ def main():
                 tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
                 elapsed = float(tmax.item())
-            mean_ms = lambda evs: float(np.mean([a.elapsed_time(b) for a, b in evs]))      # HIP events on the launch stream
+            mean_ms = lambda evs: float(np.mean([a.elapsed_time(b) for a, b in evs])) if evs else None  # HIP events, launch stream
             blocks.append((elapsed, mean_ms(fit_ev), mean_ms(lbs_ev), mean_ms(xch_ev)))
-        order = sorted(range(repeats), key=lambda i: blocks[i][0])
-        elapsed, fit_ms, lbs_ms, xch_ms = blocks[order[repeats // 2]]           # the median block (same block for all figures)
+        order = sorted(range(nblocks), key=lambda b: blocks[b][0] / sizes[b])
+        med = order[nblocks // 2]                                               # the median block (same block for all figures)
+        elapsed, fit_ms, lbs_ms, xch_ms = blocks[med]
         n_local = stop - start
         jl = joints if joints.shape[0] == n_local else joints[rank * per: rank * per + n_local]   # gathered joints: own rows
         res = {
-            "T": T, "frames_local": n_local, "elapsed": elapsed, "model": model, "kind": model_kind, "weak": weak,
-            "fit_ms": fit_ms, "lbs_ms": lbs_ms, "exchange_ms": xch_ms,
+            "T": T, "frames_local": n_local, "step_s": elapsed / sizes[med], "model": model, "kind": model_kind, "weak": weak,
+            "fit_ms": fit_ms, "lbs_ms": lbs_ms, "exchange_ms": xch_ms, "block_steps": sizes,
             "block_ms": [round(1e3 * b[0], 3) for b in blocks],
-            "err_cm": float((jl[:, :K] - j3d).norm(dim=-1).mean().item() * 100) if n_local else 0.0,
-            "loss": float(out["loss"].mean()) if n_local else 0.0,
+            "out": out, "joints": jl, "vertices": verts,
         }
+        if events:
+            res["err_cm"] = float((jl[:, :K] - j3d).norm(dim=-1).mean().item() * 100) if n_local else 0.0
+            res["loss"] = float(out["loss"].mean()) if n_local else 0.0
         return res
 
     def fractions(r):
@@ -398,9 +436,9 @@ def main():
 
     def sub_line(r, workload):
         _, _, fit_tflops, lbs_gbs = fractions(r)
-        d = {"workload": workload, "value": round(r["T"] * args.steps / r["elapsed"], 1), "unit": "frames/s",
+        d = {"workload": workload, "value": round(r["T"] / r["step_s"], 1), "unit": "frames/s",
              "scaling": "weak" if r["weak"] else "strong", "total_frames": r["T"], "frames_rank0": r["frames_local"],
-             "ms_per_step": round(r["elapsed"] / args.steps * 1e3, 4),
+             "ms_per_step": round(r["step_s"] * 1e3, 4),
              "fit_ms": round(r["fit_ms"], 4), "lbs_ms": round(r["lbs_ms"], 4),
              "fit_frac_fp32": round(fit_tflops / FP32_PEAK_TFLOPS, 4), "lbs_frac_hbm": round(lbs_gbs / HBM_PEAK_GBS, 4),
              "mean_joint_error_cm": round(r["err_cm"], 3)}
@@ -409,15 +447,18 @@ def main():
         return d
 
     weak = args.frames is not None
-    main_res = measure(args.frames if weak else args.total_frames, weak, args.steps, args.warmup, args.model)
+    main_res = measure(args.frames if weak else args.total_frames, weak, args.steps, args.warmup, args.model, args.full)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_res["out"], main_res["joints"], main_res["vertices"])
+    del main_res["out"], main_res["joints"], main_res["vertices"]
     extra = {}
-    if not weak and not args.no_weak_line and args.model == "smpl":
+    if args.full and not weak and not args.no_weak_line and args.model == "smpl":
         # the other BASELINE configs ride along in the same process (same steps / warm-up / repeats; each builds its own problem)
-        extra["weak_1024"] = sub_line(measure(1024, True, args.steps, args.warmup, "smpl"),
+        extra["weak_1024"] = sub_line(measure(1024, True, args.steps, args.warmup, "smpl", True),
                                       "BASELINE configs[1]: 1024 frames per GPU (weak scaling), same model and settings")
-        extra["seq_10000"] = sub_line(measure(10000, False, args.steps, args.warmup, "smpl"),
+        extra["seq_10000"] = sub_line(measure(10000, False, args.steps, args.warmup, "smpl", True),
                                       f"BASELINE configs[2]: 10 000-frame AMASS-style sequence, frames sharded over {world} GPU(s)")
-        extra["smplx_1024"] = sub_line(measure(1024, True, args.steps, args.warmup, "smplx"),
+        extra["smplx_1024"] = sub_line(measure(1024, True, args.steps, args.warmup, "smplx", True),
                                        "BASELINE configs[3]: SMPL-X (55 joints, V=10475, betas | expression = 20), 1024 frames per GPU, "
                                        "all 55 kinematic joints observed, 100 Adam iters")
 
@@ -425,9 +466,6 @@ def main():
         r = main_res
         model = r["model"]
         F = r["frames_local"]
-        ms_per_step = r["elapsed"] / args.steps * 1e3
-        flop_iter, lbs_bytes, fit_tflops, lbs_gbs = fractions(r)
-        traffic, traffic_lbs, traffic_src = read_traffic(args.model, F)
         n = model.native
         shape = (f"{'SMPL' if args.model == 'smpl' else 'SMPL-X'}-shaped model (V={n.num_vertices}, J={n.num_joints}, "
                  f"{n.num_betas} betas)")
@@ -441,15 +479,15 @@ def main():
         line = {
             "metric": "SMPL frames fitted/sec (100 Adam iters, 22-joint AMASS)" if args.model == "smpl"
                       else "SMPL-X frames fitted/sec (100 Adam iters, 55 kinematic joints)",
-            "value": round(r["T"] * args.steps / r["elapsed"], 1),
+            "value": round(r["T"] / r["step_s"], 1),
             "unit": "frames/s",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "repeats": repeats,                 # timed blocks of `steps` steps; value / ms_per_step are the median block's
-            "event_every": EVENT_EVERY,         # steps between HIP-event samples of the per-kernel durations (roofline.avg_launch_ms)
+            "repeats": len(r["block_steps"]),   # timed blocks the steps were split into; value / ms_per_step are the median block's
+            "block_steps": r["block_steps"],
             "block_ms": r["block_ms"],
-            "ms_per_step": round(ms_per_step, 4),
+            "ms_per_step": round(r["step_s"] * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak" if weak else "strong",
             "vs_baseline": None,
@@ -463,32 +501,36 @@ def main():
                 "step": "parallel.fit_forward_exchange (the function optimize_params_sequence runs for independent frames): "
                         "fit own block, parameter all-gather under the final forward of the own block, joints all-gather",
             },
+        }
+        if args.full:
+            flop_iter, lbs_bytes, fit_tflops, lbs_gbs = fractions(r)
+            traffic, traffic_lbs, traffic_src = read_traffic(args.model, F)
+            line["event_every"] = EVENT_EVERY   # steps between HIP-event samples of the per-kernel durations (roofline.avg_launch_ms)
             # dominant kernel: the fused fit.  It never touches HBM inside its loop; its bound is fp32 vector-ALU issue
             # (DESIGN §4.1), so the peak is the fp32 VALU peak (= the fp32-input MFMA peak), not an f16 matrix peak.
-            "roofline": {
+            line["roofline"] = {
                 "kernel": "k2b_fit_world_kernel" if args.model == "smpl" else "k2b_fit_tree_kernel", "bound": "valu", "achieved": round(fit_tflops, 3),
                 "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(fit_tflops / FP32_PEAK_TFLOPS, 4),
                 "traffic": traffic, "avg_launch_ms": round(r["fit_ms"], 4),
                 "note": f"algorithmic fp32 flops ({flop_iter / 1e6:.3f} MFLOP per frame-iteration) against the fp32 vector peak",
-            },
-            "roofline_lbs": {
+            }
+            line["roofline_lbs"] = {
                 "kernel": LBS_KERNELS[args.model], "bound": "hbm",
                 "achieved": round(lbs_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(lbs_gbs / HBM_PEAK_GBS, 4), "traffic": traffic_lbs, "avg_launch_ms": round(r["lbs_ms"], 4),
                 "bytes_per_frame": lbs_bytes,
                 "achieved_tflops": round(lbs_flop_per_frame(model) * F / (r["lbs_ms"] * 1e-3) / 1e12, 2),
-            },
-            "quality": {"mean_joint_error_cm": round(r["err_cm"], 3), "mean_final_loss": round(r["loss"], 2)},
-        }
-        if world > 1:
-            line["exchange_ms"] = round(r["exchange_ms"], 4)    # what the step waits for the collectives behind the forward
-        if traffic_src:
-            line["roofline"]["traffic_source"] = line["roofline_lbs"]["traffic_source"] = "profiles/" + traffic_src
-        sq = read_sq(args.model, F)
-        if sq:
-            line["roofline"].update({k: sq[k] for k in ("valu_active_frac", "mfma_busy_frac", "wait_any_frac", "sq_source") if k in sq})
+            }
+            line["quality"] = {"mean_joint_error_cm": round(r["err_cm"], 3), "mean_final_loss": round(r["loss"], 2)}
+            if world > 1:
+                line["exchange_ms"] = round(r["exchange_ms"], 4)    # what the step waits for the collectives behind the forward
+            if traffic_src:
+                line["roofline"]["traffic_source"] = line["roofline_lbs"]["traffic_source"] = "profiles/" + traffic_src
+            sq = read_sq(args.model, F)
+            if sq:
+                line["roofline"].update({k: sq[k] for k in ("valu_active_frac", "mfma_busy_frac", "wait_any_frac", "sq_source") if k in sq})
         line.update(extra)
-        if world == 1 and not args.no_cpu_baseline and args.model == "smpl":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "smpl":
             line["cpu_baseline"] = cpu_baseline(args.iters, args.cpu_runs)
         print(json.dumps(line), flush=True)
     if dist is not None:
