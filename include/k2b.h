@@ -21,7 +21,8 @@
  *     FIRST use of an (iterations, lr, beta1, beta2) combination per model (blocking upload
  *     of the Adam bias table; at most 64 tables are kept, least recently used evicted after
  *     a stream sync).  k2b_vertex_term never synchronises: its joint selection travels by value in
- *     the kernel arguments;
+ *     the kernel arguments; k2b_surface_term and k2b_fit_world with surface targets synchronise the
+ *     stream on the FIRST use of a selection per model (its vertex table is gathered and cached);
  *   - buffers are caller-owned; inputs are never written; handles may be shared by
  *     threads as long as concurrent calls use different streams AND different
  *     workspaces (one workspace per handle: serialise calls on one handle).
@@ -76,6 +77,15 @@ int k2b_model_dims(const k2b_model *model, int32_t *num_vertices, int32_t *num_j
 /* Pre-sizes the per-model LBS workspace for batches of up to `max_frames` frames, so that no later k2b_lbs
  * call on this model allocates or synchronises (see Conventions).  Synchronises the device if it has to grow. */
 int k2b_model_reserve(k2b_model *model, int32_t max_frames);
+/* Facial landmarks (smplx `vertices2landmarks`): landmark l is the barycentric point sum_k bary[l][k] v[vertex_ids[l][k]] of
+ * one mesh triangle (smplx: vertex_ids = faces_tensor[lmk_faces_idx], bary = lmk_bary_coords).  HOST pointers, copied.  Call
+ * at most once per handle (a second successful call fails; a failed call leaves no table and may be repeated), before any
+ * fit or LBS call on it.  0 <= L <= 1024, vertex ids in [0, V), finite weights summing to 1 within 1e-3 per landmark
+ * (barycentric).  With L > 0 the output joints follow smplx's layout: J kinematic joints, E extra vertices, L landmarks;
+ * model joint index J + E + l names landmark l in model_joint_index.  Synchronises the device. */
+int k2b_model_set_landmarks(k2b_model *model, int32_t num_landmarks, const int32_t *vertex_ids /*[L][3]*/,
+                            const float *bary /*[L][3]*/);
+int k2b_model_num_landmarks(const k2b_model *model, int32_t *num_landmarks);
 /* Copies the precomputed J_template [J][3] and J_dirs [J][3][NB] to HOST buffers (either may be NULL). */
 int k2b_model_joint_basis(const k2b_model *model, float *j_template, float *j_dirs);
 
@@ -150,11 +160,16 @@ uint32_t k2b_fit_config_size(void);
  *
  *   model_joint_index [K] HOST int32: model joint fitted to target k (the reference's
  *       smpl_index / target_model_indices, world_space.py:194-201); values must be
- *       distinct.  Indices >= J name smplx's vertex-selected "extra" joints (at
- *       most 32 of them, at least one kinematic joint beside them; any supported tree): the call then queues TWO
+ *       distinct.  Indices >= J name SURFACE targets: smplx's vertex-selected "extra" joints
+ *       (J .. J+E-1) and landmarks (J+E .. J+E+L-1, k2b_model_set_landmarks); at most 128 of them, at
+ *       least one kinematic joint beside them; any supported tree.  The call then queues TWO
  *       launches per iteration on the stream - the fused kernel in evaluate-only mode and the
- *       vertex-term kernel with its Adam tail - with no host work in between; conf may be per
- *       frame there too.
+ *       surface-term kernel with its Adam tail - with no host work in between; conf may be per
+ *       frame there too.  At most 32 extra joints and no landmark: k2b_vertex_term's kernel (the
+ *       results of the first release, bit for bit); otherwise k2b_surface_term's.  The first use of
+ *       a selection of surface targets on a model synchronises the stream (its vertex table is
+ *       gathered and cached: at most 64 selections per model, least recently used evicted after a
+ *       device sync).
  *   j3d  dev [B][K][3]   target joints (already gathered with corr_index)
  *   conf dev [K] or [B][K] (see conf_per_frame); NULL = ones
  *   *_in dev: initial global_orient [B][3], body_pose [B][3(J-1)], betas [B][NB], transl [B][3]
@@ -253,8 +268,9 @@ int k2b_fit_sequence_lbfgs(const k2b_model *model, const k2b_prior *prior, const
 /* ---------------------------------------------------------------------------------
  * k2b_lbs — full SMPL forward.  Replaces `self.smpl(**kwargs)` (smplx `SMPL.forward`,
  * call sites world_space.py:34,192,278; engine.py:114) for a batch:
- *   joints_out dev [B][J+E][3], vertices_out dev [B][V][3] (NULL: joints only; the E
- *   vertex-selected joints are then skinned alone).  transl may be NULL (no translation).
+ *   joints_out dev [B][J+E+L][3], vertices_out dev [B][V][3] (NULL: joints only; the E
+ *   vertex-selected joints and the 3L landmark vertices are then skinned alone).  transl may be NULL
+ *   (no translation).  Landmarks are combined from the translated vertices.
  * ------------------------------------------------------------------------------- */
 int k2b_lbs(const k2b_model *model, int32_t num_frames, const float *global_orient,
             const float *body_pose, const float *betas, const float *transl,
@@ -284,6 +300,14 @@ int k2b_vertex_term(const k2b_model *model, int32_t num_frames, int32_t num_sele
                     float sigma, float joint_loss_weight, const float *global_orient,
                     const float *body_pose, const float *betas, const float *transl,
                     float *loss_out, float *grad_out, void *stream);
+/* k2b_surface_term: k2b_vertex_term generalised to surface targets (extra joints and landmarks):
+ *   model_joint_index HOST int32 [T], each in [J, J+E+L); targets dev [B][T][3]; conf dev [T], or [B][T] with
+ *   conf_per_frame != 0, or NULL.  At most 128 targets per call.  Loss [B] and gradient [B][3 + 3(J-1) + NB + 3]. */
+int k2b_surface_term(const k2b_model *model, int32_t num_frames, int32_t num_selected,
+                     const int32_t *model_joint_index, const float *targets, const float *conf,
+                     int32_t conf_per_frame, float sigma, float joint_loss_weight, const float *global_orient,
+                     const float *body_pose, const float *betas, const float *transl,
+                     float *loss_out, float *grad_out, void *stream);
 int k2b_adam_step(int64_t n, float *params, const float *grad, float *m, float *v, int32_t step,
                   double step_size, double beta1, double beta2, double eps, void *stream);
 

@@ -37,7 +37,7 @@ from typing import Optional
 import torch
 
 from ... import native
-from ...models.body_model import BodyModel, as_body_model
+from ...models.body_model import BodyModel, as_body_model, check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData
 from ...prior import MaxMixturePrior
 from ..constants import JOINT_MAP, TORSO_JOINTS, category_indices
@@ -155,6 +155,7 @@ class CameraSpaceFitter:
                         targets=(j3d if identity else j3d.index_select(1, self._device_index(self.corr_index))).contiguous(),
                         stage1_idx=_TORSO_IDX, stage1_tgt=j3d.index_select(1, torso).contiguous(), depth_w=200.0, torso=torso)
         model_idx = [int(i) for i in torch.as_tensor(target_model_indices).reshape(-1).tolist()]
+        check_target_indices(self.smpl, model_idx)
         targets = j3d.contiguous()
         return dict(custom=True, model_idx=model_idx, targets=targets, stage1_idx=model_idx, stage1_tgt=targets, depth_w=100.0,
                     torso=None)

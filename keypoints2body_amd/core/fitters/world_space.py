@@ -45,7 +45,7 @@ import numpy as np
 import torch
 
 from ... import native
-from ...models.body_model import BodyModel, as_body_model
+from ...models.body_model import BodyModel, as_body_model, check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData, SMPLHData, SMPLXData
 from ...prior import MaxMixturePrior
 from ..constants import category_indices, root_indices
@@ -141,6 +141,7 @@ class WorldSpaceFitter:
             model_idx = [int(i) for i in torch.as_tensor(target_model_indices).reshape(-1).tolist()]
             if len(model_idx) != j3d.shape[1]:
                 raise ValueError("target_model_indices must have one entry per target joint")
+            check_target_indices(self.smpl, model_idx)
             tgt = j3d
             conf_sel = None
         tgt = tgt.to(self.device).contiguous()

@@ -9,6 +9,12 @@ adapter layer (reference ``keypoints2body/core/joints/adapters.py:35-380``):
   optionally with the OpenSim -> SMPL axis change;
 * dict input (``body`` / ``left_hand`` / ``right_hand`` / ``face`` blocks) is concatenated and
   comes with explicit model joint indices (layout ``"GENERIC"``).
+
+Face blocks are indexed as the reference indexes them (its ``constants.py:65-71``): a face block of
+k points addresses model joints ``67 .. 67+k-1``.  On a 55-joint SMPL-X model with smplx's output
+layout (55 joints, 21 vertex-selected extras, then the landmarks) the first 9 of those are the
+fingertip extras 67..75 and only the rest are facial landmarks (76..); a 51-point face therefore
+reaches landmarks 0..41.  This is the reference's behaviour, kept as it is.
 """
 from __future__ import annotations
 

@@ -103,6 +103,26 @@ struct k2b_model {
     struct AdamTable { float2* dev; uint64_t last_use; };
     std::map<std::tuple<int, double, double, double>, AdamTable> adam_tables;
     uint64_t adam_clock = 0;
+    std::vector<int> h_extra_ids;                            // host copy of extra_vertex_ids
+    // landmarks (k2b_model_set_landmarks): output joint J + E + l = sum_k lmk_w[l][k] v[lmk_ids[l][k]]
+    int L = 0;
+    bool lmk_set = false;
+    std::vector<int> h_lmk_ids;
+    std::vector<float> h_lmk_w;
+    int *lmk_ids = nullptr, *lmk_seq = nullptr;              // device [L][3]; lmk_seq[l][k] = 3 l + k (rows of the set below)
+    float* lmk_w = nullptr;                                  // device [L][3]
+    VertexSet lmk;                                           // LBS operands of the 3L landmark vertices (joints-only forward)
+    float* ws_lmk = nullptr;                                 // LBS workspace (grow-only, with wsXh ...): the 3L vertices of a
+    int ws_lmk_bpad = 0;                                     // joints-only call, [ws_lmk_bpad][3L][3]
+    // compact tables of the surface-point term (k2b_surface.hip), one per selection of (model index, target column) pairs;
+    // at most kMaxSurfaceTables, least recently used evicted
+    struct SurfaceTable {
+        void* dev = nullptr;
+        k2b::SurfaceTermArgs a{};                            // table pointers and sizes filled, call fields not
+        uint64_t last_use = 0;
+    };
+    std::map<std::vector<int>, SurfaceTable> surface_tables;
+    uint64_t surface_clock = 0;
     std::mutex mu;
 };
 
@@ -120,9 +140,102 @@ struct k2b_prior {
     std::mutex mu_lock;
 };
 
+namespace {
+// LBS B operands of a vertex set (f16 hi/lo, MFMA fragment order; k2b_lbs.hip, k2b_lbs_stream.hip) from HOST constants in which
+// vertex v's rows are those of `ids` (posedirs row stride 3 * V).  tag[i] = 1 + e when vertex i of the set is the vertex of
+// output joint J + e (mesh set only), else 0.
+int build_vertex_set(k2b_model* m, k2b_model::VertexSet& vs, const std::vector<int>& ids, const std::vector<int>& tag,
+                     const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights, int V) {
+    const int KX = m->k_steps_x, P = m->P, NB = m->NB, J = m->J;
+    const int n = (int)ids.size();
+    vs.num = n;
+    vs.v_tiles = (n + 31) / 32;
+    const int vp = vs.v_tiles * 32;
+    std::vector<k2b::k2b_half> pdh((size_t)KX * 3 * vp * 16, (k2b::k2b_half)0.f), pdl(pdh.size(), (k2b::k2b_half)0.f);
+    for (int i = 0; i < n; ++i) {
+        const int v = ids[i];
+        for (int c = 0; c < 3; ++c) {
+            auto put = [&](int k, k2b::k2b_half hi, k2b::k2b_half lo) {
+                const size_t o = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
+                pdh[o] = hi;
+                pdl[o] = lo;
+            };
+            auto split = [&](int k, float x) -> float {   // returns what two f16 terms leave over
+                const float xs = x * k2b::kPdScale;
+                const k2b::k2b_half hi = (k2b::k2b_half)xs;
+                const k2b::k2b_half lo = (k2b::k2b_half)(xs - (float)hi);
+                put(k, hi, lo);
+                return xs - (float)hi - (float)lo;
+            };
+            for (int k = 0; k < P; ++k) split(k, posedirs[(size_t)k * 3 * V + 3 * v + c]);
+            for (int k = 0; k < NB; ++k) split(P + k, shapedirs[((size_t)v * 3 + c) * NB + k]);
+            const float rest = split(P + NB, v_template[(size_t)v * 3 + c]);
+            // the template is metre-scale: keep its third term as an extra K row (feature = 1)
+            const k2b::k2b_half rh = (k2b::k2b_half)rest;
+            put(P + NB + 1, rh, (k2b::k2b_half)(rest - (float)rh));
+        }
+    }
+    // tile-kernel layout of W: [16-vertex tile][hi groups | lo groups | ONES | ZERO][16 rows][8 joints]
+    const int GA = k2b::tile_groups_a(J), NGP = k2b::tile_ngp(GA), v16 = vs.v_tiles * 2;
+    std::vector<k2b::k2b_half> w2((size_t)v16 * NGP * 128, (k2b::k2b_half)0.f);
+    for (int t = 0; t < v16; ++t)
+        for (int r = 0; r < 16; ++r) {
+            const int i = t * 16 + r;
+            k2b::k2b_half* rowp = w2.data() + ((size_t)t * NGP * 16 + r) * 8;
+            if (i < n)
+                for (int j = 0; j < J; ++j) {
+                    const float w = lbs_weights[(size_t)ids[i] * J + j];
+                    const k2b::k2b_half hi = (k2b::k2b_half)w;
+                    rowp[(size_t)(j >> 3) * 128 + (j & 7)] = hi;
+                    rowp[(size_t)(GA + (j >> 3)) * 128 + (j & 7)] = (k2b::k2b_half)(w - (float)hi);
+                }
+            for (int k = 0; k < 3; ++k) rowp[(size_t)(2 * GA) * 128 + k] = (k2b::k2b_half)1.f;   // ONES: picks up the PAD terms
+            if (i < n && !tag.empty() && tag[i]) rowp[(size_t)(2 * GA + 1) * 128] = (k2b::k2b_half)(float)tag[i];   // ZERO group: joint tag
+        }
+    hipError_t e;
+    if (m->stream || m->stream_x) {
+        // stream kernels: Pd [k-step][16-vertex tile][coord][hi | lo] and W [16-vertex tile][3 or 5 fragments], 1 KiB pieces in
+        // MFMA operand order (lane = row + 16 k-group, 8 halfs); vertex tiles padded to whole 128-vertex groups
+        const int nv16 = (n + 127) / 128 * 8, SK = KX / 2, NWF = m->stream ? 3 : 5;
+        vs.nv16 = nv16;
+        std::vector<k2b::k2b_half> spd((size_t)SK * nv16 * 6 * 512, (k2b::k2b_half)0.f), sw((size_t)nv16 * NWF * 512, (k2b::k2b_half)0.f);
+        for (int i = 0; i < n; ++i) {
+            const int v16 = i >> 4, r = i & 15;
+            for (int c = 0; c < 3; ++c)
+                for (int k = 0; k < KX * 16; ++k) {      // the split values already sit in pdh / pdl: same k, same scale
+                    const size_t src = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
+                    const size_t dst = ((((size_t)(k >> 5) * nv16 + v16) * 3 + c) * 2) * 512 + (size_t)((((k >> 3) & 3) * 16 + r) * 8 + (k & 7));
+                    spd[dst] = pdh[src];
+                    spd[dst + 512] = pdl[src];
+                }
+            k2b::k2b_half* wt = sw.data() + (size_t)v16 * NWF * 512;
+            auto at = [&](int frag, int group, int k) -> k2b::k2b_half& { return wt[(size_t)frag * 512 + (size_t)((group * 16 + r) * 8 + k)]; };
+            for (int j = 0; j < J; ++j) {
+                const float w = lbs_weights[(size_t)ids[i] * J + j];
+                const k2b::k2b_half hi = (k2b::k2b_half)w, lo = (k2b::k2b_half)(w - (float)hi);
+                const int gj = j >> 3, kj = j & 7;
+                if (m->stream) { at(0, gj, kj) = hi; at(1, gj, kj) = hi; at(2, gj, kj) = lo; }
+                else if (gj < 4) { at(0, gj, kj) = hi; at(2, gj, kj) = lo; }
+                else { at(1, gj - 4, kj) = hi; at(4, gj - 4, kj) = hi; at(3, gj - 4, kj) = lo; }
+            }
+            // last group of the fragment that meets the PAD group of A: ONES; of the one that meets ZERO: the joint tag
+            for (int k = 0; k < 3; ++k) at(m->stream ? 0 : 1, 3, k) = (k2b::k2b_half)1.f;
+            if (!tag.empty() && tag[i]) at(m->stream ? 1 : 4, 3, 0) = (k2b::k2b_half)(float)tag[i];
+        }
+        if ((e = upload(&vs.spd, spd.data(), spd.size())) != hipSuccess) return (int)e;
+        if ((e = upload(&vs.sw, sw.data(), sw.size())) != hipSuccess) return (int)e;
+    }
+    if (m->stream || m->stream_x) return 0;          // the tile kernel's images stay on the host (SMPL-X: 64 MB less per GPU)
+    if ((e = upload(&vs.w2, w2.data(), w2.size())) != hipSuccess) return (int)e;
+    if ((e = upload(&vs.pdh, pdh.data(), pdh.size())) != hipSuccess) return (int)e;
+    if ((e = upload(&vs.pdl, pdl.data(), pdl.size())) != hipSuccess) return (int)e;
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 0u; }
+uint32_t k2b_version(void) { return (1u << 16) | 1u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
@@ -186,6 +299,7 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
     HIP_TRY(upload(&m->lbs_weights, lbs_weights, (size_t)V * J));
     HIP_TRY(upload(&m->parents, parents, (size_t)J));
     HIP_TRY(upload(&m->extra_ids, extra_vertex_ids, (size_t)E));
+    m->h_extra_ids.assign(extra_vertex_ids, extra_vertex_ids + E);
 
     // LBS operands: B side of the two GEMMs, f16 hi/lo in fragment order (k2b_lbs.hip)
     {
@@ -198,92 +312,6 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
         m->stream = K2B_LBS_STREAM && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
         m->stream_x = K2B_LBS_STREAM && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
         HIP_TRY(hipMalloc((void**)&m->dump, 64 * 1024));     // 64 x 3 floats used; the rest is room for diagnostic builds
-        // tag[i] = 1 + e when vertex i of the set is the vertex of output joint J + e (mesh set only), else 0
-        auto build = [&](k2b_model::VertexSet& vs, const std::vector<int>& ids, const std::vector<int>& tag) -> int {
-            const int n = (int)ids.size();
-            vs.num = n;
-            vs.v_tiles = (n + 31) / 32;
-            const int vp = vs.v_tiles * 32;
-            std::vector<k2b::k2b_half> pdh((size_t)KX * 3 * vp * 16, (k2b::k2b_half)0.f), pdl(pdh.size(), (k2b::k2b_half)0.f);
-            for (int i = 0; i < n; ++i) {
-                const int v = ids[i];
-                for (int c = 0; c < 3; ++c) {
-                    auto put = [&](int k, k2b::k2b_half hi, k2b::k2b_half lo) {
-                        const size_t o = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
-                        pdh[o] = hi;
-                        pdl[o] = lo;
-                    };
-                    auto split = [&](int k, float x) -> float {   // returns what two f16 terms leave over
-                        const float xs = x * k2b::kPdScale;
-                        const k2b::k2b_half hi = (k2b::k2b_half)xs;
-                        const k2b::k2b_half lo = (k2b::k2b_half)(xs - (float)hi);
-                        put(k, hi, lo);
-                        return xs - (float)hi - (float)lo;
-                    };
-                    for (int k = 0; k < P; ++k) split(k, posedirs[(size_t)k * 3 * V + 3 * v + c]);
-                    for (int k = 0; k < NB; ++k) split(P + k, shapedirs[((size_t)v * 3 + c) * NB + k]);
-                    const float rest = split(P + NB, v_template[(size_t)v * 3 + c]);
-                    // the template is metre-scale: keep its third term as an extra K row (feature = 1)
-                    const k2b::k2b_half rh = (k2b::k2b_half)rest;
-                    put(P + NB + 1, rh, (k2b::k2b_half)(rest - (float)rh));
-                }
-            }
-            // tile-kernel layout of W: [16-vertex tile][hi groups | lo groups | ONES | ZERO][16 rows][8 joints]
-            const int GA = k2b::tile_groups_a(J), NGP = k2b::tile_ngp(GA), v16 = vs.v_tiles * 2;
-            std::vector<k2b::k2b_half> w2((size_t)v16 * NGP * 128, (k2b::k2b_half)0.f);
-            for (int t = 0; t < v16; ++t)
-                for (int r = 0; r < 16; ++r) {
-                    const int i = t * 16 + r;
-                    k2b::k2b_half* rowp = w2.data() + ((size_t)t * NGP * 16 + r) * 8;
-                    if (i < n)
-                        for (int j = 0; j < J; ++j) {
-                            const float w = lbs_weights[(size_t)ids[i] * J + j];
-                            const k2b::k2b_half hi = (k2b::k2b_half)w;
-                            rowp[(size_t)(j >> 3) * 128 + (j & 7)] = hi;
-                            rowp[(size_t)(GA + (j >> 3)) * 128 + (j & 7)] = (k2b::k2b_half)(w - (float)hi);
-                        }
-                    for (int k = 0; k < 3; ++k) rowp[(size_t)(2 * GA) * 128 + k] = (k2b::k2b_half)1.f;   // ONES: picks up the PAD terms
-                    if (i < n && !tag.empty() && tag[i]) rowp[(size_t)(2 * GA + 1) * 128] = (k2b::k2b_half)(float)tag[i];   // ZERO group: joint tag
-                }
-            hipError_t e;
-            if (m->stream || m->stream_x) {
-                // stream kernels: Pd [k-step][16-vertex tile][coord][hi | lo] and W [16-vertex tile][3 or 5 fragments], 1 KiB pieces in
-                // MFMA operand order (lane = row + 16 k-group, 8 halfs); vertex tiles padded to whole 128-vertex groups
-                const int nv16 = (n + 127) / 128 * 8, SK = KX / 2, NWF = m->stream ? 3 : 5;
-                vs.nv16 = nv16;
-                std::vector<k2b::k2b_half> spd((size_t)SK * nv16 * 6 * 512, (k2b::k2b_half)0.f), sw((size_t)nv16 * NWF * 512, (k2b::k2b_half)0.f);
-                for (int i = 0; i < n; ++i) {
-                    const int v16 = i >> 4, r = i & 15;
-                    for (int c = 0; c < 3; ++c)
-                        for (int k = 0; k < KX * 16; ++k) {      // the split values already sit in pdh / pdl: same k, same scale
-                            const size_t src = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
-                            const size_t dst = ((((size_t)(k >> 5) * nv16 + v16) * 3 + c) * 2) * 512 + (size_t)((((k >> 3) & 3) * 16 + r) * 8 + (k & 7));
-                            spd[dst] = pdh[src];
-                            spd[dst + 512] = pdl[src];
-                        }
-                    k2b::k2b_half* wt = sw.data() + (size_t)v16 * NWF * 512;
-                    auto at = [&](int frag, int group, int k) -> k2b::k2b_half& { return wt[(size_t)frag * 512 + (size_t)((group * 16 + r) * 8 + k)]; };
-                    for (int j = 0; j < J; ++j) {
-                        const float w = lbs_weights[(size_t)ids[i] * J + j];
-                        const k2b::k2b_half hi = (k2b::k2b_half)w, lo = (k2b::k2b_half)(w - (float)hi);
-                        const int gj = j >> 3, kj = j & 7;
-                        if (m->stream) { at(0, gj, kj) = hi; at(1, gj, kj) = hi; at(2, gj, kj) = lo; }
-                        else if (gj < 4) { at(0, gj, kj) = hi; at(2, gj, kj) = lo; }
-                        else { at(1, gj - 4, kj) = hi; at(4, gj - 4, kj) = hi; at(3, gj - 4, kj) = lo; }
-                    }
-                    // last group of the fragment that meets the PAD group of A: ONES; of the one that meets ZERO: the joint tag
-                    for (int k = 0; k < 3; ++k) at(m->stream ? 0 : 1, 3, k) = (k2b::k2b_half)1.f;
-                    if (!tag.empty() && tag[i]) at(m->stream ? 1 : 4, 3, 0) = (k2b::k2b_half)(float)tag[i];
-                }
-                if ((e = upload(&vs.spd, spd.data(), spd.size())) != hipSuccess) return (int)e;
-                if ((e = upload(&vs.sw, sw.data(), sw.size())) != hipSuccess) return (int)e;
-            }
-            if (m->stream || m->stream_x) return 0;          // the tile kernel's images stay on the host (SMPL-X: 64 MB less per GPU)
-            if ((e = upload(&vs.w2, w2.data(), w2.size())) != hipSuccess) return (int)e;
-            if ((e = upload(&vs.pdh, pdh.data(), pdh.size())) != hipSuccess) return (int)e;
-            if ((e = upload(&vs.pdl, pdl.data(), pdl.size())) != hipSuccess) return (int)e;
-            return 0;
-        };
         std::vector<int> all(V), ex(extra_vertex_ids, extra_vertex_ids + E), tag(V, 0);
         for (int v = 0; v < V; ++v) all[v] = v;
         // an output joint rides in the W image of its vertex (k2b_lbs.hip) - unless two joints share a vertex or the index
@@ -294,7 +322,8 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
             tag[extra_vertex_ids[e]] = e + 1;
         }
         if (!m->joints_in_mesh) std::fill(tag.begin(), tag.end(), 0);
-        if (build(m->mesh, all, tag) != 0 || (E > 0 && build(m->extra, ex, std::vector<int>()) != 0))
+        if (build_vertex_set(m, m->mesh, all, tag, v_template, shapedirs, posedirs, lbs_weights, V) != 0 ||
+            (E > 0 && build_vertex_set(m, m->extra, ex, std::vector<int>(), v_template, shapedirs, posedirs, lbs_weights, V) != 0))
             return fail(K2B_ERR_HIP, "k2b_model_create: uploading LBS operands failed");
     }
 
@@ -438,6 +467,13 @@ void k2b_model_destroy(k2b_model* m) {
     if (m->extra_ids) (void)hipFree(m->extra_ids);
     if (m->tree) (void)hipFree(m->tree);
     for (auto& kv : m->adam_tables) (void)hipFree(kv.second.dev);
+    for (auto& kv : m->surface_tables) (void)hipFree(kv.second.dev);
+    if (m->lmk_ids) (void)hipFree(m->lmk_ids);
+    if (m->lmk_seq) (void)hipFree(m->lmk_seq);
+    if (m->lmk_w) (void)hipFree(m->lmk_w);
+    if (m->ws_lmk) (void)hipFree(m->ws_lmk);
+    k2b::k2b_half* ll[] = {m->lmk.pdh, m->lmk.pdl, m->lmk.w2, m->lmk.spd, m->lmk.sw};
+    for (k2b::k2b_half* p : ll) if (p) (void)hipFree(p);
     delete m;
 }
 
@@ -454,6 +490,88 @@ int k2b_model_dims(const k2b_model* m, int32_t* V, int32_t* J, int32_t* NB, int3
     if (J) *J = m->J;
     if (NB) *NB = m->NB;
     if (E) *E = m->E;
+    return K2B_OK;
+}
+
+}  // extern "C"
+
+namespace {
+int reserve_lbs_workspace(k2b_model* m, int bpad);
+// k2b_model_set_landmarks after validation, caller holds m->mu
+int set_landmarks_locked(k2b_model* m, int32_t L, const int32_t* vertex_ids, const float* bary) {
+    m->h_lmk_ids.assign(vertex_ids, vertex_ids + 3 * L);
+    m->h_lmk_w.assign(bary, bary + 3 * L);
+    std::vector<int> seq(3 * L);
+    for (int i = 0; i < 3 * L; ++i) seq[i] = i;
+    HIP_TRY(upload(&m->lmk_ids, vertex_ids, (size_t)3 * L));
+    HIP_TRY(upload(&m->lmk_w, bary, (size_t)3 * L));
+    HIP_TRY(upload(&m->lmk_seq, seq.data(), seq.size()));
+    // LBS operands of the 3L vertices: their rows gathered on the device, then laid out on the host like the extra joints'
+    const int n = 3 * L, J = m->J, NB = m->NB, PF = m->P;
+    const size_t nf = (size_t)n * 3 + (size_t)n * 3 * NB + (size_t)PF * 3 * n + (size_t)n * J;
+    float* g = nullptr;
+    HIP_TRY(hipMalloc((void**)&g, nf * sizeof(float)));
+    float *gvt = g, *gsd = gvt + (size_t)n * 3, *gpd = gsd + (size_t)n * 3 * NB, *glw = gpd + (size_t)PF * 3 * n;
+    hipError_t e = k2b::launch_surface_gather(m->v_template, m->shapedirs, m->posedirs, m->lbs_weights, m->lmk_ids, n, m->V, J, NB,
+                                              gvt, gsd, gpd, glw, nullptr);
+    std::vector<float> h(nf);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h.data(), g, nf * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(g);
+    if (e != hipSuccess) return fail(K2B_ERR_HIP, "k2b_model_set_landmarks: gathering the landmark vertices failed: %s", hipGetErrorString(e));
+    const float* hvt = h.data();
+    const float *hsd = hvt + (size_t)n * 3, *hpd = hsd + (size_t)n * 3 * NB, *hlw = hpd + (size_t)PF * 3 * n;
+    if (build_vertex_set(m, m->lmk, seq, std::vector<int>(), hvt, hsd, hpd, hlw, n) != 0)
+        return fail(K2B_ERR_HIP, "k2b_model_set_landmarks: uploading LBS operands failed");
+    m->L = L;
+    // a workspace reserved before this call covers the landmark vertices too
+    if (m->ws_bpad > 0) return reserve_lbs_workspace(m, m->ws_bpad);
+    return K2B_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int k2b_model_set_landmarks(k2b_model* m, int32_t L, const int32_t* vertex_ids, const float* bary) {
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: model is NULL");
+    if (m->lmk_set) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: the model already has a landmark table");
+    if (L < 0 || L > k2b::kMaxLandmarks)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: num_landmarks=%d (0..%d)", L, k2b::kMaxLandmarks);
+    if (L > 0 && (!vertex_ids || !bary)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: NULL table");
+    for (int i = 0; i < 3 * L; ++i) {
+        if (vertex_ids[i] < 0 || vertex_ids[i] >= m->V)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: vertex_ids[%d][%d]=%d outside [0,%d)", i / 3, i % 3, vertex_ids[i], m->V);
+        if (!std::isfinite(bary[i]))
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: bary[%d][%d] is not finite", i / 3, i % 3);
+    }
+    for (int l = 0; l < L; ++l) {
+        const double sum = (double)bary[3 * l] + bary[3 * l + 1] + bary[3 * l + 2];
+        if (std::fabs(sum - 1.0) > 1e-3)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_set_landmarks: the weights of landmark %d sum to %g, not 1 (barycentric)", l, sum);
+    }
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (L == 0) { m->lmk_set = true; return K2B_OK; }
+    const int rc = set_landmarks_locked(m, L, vertex_ids, bary);
+    if (rc != K2B_OK) {                                       // nothing of a failed call stays on the handle: it may be retried
+        int* ip[] = {m->lmk_ids, m->lmk_seq};
+        for (int* p : ip) if (p) (void)hipFree(p);
+        if (m->lmk_w) (void)hipFree(m->lmk_w);
+        if (m->ws_lmk) (void)hipFree(m->ws_lmk);
+        k2b::k2b_half* ll[] = {m->lmk.pdh, m->lmk.pdl, m->lmk.w2, m->lmk.spd, m->lmk.sw};
+        for (k2b::k2b_half* p : ll) if (p) (void)hipFree(p);
+        m->lmk_ids = m->lmk_seq = nullptr; m->lmk_w = nullptr; m->ws_lmk = nullptr; m->ws_lmk_bpad = 0;
+        m->lmk = k2b_model::VertexSet{};
+        m->h_lmk_ids.clear(); m->h_lmk_w.clear();
+        m->L = 0;
+        return rc;
+    }
+    m->lmk_set = true;
+    return K2B_OK;
+}
+
+int k2b_model_num_landmarks(const k2b_model* m, int32_t* L) {
+    if (!m || !L) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_model_num_landmarks: NULL argument");
+    *L = m->L;
     return K2B_OK;
 }
 
@@ -665,10 +783,117 @@ int folded_prior(k2b_prior* p, int Dv, k2b_prior::Folded* out) {
     return K2B_OK;
 }
 
+// Compact table of the surface-point term for targets sel[t] (model joint indices >= J) in target columns col[t]: the U distinct
+// vertices in order of first appearance, their rows gathered on the device, the (slot, weight) pairs of every target and the
+// pairs of every vertex (CSR).  Cached per model and selection; the first use of a selection synchronises `stream`.
+int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<int>& col, hipStream_t stream, k2b::SurfaceTermArgs* out) {
+    const int J = m->J, E = m->E, NB = m->NB, PF = m->P, T = (int)sel.size();
+    if (T < 1 || T > k2b::kSurfMaxTargets)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: %d surface targets (vertex-selected joints and landmarks), at most %d per call", T,
+                    k2b::kSurfMaxTargets);
+    std::vector<int> key;
+    for (int t = 0; t < T; ++t) { key.push_back(sel[t]); key.push_back(col[t]); }
+    std::lock_guard<std::mutex> lk(m->mu);
+    auto it = m->surface_tables.find(key);
+    if (it != m->surface_tables.end()) {
+        it->second.last_use = ++m->surface_clock;
+        *out = it->second.a;
+        return K2B_OK;
+    }
+    std::vector<int> ids, pair_u(3 * T, 0);
+    std::vector<float> pair_w(3 * T, 0.f);
+    std::map<int, int> slot;
+    for (int t = 0; t < T; ++t) {
+        const int j = sel[t];
+        for (int k = 0; k < 3; ++k) {
+            int v;
+            float w;
+            if (j < J + E) {
+                if (k > 0) break;
+                v = m->h_extra_ids[j - J]; w = 1.f;
+            } else {
+                v = m->h_lmk_ids[(j - J - E) * 3 + k]; w = m->h_lmk_w[(j - J - E) * 3 + k];
+            }
+            auto ins = slot.emplace(v, (int)ids.size());
+            if (ins.second) ids.push_back(v);
+            pair_u[t * 3 + k] = ins.first->second;
+            pair_w[t * 3 + k] = w;
+        }
+    }
+    const int U = (int)ids.size();
+    std::vector<int> inv_off(U + 1, 0), inv_t;
+    std::vector<float> inv_w;
+    {
+        std::vector<std::vector<std::pair<int, float>>> lists(U);
+        for (int t = 0; t < T; ++t)
+            for (int k = 0; k < 3; ++k)
+                if (pair_w[t * 3 + k] != 0.f) lists[pair_u[t * 3 + k]].push_back({t, pair_w[t * 3 + k]});
+        for (int u = 0; u < U; ++u) {
+            for (const auto& p : lists[u]) { inv_t.push_back(p.first); inv_w.push_back(p.second); }
+            inv_off[u + 1] = (int)inv_t.size();
+        }
+    }
+    const int n = (int)inv_t.size();
+    // one allocation: floats (vt, sd, pd, lw, pair_w, inv_w), then ints (pair_u, sel_k, inv_off, inv_t, ids)
+    const size_t n_tab = (size_t)U * 3 + (size_t)U * 3 * NB + (size_t)PF * 3 * U + (size_t)U * J;
+    const size_t n_f = n_tab + 3 * (size_t)T + (size_t)n;
+    const size_t n_i = 3 * (size_t)T + T + (U + 1) + (size_t)n + U;
+    std::vector<float> hf(3 * (size_t)T + n);
+    std::copy(pair_w.begin(), pair_w.end(), hf.begin());
+    std::copy(inv_w.begin(), inv_w.end(), hf.begin() + 3 * T);
+    std::vector<int> hi;
+    hi.insert(hi.end(), pair_u.begin(), pair_u.end());
+    hi.insert(hi.end(), col.begin(), col.end());
+    hi.insert(hi.end(), inv_off.begin(), inv_off.end());
+    hi.insert(hi.end(), inv_t.begin(), inv_t.end());
+    hi.insert(hi.end(), ids.begin(), ids.end());
+    constexpr size_t kMaxSurfaceTables = 64;
+    if (m->surface_tables.size() >= kMaxSurfaceTables) {      // evict the least recently used table
+        auto victim = m->surface_tables.begin();
+        for (auto jt = m->surface_tables.begin(); jt != m->surface_tables.end(); ++jt)
+            if (jt->second.last_use < victim->second.last_use) victim = jt;
+        HIP_TRY(hipDeviceSynchronize());                     // a launch in flight may still read it
+        HIP_TRY(hipFree(victim->second.dev));
+        m->surface_tables.erase(victim);
+    }
+    k2b_model::SurfaceTable st;
+    HIP_TRY(hipMalloc(&st.dev, n_f * sizeof(float) + n_i * sizeof(int)));
+    float* f = static_cast<float*>(st.dev);
+    int* ip = reinterpret_cast<int*>(f + n_f);
+    auto release = [&](int rc) { (void)hipFree(st.dev); return rc; };
+    if (hipMemcpy(f + n_tab, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ip, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return release(fail(K2B_ERR_HIP, "k2b_fit_world: uploading the surface-term table failed"));
+    k2b::SurfaceTermArgs& a = st.a;
+    a.vt = f; a.sd = f + (size_t)U * 3; a.pd = a.sd + (size_t)U * 3 * NB; a.lw = a.pd + (size_t)PF * 3 * U;
+    a.pair_w = f + n_tab; a.inv_w = a.pair_w + 3 * T;
+    a.pair_u = ip; a.sel_k = ip + 3 * T; a.inv_off = a.sel_k + T; a.inv_t = a.inv_off + U + 1;
+    const int* dids = a.inv_t + n;
+    a.j_template = m->j_template; a.j_dirs = m->j_dirs; a.parents = m->parents;
+    a.num_u = U; a.num_betas = NB; a.num_joints = J; a.num_sel = T;
+    if (k2b::launch_surface_gather(m->v_template, m->shapedirs, m->posedirs, m->lbs_weights, dids, U, m->V, J, NB, f, const_cast<float*>(a.sd),
+                                   const_cast<float*>(a.pd), const_cast<float*>(a.lw), stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+        return release(fail(K2B_ERR_HIP, "k2b_fit_world: gathering the surface-term table failed"));
+    st.last_use = ++m->surface_clock;
+    m->surface_tables[key] = st;
+    *out = a;
+    return K2B_OK;
+}
+
+// Targets with model index >= J go to the vertex-term kernel when they are at most 32 extra joints (the path of the first
+// release, bit for bit), to the surface-point kernel otherwise (landmarks among them, or more than 32).
+bool needs_surface_kernel(const k2b_model* m, const std::vector<int>& sel) {
+    if (sel.size() > 32) return true;
+    for (int j : sel)
+        if (j >= m->J + m->E) return true;
+    return false;
+}
+
 extern "C++" {
 template <class Args, class Launch>
 int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a, const float* tr_prior_src, int frozen_shape,
-                            const std::vector<int>& vsel, const std::vector<int>& vcol, hipStream_t stream, Launch launch_eval);
+                            const std::vector<int>& ssel, const std::vector<int>& vcol, hipStream_t stream, Launch launch_eval);
 }
 
 // large trees (SMPL-H / SMPL-X), or a prior over a prefix of the body pose: k2b_fit_tree.hip
@@ -683,7 +908,7 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     if (cfg->transl_prior_weight != 0.0f || tr_prior)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the translation prior (camera-space fitter) is not built for %d-joint models", J);
     if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_frames=%d", B);
-    if (K < 1 || K > J + model->E) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_targets=%d out of range", K);
+    if (K < 1 || K > J + model->E + model->L) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_targets=%d out of range", K);
     if (!model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index is NULL");
     if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_iters=%d", cfg->num_iters);
     if (!(cfg->step_size >= 0.0) || !(cfg->adam_beta1 >= 0.0 && cfg->adam_beta1 < 1.0) || !(cfg->adam_beta2 >= 0.0 && cfg->adam_beta2 < 1.0))
@@ -694,13 +919,15 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     k2b::FitTreeArgs a{};
     for (int l = 0; l < 64; ++l) a.lane_target[l] = -1;
     int maxd = 0, num_kinematic = 0;
-    std::vector<int> vsel, vcol;             // vertex-selected joints: index into the model's extra joints, target column
+    std::vector<int> vsel, vcol;             // surface targets (extra joints, landmarks): model index, target column
     for (int k = 0; k < K; ++k) {
         const int j = model_joint_index[k];
-        if (j < 0 || j >= J + model->E) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index[%d]=%d out of range", k, j);
-        if (j >= J) {                        // vertex-selected joint: its term comes from k2b_vertex_term_kernel
-            if ((int)vsel.size() >= 32) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: more than 32 vertex-selected joints among the targets");
-            vsel.push_back(j - J);
+        if (j < 0 || j >= J + model->E + model->L)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index[%d]=%d out of range", k, j);
+        if (j >= J) {                        // surface target: its term comes from k2b_vertex_term_kernel / k2b_surface_term_kernel
+            if ((int)vsel.size() >= k2b::kSurfMaxTargets)
+                return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: more than %d surface targets (vertex-selected joints and landmarks)", k2b::kSurfMaxTargets);
+            vsel.push_back(j);
             vcol.push_back(k);
             continue;
         }
@@ -790,8 +1017,12 @@ namespace {
 extern "C++" {
 template <class Args, class Launch>
 int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a, const float* tr_prior_src, int frozen_shape,
-                            const std::vector<int>& vsel, const std::vector<int>& vcol, hipStream_t stream, Launch launch_eval) {
+                            const std::vector<int>& ssel, const std::vector<int>& vcol, hipStream_t stream, Launch launch_eval) {
     const int B = a.num_frames, NB = model->NB, D = 3 * (model->J - 1), P = 3 + D + NB + 3;
+    const bool surface = needs_surface_kernel(model, ssel);
+    k2b::SurfaceTermArgs s{};
+    if (surface)
+        if (const int rc = surface_table(model, ssel, vcol, stream, &s); rc != K2B_OK) return rc;
     const int iters = cfg->num_iters;
     float2 *coef = nullptr, *coef_eval = nullptr;
     if (const int rc = adam_table(model, cfg, stream, &coef); rc != K2B_OK) return rc;
@@ -829,8 +1060,8 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
     v.j_template = model->j_template; v.j_dirs = model->j_dirs; v.parents = model->parents; v.extra_ids = model->extra_ids;
     v.num_vertices = model->V; v.num_betas = NB; v.num_joints = model->J;
     v.frozen_shape = frozen_shape;
-    v.num_frames = B; v.num_sel = (int)vsel.size();
-    for (size_t e = 0; e < vsel.size(); ++e) { v.sel[e] = vsel[e]; v.sel_k[e] = vcol[e]; }
+    v.num_frames = B; v.num_sel = surface ? 0 : (int)ssel.size();
+    for (int e = 0; e < v.num_sel; ++e) { v.sel[e] = ssel[e] - model->J; v.sel_k[e] = vcol[e]; }
     v.num_targets = a.num_targets; v.targets = a.j3d; v.conf = a.conf; v.conf_per_frame = a.conf_per_frame;
     v.sigma = a.sigma; v.joint_w = a.joint_w;
     v.go = a.go_out; v.bp = a.bp_out; v.be = a.be_out; v.tr = a.tr_out;
@@ -840,13 +1071,26 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
     v.adam_m = mbuf; v.adam_v = vbuf;
     v.one_minus_beta1 = a.one_minus_beta1; v.beta2 = a.beta2; v.one_minus_beta2 = a.one_minus_beta2; v.eps = a.eps;
     v.opt_mask = a.opt_mask;
+    // the surface kernel: the same call fields
+    s.num_frames = B; s.num_targets = v.num_targets; s.targets = v.targets; s.conf = v.conf; s.conf_per_frame = v.conf_per_frame;
+    s.sigma = v.sigma; s.joint_w = v.joint_w;
+    s.go = v.go; s.bp = v.bp; s.be = v.be; s.tr = v.tr;
+    s.go_w = v.go_w; s.bp_w = v.bp_w; s.be_w = v.be_w; s.tr_w = v.tr_w;
+    s.loss_in = v.loss_in; s.grad_in = v.grad_in; s.adam_m = v.adam_m; s.adam_v = v.adam_v;
+    s.one_minus_beta1 = v.one_minus_beta1; s.beta2 = v.beta2; s.one_minus_beta2 = v.one_minus_beta2; s.eps = v.eps;
+    s.opt_mask = v.opt_mask; s.frozen_shape = v.frozen_shape;
     for (int it = 0; it < iters; ++it) {
         K2B_TRY_WS(launch_eval(a));
         v.adam_coef = coef + it;
         const bool last = it == iters - 1;
         v.loss_out = last ? loss_sink : lbuf;        // (lbuf: read and written by the same lane)
         v.grad_out = last ? user_grad : nullptr;
-        K2B_TRY_WS(k2b::launch_vertex_term(v, stream));
+        if (surface) {
+            s.adam_coef = v.adam_coef; s.loss_out = v.loss_out; s.grad_out = v.grad_out;
+            K2B_TRY_WS(k2b::launch_surface_term(s, stream));
+        } else {
+            K2B_TRY_WS(k2b::launch_vertex_term(v, stream));
+        }
     }
 #undef K2B_TRY_WS
     return cleanup(K2B_OK);
@@ -875,7 +1119,7 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
         return fit_tree(model, const_cast<k2b_prior*>(prior), cfg, prior_dims, B, K, model_joint_index, j3d, conf, go_in, bp_in, be_in, tr_in,
                         preserve, tr_prior, go_out, bp_out, be_out, tr_out, loss_out, grad_out, stream, chain_len, chain_iters);
     if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_frames=%d", B);
-    if (K < 1 || K > model->J + model->E) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_targets=%d out of range", K);
+    if (K < 1 || K > model->J + model->E + model->L) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_targets=%d out of range", K);
     if (!model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index is NULL");
     if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_iters=%d", cfg->num_iters);
     if (!(cfg->step_size >= 0.0) || !(cfg->adam_beta1 >= 0.0 && cfg->adam_beta1 < 1.0) || !(cfg->adam_beta2 >= 0.0 && cfg->adam_beta2 < 1.0))
@@ -886,15 +1130,17 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
 
     k2b::FitArgs a{};
     int lane_target[k2b::kFitJoints];
-    std::vector<int> vsel, vcol;             // vertex-selected joints: index into the model's extra joints, target column
+    std::vector<int> vsel, vcol;             // surface targets (extra joints, landmarks): model index, target column
     int num_kinematic = 0;
     for (int j = 0; j < k2b::kFitJoints; ++j) lane_target[j] = -1;
     for (int k = 0; k < K; ++k) {
         const int j = model_joint_index[k];
-        if (j < 0 || j >= model->J + model->E) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index[%d]=%d out of range", k, j);
-        if (j >= model->J) {                 // vertex-selected joint: its term comes from k2b_vertex_term_kernel
-            if ((int)vsel.size() >= 32) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: more than 32 vertex-selected joints among the targets");
-            vsel.push_back(j - model->J);
+        if (j < 0 || j >= model->J + model->E + model->L)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index[%d]=%d out of range", k, j);
+        if (j >= model->J) {                 // surface target: its term comes from k2b_vertex_term_kernel / k2b_surface_term_kernel
+            if ((int)vsel.size() >= k2b::kSurfMaxTargets)
+                return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: more than %d surface targets (vertex-selected joints and landmarks)", k2b::kSurfMaxTargets);
+            vsel.push_back(j);
             vcol.push_back(k);
             continue;
         }
@@ -1229,6 +1475,14 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
 namespace {
 // grow-only per-model workspace of the per-frame LBS operands (caller holds m->mu)
 int reserve_lbs_workspace(k2b_model* m, int bpad) {
+    if (m->L > 0 && bpad > m->ws_lmk_bpad) {                 // the landmark vertices of joints-only calls
+        HIP_TRY(hipDeviceSynchronize());
+        if (m->ws_lmk) HIP_TRY(hipFree(m->ws_lmk));
+        m->ws_lmk = nullptr;
+        m->ws_lmk_bpad = 0;
+        HIP_TRY(hipMalloc((void**)&m->ws_lmk, (size_t)bpad * 3 * m->L * 3 * sizeof(float)));
+        m->ws_lmk_bpad = bpad;
+    }
     if (bpad <= m->ws_bpad) return K2B_OK;
     HIP_TRY(hipDeviceSynchronize());
     k2b::k2b_half** ws[] = {&m->wsXh, &m->wsXl, &m->wsA2};
@@ -1271,7 +1525,8 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
     }
     k2b::PoseArgs pa{};
     pa.j_basis_lane = m->j_basis_lane; pa.parents = m->parents;
-    pa.num_joints = m->J; pa.num_betas = m->NB; pa.num_out_joints = m->J + m->E;
+    const int ostride = m->J + m->E + m->L;                  // rows of joints_out: J kinematic, E extra vertices, L landmarks
+    pa.num_joints = m->J; pa.num_betas = m->NB; pa.num_out_joints = ostride;
     pa.num_frames = B; pa.frames_padded = bpad; pa.k_steps_x = m->k_steps_x;
     pa.go = go; pa.bp = bp; pa.be = be; pa.tr = tr;
     if (m->groups_a != 3 && m->groups_a != 7)
@@ -1286,7 +1541,7 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
             sa.f32_tiles = bpad / 32; sa.nv16 = vs.nv16;
             sa.num_frames = B; sa.num_out = vs.num; sa.out = out; sa.out_stride = stride; sa.out_row0 = row0;
             sa.dump = m->dump;
-            sa.joints_out = joint_copies; sa.joints_stride = m->J + m->E; sa.joints_row0 = m->J;
+            sa.joints_out = joint_copies; sa.joints_stride = ostride; sa.joints_row0 = m->J;
             return m->stream ? k2b::launch_skin_stream(sa, device_cus(), stream) : k2b::launch_skin_stream_x(sa, device_cus(), stream);
         }
         k2b::TileArgs ta{};
@@ -1294,7 +1549,7 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
         ta.groups_a = m->groups_a; ta.k_steps_x = m->k_steps_x; ta.f_tiles = bpad / 32; ta.v_tiles = vs.v_tiles;
         ta.num_frames = B; ta.num_out = vs.num; ta.out = out; ta.out_stride = stride; ta.out_row0 = row0;
         ta.dump = m->dump;
-        ta.joints_out = joint_copies; ta.joints_stride = m->J + m->E; ta.joints_row0 = m->J;
+        ta.joints_out = joint_copies; ta.joints_stride = ostride; ta.joints_row0 = m->J;
         return k2b::launch_skin_tiles(ta, device_cus(), stream);
     };
     if (vertices_out) {
@@ -1302,9 +1557,17 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
         const bool copies = joints_out && m->E > 0 && m->joints_in_mesh;
         HIP_TRY(skin(m->mesh, vertices_out, m->V, 0, copies ? joints_out : nullptr));
         if (joints_out && m->E > 0 && !copies)
-            HIP_TRY(k2b::launch_gather_joints(vertices_out, m->extra_ids, joints_out, B, m->V, m->J, m->E, stream));
-    } else if (joints_out && m->E > 0) {
-        HIP_TRY(skin(m->extra, joints_out, m->J + m->E, m->J, nullptr));
+            HIP_TRY(k2b::launch_gather_joints(vertices_out, m->extra_ids, joints_out, B, m->V, m->J, m->E, ostride, stream));
+        // landmarks: a stream-ordered pass over this call's vertices
+        if (joints_out && m->L > 0)
+            HIP_TRY(k2b::launch_landmarks(vertices_out, m->V, m->lmk_ids, m->lmk_w, joints_out, ostride, m->J + m->E, B, m->L, stream));
+        return K2B_OK;
+    }
+    if (joints_out && m->E > 0) HIP_TRY(skin(m->extra, joints_out, ostride, m->J, nullptr));
+    if (joints_out && m->L > 0) {
+        // landmarks without the mesh: the 3L vertices skinned alone into the model's workspace (sized above), then combined
+        HIP_TRY(skin(m->lmk, m->ws_lmk, 3 * m->L, 0, nullptr));
+        HIP_TRY(k2b::launch_landmarks(m->ws_lmk, 3 * m->L, m->lmk_seq, m->lmk_w, joints_out, ostride, m->J + m->E, B, m->L, stream));
     }
     return K2B_OK;
 }
@@ -1334,6 +1597,34 @@ int k2b_vertex_term(const k2b_model* model_c, int32_t B, int32_t E_sel, const in
     a.sigma = sigma; a.joint_w = joint_loss_weight;
     a.go = go; a.bp = bp; a.be = be; a.tr = tr; a.loss_out = loss_out; a.grad_out = grad_out;
     HIP_TRY(k2b::launch_vertex_term(a, stream));
+    return K2B_OK;
+}
+
+int k2b_surface_term(const k2b_model* model_c, int32_t B, int32_t T, const int32_t* model_joint_index, const float* targets,
+                     const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight, const float* go, const float* bp,
+                     const float* be, const float* tr, float* loss_out, float* grad_out, void* stream_v) {
+    k2b_model* m = const_cast<k2b_model*>(model_c);
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model is NULL");
+    if (B < 0 || T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: negative size");
+    if (B == 0 || T == 0) return K2B_OK;
+    if (T > k2b::kSurfMaxTargets) return fail(K2B_ERR_UNSUPPORTED, "k2b_surface_term: %d targets, at most %d per call", T, k2b::kSurfMaxTargets);
+    if (!model_joint_index || !targets || !go || !bp || !be || !tr || !loss_out || !grad_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: NULL buffer");
+    std::vector<int> sel(T), col(T);
+    for (int t = 0; t < T; ++t) {
+        const int j = model_joint_index[t];
+        if (j < m->J || j >= m->J + m->E + m->L)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model_joint_index[%d]=%d outside [%d,%d)", t, j, m->J, m->J + m->E + m->L);
+        sel[t] = j;
+        col[t] = t;
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    k2b::SurfaceTermArgs a{};
+    if (const int rc = surface_table(m, sel, col, stream, &a); rc != K2B_OK) return rc;
+    a.num_frames = B; a.num_targets = T; a.targets = targets; a.conf = conf; a.conf_per_frame = conf_per_frame ? 1 : 0;
+    a.sigma = sigma; a.joint_w = joint_loss_weight;
+    a.go = go; a.bp = bp; a.be = be; a.tr = tr; a.loss_out = loss_out; a.grad_out = grad_out;
+    HIP_TRY(k2b::launch_surface_term(a, stream));
     return K2B_OK;
 }
 

@@ -216,7 +216,7 @@ hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stre
 constexpr int kStreamXKSteps = 16;
 hipError_t launch_skin_stream_x(const StreamArgs& a, int num_cus, hipStream_t stream);
 hipError_t launch_gather_joints(const float* verts, const int* ids, float* joints, int num_frames, int V, int J, int E,
-                                hipStream_t stream);
+                                int out_stride, hipStream_t stream);   // out_stride: J + E (+ L: landmark rows behind)
 
 // J x V contraction on the matrix cores: out[J][N] = j_regressor[J][V] . rhs[V][N].
 hipError_t launch_jreg_contract(const float* j_regressor, const float* rhs, float* out, int J, int V, int N,
@@ -250,6 +250,45 @@ struct VertexTermArgs {
     int frozen_shape;                   // the first `frozen_shape` shape coefficients take no step (frozen betas beside a free expression)
 };
 hipError_t launch_vertex_term(const VertexTermArgs& a, hipStream_t stream);
+
+// Surface-point term (k2b_surface.hip): targets that are weighted vertex sets of up to 3 (vertex, weight) pairs (extra joints:
+// one pair of weight 1; landmarks: the barycentric pairs of a triangle), over a compact table of the selection's U vertices.
+constexpr int kSurfMaxTargets = 128;                  // surface targets per call
+constexpr int kSurfMaxVerts = 3 * kSurfMaxTargets;    // distinct vertices per call
+constexpr int kMaxLandmarks = 1024;                   // landmarks per model (k2b_model_set_landmarks)
+struct SurfaceTermArgs {
+    // compact table of the U distinct vertices (device, k2b_surface_gather_kernel)
+    const float *vt, *sd, *pd, *lw;     // [U][3], [U][3][NB], [9(J-1)][3U], [U][J]
+    const float *j_template, *j_dirs;
+    const int* parents;
+    int num_u, num_betas, num_joints;
+    // targets (device): pair slots / weights [T][3] (unused pairs: slot 0, weight 0), target column [T], and the pairs of
+    // every vertex as CSR (offsets [U + 1], target [n], weight [n])
+    const int *pair_u, *sel_k, *inv_off, *inv_t;
+    const float *pair_w, *inv_w;
+    // call: as VertexTermArgs
+    int num_frames, num_sel, num_targets;
+    const float* targets;
+    const float* conf;
+    int conf_per_frame;
+    float sigma, joint_w;
+    const float *go, *bp, *be, *tr;
+    float *loss_out, *grad_out;
+    const float *loss_in, *grad_in;
+    float *go_w, *bp_w, *be_w, *tr_w;
+    float *adam_m, *adam_v;
+    const float2* adam_coef;
+    float one_minus_beta1, beta2, one_minus_beta2, eps;
+    int opt_mask;
+    int frozen_shape;
+};
+hipError_t launch_surface_term(const SurfaceTermArgs& a, hipStream_t stream);
+hipError_t launch_surface_gather(const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights,
+                                 const int* ids, int n, int V, int J, int NB, float* vt, float* sd, float* pd, float* lw,
+                                 hipStream_t stream);
+hipError_t launch_landmarks(const float* src, int src_stride, const int* ids, const float* w, float* joints, int out_stride, int row0,
+                            int num_frames, int L, hipStream_t stream);
+
 hipError_t launch_adam(float* x, const float* g, float* m, float* v, long long n, float lr_over_bc1, float sqrt_bc2,
                        float one_minus_beta1, float beta2, float one_minus_beta2, float eps, hipStream_t stream);
 

@@ -627,12 +627,12 @@ __global__ __launch_bounds__(512) void k2b_lbs_tile_kernel(const TileArgs a) {
 
 // joints J..J+E-1 := vertices[extra ids]: only when an output joint's vertex cannot ride in the W image (two joints on one vertex)
 __global__ void k2b_gather_joints_kernel(const float* __restrict__ verts, const int* __restrict__ ids, float* joints,
-                                         int num_frames, int V, int J, int E) {
+                                         int num_frames, int V, int J, int E, int out_stride) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= num_frames * E) return;
     const int f = i / E, e = i % E;
     const float* s = verts + ((size_t)f * V + ids[e]) * 3;
-    float* d = joints + ((size_t)f * (J + E) + J + e) * 3;
+    float* d = joints + ((size_t)f * out_stride + J + e) * 3;
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
@@ -683,11 +683,11 @@ hipError_t launch_skin_tiles(const TileArgs& a_in, int num_cus, hipStream_t stre
 }
 
 hipError_t launch_gather_joints(const float* verts, const int* ids, float* joints, int num_frames, int V, int J, int E,
-                                hipStream_t stream) {
+                                int out_stride, hipStream_t stream) {
     if (num_frames <= 0 || E <= 0) return hipSuccess;
     const int n = num_frames * E;
     hipLaunchKernelGGL(k2b_gather_joints_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, verts, ids, joints,
-                       num_frames, V, J, E);
+                       num_frames, V, J, E, out_stride);
     return hipGetLastError();
 }
 

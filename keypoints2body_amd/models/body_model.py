@@ -37,9 +37,11 @@ class BodyModel:
     NUM_HAND_JOINTS = 15
 
     def __init__(self, v_template, shapedirs, posedirs, J_regressor, lbs_weights, parents,
-                 extra_vertex_ids=None, device=None, model_type: str = "smpl", num_betas: Optional[int] = None):
+                 extra_vertex_ids=None, device=None, model_type: str = "smpl", num_betas: Optional[int] = None,
+                 landmarks=None):
+        # landmarks: optional (vertex_ids [L,3], bary [L,3]) - smplx's facial landmarks, output joints J+E .. J+E+L-1
         self.native = native.NativeModel(v_template, shapedirs, posedirs, J_regressor, lbs_weights, parents,
-                                         extra_vertex_ids, device=device)
+                                         extra_vertex_ids, device=device, landmarks=landmarks)
         self.device = self.native.device
         nj = self.native.num_joints
         self.model_type = "smplx" if nj == 55 else ("smplh" if nj == 52 else model_type)
@@ -61,6 +63,8 @@ class BodyModel:
             self.num_betas = self.num_shape
         self.num_joints = self.native.num_joints
         self.num_vertices = self.native.num_vertices
+        self.num_landmarks = self.native.num_landmarks
+        self.num_output_joints = self.native.num_output_joints    # rows of `joints`: J + E extra vertices + L landmarks
         self.parents = torch.as_tensor(np.asarray(parents), dtype=torch.long)
 
     # -- constructors ---------------------------------------------------------------------
@@ -131,8 +135,9 @@ class BodyModel:
     def from_npz(cls, path: str, device=None) -> "BodyModel":
         with np.load(path) as z:
             extra = z["extra_vertex_ids"] if "extra_vertex_ids" in z else None
+            lmk = (z["lmk_vertex_ids"], z["lmk_bary_coords"]) if "lmk_vertex_ids" in z and "lmk_bary_coords" in z else None
             return cls(z["v_template"], z["shapedirs"], z["posedirs"], z["J_regressor"], z["lbs_weights"],
-                       z["parents"], extra, device=device)
+                       z["parents"], extra, device=device, landmarks=lmk)
 
     # -- smplx-style forward --------------------------------------------------------------
     def _as_dev(self, x, cols) -> torch.Tensor:
@@ -182,7 +187,11 @@ def smplx_constants(model) -> dict:
       hand, which this engine does not take (the packed pose has 45 values per hand);
     * ``pose_mean`` (smplx adds it to the full pose before Rodrigues; non-zero for ``flat_hand_mean=False``, the smplx default)
       would make a zero hand pose mean a different mesh than here: a non-zero one is refused - build the smplx module with
-      ``flat_hand_mean=True``.
+      ``flat_hand_mean=True``;
+    * facial landmarks: a module with ``faces_tensor``, ``lmk_faces_idx`` and ``lmk_bary_coords`` (SMPL-X) gives
+      ``landmarks = (faces_tensor[lmk_faces_idx], lmk_bary_coords)``, its static landmarks (output joints J+E ..); the 17
+      dynamic contour landmarks of ``use_face_contour=True`` (they depend on the head's yaw) are not adopted.  A module
+      without them gives no ``landmarks`` key.
     """
     get = lambda name: getattr(model, name)
     selector = getattr(model, "vertex_joint_selector", None)
@@ -207,10 +216,28 @@ def smplx_constants(model) -> dict:
         raise NotImplementedError("an smplx module with a non-zero pose_mean (flat_hand_mean=False): build it with "
                                   "flat_hand_mean=True - the kernels apply the pose as given")
     nj = int(host(get("parents")).shape[0])
-    return dict(v_template=host(get("v_template")), shapedirs=np.ascontiguousarray(shapedirs), posedirs=host(get("posedirs")),
-                J_regressor=host(get("J_regressor")), lbs_weights=host(get("lbs_weights")), parents=host(get("parents")),
-                extra_vertex_ids=None if extra is None else host(extra),
-                model_type="smplx" if nj == 55 else ("smplh" if nj == 52 else "smpl"), num_betas=nb)
+    out = dict(v_template=host(get("v_template")), shapedirs=np.ascontiguousarray(shapedirs), posedirs=host(get("posedirs")),
+               J_regressor=host(get("J_regressor")), lbs_weights=host(get("lbs_weights")), parents=host(get("parents")),
+               extra_vertex_ids=None if extra is None else host(extra),
+               model_type="smplx" if nj == 55 else ("smplh" if nj == 52 else "smpl"), num_betas=nb)
+    faces, lmk_faces, lmk_bary = (getattr(model, n, None) for n in ("faces_tensor", "lmk_faces_idx", "lmk_bary_coords"))
+    if faces is not None and lmk_faces is not None and lmk_bary is not None:
+        tri = host(faces).astype(np.int64)[host(lmk_faces).astype(np.int64).reshape(-1)]
+        out["landmarks"] = (np.ascontiguousarray(tri, dtype=np.int32),
+                            np.ascontiguousarray(host(lmk_bary), dtype=np.float32).reshape(-1, 3))
+    return out
+
+
+def check_target_indices(model: BodyModel, model_idx) -> None:
+    """Raise ``ValueError`` for a target index outside the model's output joints (J kinematic, E extra vertices, L
+    landmarks).  smplx's 17 dynamic face-contour landmarks (``use_face_contour=True``) have no output row here."""
+    n = int(model.num_output_joints)
+    bad = [int(i) for i in model_idx if not 0 <= int(i) < n]
+    if bad:
+        raise ValueError(
+            f"target_model_indices {bad[:8]} outside the model's {n} output joints ({model.num_joints} kinematic, "
+            f"{n - model.num_joints - model.num_landmarks} vertex-selected, {model.num_landmarks} landmarks); "
+            "the dynamic face-contour landmarks of use_face_contour=True are not supported")
 
 
 def as_body_model(model, device=None) -> BodyModel:

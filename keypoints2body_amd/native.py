@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "k2b_version", "k2b_last_error", "k2b_model_create", "k2b_model_destroy", "k2b_model_dims",
     "k2b_model_joint_basis", "k2b_model_reserve", "k2b_debug_read_dump", "k2b_prior_create", "k2b_prior_destroy", "k2b_fit_config_default", "k2b_fit_config_size",
     "k2b_fit_world", "k2b_fit_sequence", "k2b_lbs", "k2b_vertex_term", "k2b_adam_step", "k2b_angular_error_deg",
-    "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs",
+    "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs", "k2b_model_set_landmarks", "k2b_model_num_landmarks", "k2b_surface_term",
 )
 
 
@@ -113,6 +113,12 @@ def load_library():
                                            [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
     lib.k2b_vertex_term.restype = C.c_int
     lib.k2b_vertex_term.argtypes = [vp, C.c_int32, C.c_int32, ip, fp, fp, C.c_float, C.c_float] + [fp] * 6 + [vp]
+    lib.k2b_model_set_landmarks.restype = C.c_int
+    lib.k2b_model_set_landmarks.argtypes = [vp, C.c_int32, ip, fp]
+    lib.k2b_model_num_landmarks.restype = C.c_int
+    lib.k2b_model_num_landmarks.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.k2b_surface_term.restype = C.c_int
+    lib.k2b_surface_term.argtypes = [vp, C.c_int32, C.c_int32, ip, fp, fp, C.c_int32, C.c_float, C.c_float] + [fp] * 6 + [vp]
     lib.k2b_adam_step.restype = C.c_int
     lib.k2b_adam_step.argtypes = [C.c_int64, fp, fp, fp, fp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.k2b_angular_error_deg.restype = C.c_int
@@ -178,7 +184,9 @@ class NativeModel:
     """Owner of a ``k2b_model`` handle (body-model constants in HBM)."""
 
     def __init__(self, v_template, shapedirs, posedirs, J_regressor, lbs_weights, parents,
-                 extra_vertex_ids, device=None):
+                 extra_vertex_ids, device=None, landmarks=None):
+        """`landmarks`: optional ``(vertex_ids [L,3] int, bary [L,3] float)``, smplx's facial landmarks
+        (``faces_tensor[lmk_faces_idx]``, ``lmk_bary_coords``): output joints J+E .. J+E+L-1."""
         self.device = require_device(device)
         lib = load_library()
         vt = _host_f32(v_template)
@@ -195,11 +203,28 @@ class NativeModel:
             raise ValueError(
                 f"inconsistent body-model constants: v_template {vt.shape}, shapedirs {sd.shape}, posedirs {pd.shape}, "
                 f"J_regressor {jr.shape}, lbs_weights {lw.shape}, parents {par.shape}")
+        lm_ids = lm_w = None
+        if landmarks is not None:
+            lm_ids, lm_w = _host_i32(landmarks[0]), _host_f32(landmarks[1])
+            if lm_ids.ndim != 2 or lm_ids.shape[1] != 3 or lm_w.shape != lm_ids.shape:
+                raise ValueError(f"landmarks must be (vertex_ids [L,3], bary [L,3]), got {lm_ids.shape} and {lm_w.shape}")
         self.num_vertices, self.num_joints, self.num_betas, self.num_extra = V, J, NB, E
+        self.num_landmarks = 0
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _check(lib.k2b_model_create(C.byref(self._h), V, J, NB, E, _np_ptr(vt), _np_ptr(sd), _np_ptr(pd),
                                         _np_ptr(jr), _np_ptr(lw), _np_ptr(par), _np_ptr(ex)), "k2b_model_create")
+            if lm_ids is not None:
+                _check(lib.k2b_model_set_landmarks(self._h, lm_ids.shape[0], _np_ptr(lm_ids), _np_ptr(lm_w)),
+                       "k2b_model_set_landmarks")
+                n = C.c_int32(0)
+                _check(lib.k2b_model_num_landmarks(self._h, C.byref(n)), "k2b_model_num_landmarks")
+                self.num_landmarks = int(n.value)
+
+    @property
+    def num_output_joints(self) -> int:
+        """Rows of ``lbs``'s joints: J kinematic, E vertex-selected, L landmarks (smplx's layout)."""
+        return self.num_joints + self.num_extra + self.num_landmarks
 
     @property
     def handle(self):
@@ -217,7 +242,7 @@ class NativeModel:
         return jt, jd
 
     def lbs(self, global_orient, body_pose, betas, transl=None, want_vertices=True):
-        """Full forward: returns (joints (B,J+E,3), vertices (B,V,3) or None)."""
+        """Full forward: returns (joints (B,J+E+L,3), vertices (B,V,3) or None)."""
         dev = self.device
         B = global_orient.shape[0]
         D = 3 * (self.num_joints - 1)
@@ -225,7 +250,7 @@ class NativeModel:
         bp = _dev(body_pose, "body_pose", dev, (B, D))
         be = _dev(betas, "betas", dev, (B, self.num_betas))
         tr = _dev(transl, "transl", dev, (B, 3))
-        joints = torch.empty((B, self.num_joints + self.num_extra, 3), dtype=torch.float32, device=dev)
+        joints = torch.empty((B, self.num_output_joints, 3), dtype=torch.float32, device=dev)
         verts = torch.empty((B, self.num_vertices, 3), dtype=torch.float32, device=dev) if want_vertices else None
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -470,6 +495,32 @@ def vertex_term(model: NativeModel, extra_index: Sequence[int], targets: torch.T
             _dev(body_pose, "body_pose", dev, (B, D)), _dev(betas, "betas", dev, (B, model.num_betas)),
             _dev(transl, "transl", dev, (B, 3)), C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()), stream),
             "k2b_vertex_term")
+    return loss, grad
+
+
+def surface_term(model: NativeModel, model_joint_index: Sequence[int], targets: torch.Tensor, conf: Optional[torch.Tensor],
+                 sigma: float, joint_loss_weight: float, global_orient: torch.Tensor, body_pose: torch.Tensor,
+                 betas: torch.Tensor, transl: torch.Tensor):
+    """Loss (B,) and gradient (B, P) of the joint-loss term of surface targets - extra joints and landmarks, given as model
+    joint indices in [J, J+E+L) - (``k2b_surface_term``).  `conf`: (T,), (B, T) per frame, or None."""
+    dev = model.device
+    B, T = targets.shape[0], targets.shape[1]
+    D = 3 * (model.num_joints - 1)
+    idx = _host_i32(np.asarray(list(model_joint_index)))
+    if idx.shape != (T,):
+        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {T} targets")
+    per_frame = conf is not None and conf.dim() == 2
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, 3 + D + model.num_betas + 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(load_library().k2b_surface_term(
+            model.handle, B, T, _np_ptr(idx), _dev(targets, "targets", dev, (B, T, 3)),
+            _dev(conf, "conf", dev, (B, T) if per_frame else (T,)), 1 if per_frame else 0,
+            float(sigma), float(joint_loss_weight), _dev(global_orient, "global_orient", dev, (B, 3)),
+            _dev(body_pose, "body_pose", dev, (B, D)), _dev(betas, "betas", dev, (B, model.num_betas)),
+            _dev(transl, "transl", dev, (B, 3)), C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()), stream),
+            "k2b_surface_term")
     return loss, grad
 
 

@@ -275,6 +275,25 @@ def make_body_model(seed: int = 0, num_vertices: int = 6890, num_betas: int = 10
     )
 
 
+def make_landmarks(num_vertices: int = 10475, num_joints: int = 55, num_landmarks: int = 51, seed: int = 0,
+                   joints=(15, 22)) -> tuple:
+    """Seeded landmark table for a synthetic mesh of ``make_body_model`` (smplx ``vertices2landmarks`` layout): landmark l
+    is the barycentric point ``sum_k bary[l, k] v[vertex_ids[l, k]]`` of a triangle of three distinct vertices that hang
+    on one of `joints` (default: SMPL-X head and jaw, where smplx's facial landmarks sit; the synthetic mesh has no face
+    list, so the triangle is three vertices of the same joint), weights drawn uniformly on the simplex.  Returns
+    ``(vertex_ids [L,3] int32, bary [L,3] float32)``.  Independent of the other generators (own random streams)."""
+    V, J, L = int(num_vertices), int(num_joints), int(num_landmarks)
+    pool = np.concatenate([np.arange(j, V, J) for j in joints])        # vertices whose primary joint is one of `joints`
+    per = V // J - 2                                                    # room for the two neighbours a + J, a + 2J
+    u = uniform(40, L, seed)
+    base = pool[(u * len(pool)).astype(np.int64)]
+    base = np.where(base + 2 * J < V, base, base - 2 * J) if per > 0 else base
+    ids = np.stack([base, base + J, base + 2 * J], axis=1) % V
+    r = np.sort(uniform(41, 2 * L, seed).reshape(L, 2), axis=1)          # Dirichlet(1, 1, 1): gaps of sorted uniforms
+    bary = np.stack([r[:, 0], r[:, 1] - r[:, 0], 1.0 - r[:, 1]], axis=1)
+    return ids.astype(np.int32), bary.astype(np.float32)
+
+
 @dataclass
 class SyntheticGMM:
     """Mixture parameters in the dict layout of ``gmm_08.pkl``
