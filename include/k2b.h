@@ -46,6 +46,7 @@ typedef enum k2b_status {
 
 typedef struct k2b_model k2b_model; /* body-model constants resident in HBM */
 typedef struct k2b_prior k2b_prior; /* max-mixture pose prior resident in HBM */
+typedef struct k2b_ikgat k2b_ikgat; /* IK-GAT rotation regressor (weights + graph) resident in HBM */
 
 /* Library / ABI version: (major << 16) | minor. */
 uint32_t k2b_version(void);
@@ -320,6 +321,40 @@ int k2b_adam_step(int64_t n, float *params, const float *grad, float *m, float *
  * ------------------------------------------------------------------------------- */
 int k2b_angular_error_deg(int64_t n, const float *pred_rotvec, const float *gt_rotvec,
                           float *err_deg_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * IK-GAT rotation regressor — inference of the reference's learned estimator
+ * (core/estimators/ikgat/: gan_regressor.py:39-126, inference.py:39-43 and 83-120,
+ * utils.py:13-52) in eval mode.  Per frame: joint positions minus joint 0 (plus the 6-D form
+ * of the input quaternions when input_dim == 9) -> J unit quaternions, xyzw, qw >= 0.
+ *
+ * k2b_ikgat_create: HOST pointers, copied.
+ *   parents [J]: parent of each joint, negative = none; edges run both ways between a joint and its
+ *     parent; with no parent >= 0 at all the graph is the chain i <-> i+1 (gan_regressor.py:16-36).
+ *   weights [num_weights] float32: the state dict's tensors, row-major, concatenated in this order
+ *   (H = hidden_dim, H2 = H / 2, IN = input_dim):
+ *     input_proj.weight [H][IN], input_proj.bias [H], joint_pos_embed.weight [J][H],
+ *     residual_proj.weight [H][IN], residual_proj.bias [H],
+ *     for each layer l: gat_layers.l.lin.weight [H][H], gat_layers.l.att_src [H], gat_layers.l.att_dst [H],
+ *       gat_layers.l.bias [H], layer_norms.l.weight [H], layer_norms.l.bias [H],
+ *     output_head.0.weight [H2][H], output_head.0.bias [H2], output_head.2.weight [H2], output_head.2.bias [H2],
+ *     output_head.4.weight [6][H2], output_head.4.bias [6].
+ *   Supported: 1 <= J <= 64, H a multiple of 16 and <= 256, num_heads dividing H, 1 <= num_layers <= 8,
+ *   input_dim 3 or 9, and one frame's working set within 160 KiB of LDS; anything else K2B_ERR_UNSUPPORTED.
+ *   A parent >= J or a num_weights that does not match the dimensions: K2B_ERR_INVALID_ARGUMENT.
+ * k2b_ikgat_predict: positions dev [num_frames][J][3]; quat_in dev [num_frames][J][4] xyzw (input_dim 9;
+ *   ignored and may be NULL for input_dim 3); quat_out dev [num_frames][J][4].
+ *   chain == 0: the frames are independent.  chain != 0 (input_dim 9): frame 0 reads quat_in[0], frame t > 0
+ *   reads frame t-1's output (warm-started sequence, one workgroup, one launch; only quat_in[0] is read); the result
+ *   is bit-identical to num_frames calls with chain == 0 and num_frames == 1 that pass each output on.
+ *   A frame's outputs do not depend on num_frames or on its position in the batch.  num_frames == 0 is a no-op.
+ * ------------------------------------------------------------------------------- */
+int k2b_ikgat_create(k2b_ikgat **out, int32_t num_joints, int32_t input_dim, int32_t hidden_dim,
+                     int32_t num_layers, int32_t num_heads, const int32_t *parents, const float *weights,
+                     int64_t num_weights);
+void k2b_ikgat_destroy(k2b_ikgat *net);
+int k2b_ikgat_predict(const k2b_ikgat *net, int32_t num_frames, const float *positions, const float *quat_in,
+                      int32_t chain, float *quat_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,8 @@ def optimize_params_frame(joints, *, prev_params: Optional[BodyModelParams] = No
     else:
         j3d, conf_3d, model_indices = common.canonicalize(j3d, conf_3d, model_indices, in_layout, joint_layout,
                                                           body_model, frame_cfg, device)
+    if frame_cfg.estimator_type == "ikgat":
+        return _ikgat_frame(j3d, conf_3d, model_indices, prev_params, body_model, model, frame_cfg, device)
     model = common.obtain_model(model, body_model, device)
     engine = OptimizeEngine(model=model, frame_config=frame_cfg, device=device, model_type=body_model,
                             pose_prior=pose_prior)
@@ -73,3 +75,37 @@ def optimize_params_frame(joints, *, prev_params: Optional[BodyModelParams] = No
 
     return engine.fit_frame(init_params=init_params, j3d=j3d, conf_3d=conf_3d, seq_ind=0,
                             target_model_indices=model_indices)
+
+
+def ikgat_init_params(j3d: torch.Tensor, frame_cfg: FrameOptimizeConfig, device) -> SMPLData:
+    """The IK-GAT path's start without ``prev_params`` (reference ``api/frame.py:115-123``): zero SMPL parameters,
+    ``transl`` = the frame's root joint in world mode, ``None`` in camera mode."""
+    z = lambda c: torch.zeros((1, c), dtype=torch.float32, device=device)
+    transl = j3d[:, 0, :].detach() if frame_cfg.coordinate_mode == "world" else None
+    return SMPLData(betas=z(10), global_orient=z(3), body_pose=z(69), transl=transl)
+
+
+def ikgat_prev_params(prev: BodyModelParams, j3d: torch.Tensor, body_model: str, model, frame_cfg, device, name: str):
+    """Caller-given start of the IK-GAT path: the reference's type check against ``body_model`` applies
+    (``api/frame.py:150-161``), so an ``SMPLData`` with ``body_model="smplx"`` raises ``ValueError``.  A world-mode start
+    without ``transl`` gets the root-aligned one through ``model`` as in the reference; without a model the reference
+    fails with a ``TypeError`` (it calls the missing model) - this raises ``ValueError`` instead."""
+    common.check_param_type(prev, body_model, name)
+    init = prev.to(device)
+    if frame_cfg.coordinate_mode == "world" and init.transl is None:
+        if model is None:
+            raise ValueError(f"estimator_type='ikgat' in world mode: {name}.transl is None and no model= was given to "
+                             "derive the root-aligned translation from (pass transl, a model, or use camera mode)")
+        init = _with_root_aligned_transl(init, j3d, common.obtain_model(model, body_model, device), frame_cfg, device)
+    return init
+
+
+def _ikgat_frame(j3d, conf_3d, model_indices, prev_params, body_model, model, frame_cfg, device) -> BodyModelFitResult:
+    """IK-GAT: no body model, no mean parameters (reference ``api/frame.py:76,106,115-123``)."""
+    from ..core.estimators.ikgat import IKGATEstimator
+    est = IKGATEstimator(frame_cfg, device=device)
+    if prev_params is None:
+        init_params = ikgat_init_params(j3d, frame_cfg, device)
+    else:
+        init_params = ikgat_prev_params(prev_params, j3d, body_model, model, frame_cfg, device, "prev_params")
+    return est.fit_frame(init_params=init_params, j3d=j3d, conf_3d=conf_3d, seq_ind=0, target_model_indices=model_indices)

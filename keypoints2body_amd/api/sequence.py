@@ -31,7 +31,7 @@ from ..core.engine import (OptimizeEngine, default_init_params, load_mean_pose_s
 from ..core.joints.adapters import normalize_sequence_observations
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams, SMPLData
 from . import common
-from .frame import _with_root_aligned_transl
+from .frame import _with_root_aligned_transl, ikgat_init_params, ikgat_prev_params
 
 
 def _process_group():
@@ -149,6 +149,8 @@ def optimize_params_sequence(joints_seq, *, init_params: Optional[BodyModelParam
         conf = conf.clone()
         conf[:, [7, 8, 10, 11]] = 1.5
 
+    if frame_cfg.estimator_type == "ikgat":
+        return _ikgat_sequence(xyz, init_params, body_model, model, seq_cfg, device)
     model = common.obtain_model(model, body_model, device)
     mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(
         common.DEFAULT_MEAN_FILE, device)
@@ -206,6 +208,27 @@ def optimize_params_sequence(joints_seq, *, init_params: Optional[BodyModelParam
                                                            gather_vertices)
     return [BodyModelFitResult(params=est.fitter.result_params(out, prev, slice(i, i + 1)), vertices=vertex_of(i),
                                joints=joints[i: i + 1], loss=loss[i]) for i in range(T)]
+
+
+def _ikgat_sequence(xyz, init_params, body_model, model, seq_cfg, device) -> list[BodyModelFitResult]:
+    """IK-GAT over a sequence (reference ``api/sequence.py:90,130-137,167-176,214-281``): no model, no mean parameters, no
+    shape pass.  The one start object is carried through every frame, so every result's params equal it (frame 0's
+    ``transl`` included).  ONE launch and one device-to-host copy of the (T, J, 4) quaternions: independent frames run
+    batched; the pos-rot6 network with ``use_previous_frame_init=True`` runs as one in-kernel chain, frame t reading frame
+    t-1's prediction.  Under a process group every rank runs all frames (no sharding)."""
+    from ..core.estimators.ikgat import IKGATEstimator, result_for
+    frame_cfg = seq_cfg.frame
+    est = IKGATEstimator(frame_cfg, device=device)
+    T = xyz.shape[0]
+    if T == 0:
+        return []
+    if init_params is None:
+        prev = ikgat_init_params(xyz[0:1], frame_cfg, device)
+    else:
+        prev = ikgat_prev_params(init_params, xyz[0:1], body_model, model, frame_cfg, device, "init_params")
+    chain = est.needs_quaternions and seq_cfg.use_previous_frame_init and T > 1
+    quats = est.predict(est._positions(xyz), est._quaternions(prev), chain=chain)
+    return [result_for(prev, quats[t], xyz[t: t + 1]) for t in range(T)]
 
 
 def _batched_results(est, out, joints, verts, loss, init, n) -> list[BodyModelFitResult]:

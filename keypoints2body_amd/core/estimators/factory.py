@@ -1,5 +1,7 @@
 """Estimator selection by ``FrameOptimizeConfig.estimator_type``
-(reference ``keypoints2body/core/estimators/factory.py:20-44``)."""
+(reference ``keypoints2body/core/estimators/factory.py:20-44``): ``"optimization"`` is the HIP fitter,
+``"ikgat"`` the learned IK-GAT regressor on the HIP engine (``ikgat.py``); ``"learned"`` stays the reference's
+``NotImplementedError`` placeholder."""
 from __future__ import annotations
 
 from ..config import FrameOptimizeConfig
@@ -17,7 +19,6 @@ def create_estimator(model, frame_config: FrameOptimizeConfig, device=None, mode
             "estimator_type='learned' is not implemented yet. "
             "Implement under keypoints2body.core.estimators and wire model loading/inference.")
     if kind == "ikgat":
-        raise NotImplementedError(
-            "estimator_type='ikgat': the learned GAT regressor (reference core/estimators/ikgat/) needs "
-            "torch_geometric and trained weights and is outside the HIP engine's scope")
+        from .ikgat import IKGATEstimator
+        return IKGATEstimator(frame_config=frame_config, device=device)
     raise ValueError(f"Unknown estimator_type: {kind}")

@@ -316,4 +316,22 @@ hipError_t launch_lbfgs_frame_prep(float* go, const float* sgo, float* bp, const
 // Geodesic angle (degrees) between n pairs of axis-angle rotations (evaluation metric, k2b_metrics.hip).
 hipError_t launch_angular_error(const float* pred, const float* gt, float* out, long long n, hipStream_t stream);
 
+// ---- IK-GAT regressor inference (k2b_ikgat.hip): B frames of J joint positions (+ input quaternions when in == 9) -> J
+// quaternions per frame.  Batched: ceil(B / F) workgroups of F frames; chain: one workgroup walks the B frames in order,
+// frame t + 1 reading frame t's outputs as its input quaternions.
+struct IkgatArgs {
+    const float* w;          // device weight layout (k2b_ikgat_create in k2b_api.hip)
+    const int* csr;          // [J + 1] in-edge offsets, then the source node of every in-edge (self loops included)
+    const float* pos;        // [B][J][3]
+    const float* quat_in;    // [B][J][4] xyzw (in == 9), or NULL
+    float* quat_out;         // [B][J][4] xyzw
+    int B, J, H, heads, L, in, F, KC, ldx, nedges, chain;
+};
+// columns of a GAT layer's extended projection: H of x', heads of a_src, heads of a_dst, padded to a multiple of 4
+inline int ikgat_ldx(int H, int heads) { return (H + 2 * heads + 3) & ~3; }
+constexpr size_t kIkgatMaxLds = 160 * 1024;
+constexpr int kIkgatChunkFloats = 4096;      // weights staged per k-chunk: KC * (columns) <= this
+size_t ikgat_lds_bytes(int J, int H, int heads, int in, int nedges, int F, int KC);
+hipError_t launch_ikgat(const IkgatArgs& a, size_t lds_bytes, hipStream_t stream);
+
 }  // namespace k2b

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "k2b_model_joint_basis", "k2b_model_reserve", "k2b_debug_read_dump", "k2b_prior_create", "k2b_prior_destroy", "k2b_fit_config_default", "k2b_fit_config_size",
     "k2b_fit_world", "k2b_fit_sequence", "k2b_lbs", "k2b_vertex_term", "k2b_adam_step", "k2b_angular_error_deg",
     "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs", "k2b_model_set_landmarks", "k2b_model_num_landmarks", "k2b_surface_term",
+    "k2b_ikgat_create", "k2b_ikgat_destroy", "k2b_ikgat_predict",
 )
 
 
@@ -123,6 +124,12 @@ def load_library():
     lib.k2b_adam_step.argtypes = [C.c_int64, fp, fp, fp, fp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.k2b_angular_error_deg.restype = C.c_int
     lib.k2b_angular_error_deg.argtypes = [C.c_int64, fp, fp, fp, vp]
+    lib.k2b_ikgat_create.restype = C.c_int
+    lib.k2b_ikgat_create.argtypes = [C.POINTER(vp)] + [C.c_int32] * 5 + [ip, fp, C.c_int64]
+    lib.k2b_ikgat_destroy.restype = None
+    lib.k2b_ikgat_destroy.argtypes = [vp]
+    lib.k2b_ikgat_predict.restype = C.c_int
+    lib.k2b_ikgat_predict.argtypes = [vp, C.c_int32, fp, fp, C.c_int32, fp, vp]
     _lib = lib
     return lib
 
@@ -537,3 +544,51 @@ def adam_step(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torc
         _check(load_library().k2b_adam_step(n, _dev(params, "params", dev), _dev(grad, "grad", dev), _dev(m, "m", dev),
                                             _dev(v, "v", dev), int(step), float(step_size), float(beta1), float(beta2),
                                             float(eps), stream), "k2b_adam_step")
+
+
+class NativeIkgat:
+    """Owner of a ``k2b_ikgat`` handle: the IK-GAT regressor's packed weights and graph in HBM
+    (layout: ``include/k2b.h``, ``k2b_ikgat_create``)."""
+
+    def __init__(self, parents, weights, input_dim: int, hidden_dim: int, num_layers: int, num_heads: int, device=None):
+        self.device = require_device(device)
+        par = _host_i32(parents).reshape(-1)
+        w = _host_f32(weights).reshape(-1)
+        self.num_joints, self.input_dim = int(par.shape[0]), int(input_dim)
+        self.hidden_dim, self.num_layers, self.num_heads = int(hidden_dim), int(num_layers), int(num_heads)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(load_library().k2b_ikgat_create(C.byref(self._h), self.num_joints, self.input_dim, self.hidden_dim,
+                                                   self.num_layers, self.num_heads, _np_ptr(par), _np_ptr(w), int(w.size)),
+                   "k2b_ikgat_create")
+
+    def predict(self, positions: torch.Tensor, quat_in: Optional[torch.Tensor] = None, chain: bool = False) -> torch.Tensor:
+        """(T, J, 3) positions [+ (T, J, 4) xyzw quaternions] -> (T, J, 4) quaternions on the device.  ``chain``: frame t > 0
+        takes frame t-1's output as its input quaternions (one launch); only ``quat_in[0]`` is read, so (1, J, 4) will do."""
+        dev, J = self.device, self.num_joints
+        if positions.dim() != 3 or positions.shape[1:] != (J, 3):
+            raise ValueError(f"positions has shape {tuple(positions.shape)}, the network expects (T, {J}, 3)")
+        T = int(positions.shape[0])
+        pos = _dev(positions, "positions", dev)
+        q = None
+        if self.input_dim == 9:
+            if quat_in is None:
+                raise ValueError("the pos-rot6 network needs input quaternions")
+            q = _dev(quat_in, "quat_in", dev)
+            if quat_in.dim() != 3 or quat_in.shape[1:] != (J, 4) or quat_in.shape[0] not in ((1, T) if chain else (T,)):
+                raise ValueError(f"quat_in has shape {tuple(quat_in.shape)}, expected ({T}, {J}, 4)"
+                                 + (" or (1, J, 4) in chain mode" if chain else ""))
+        out = torch.empty((T, J, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _check(load_library().k2b_ikgat_predict(self._h, T, pos, q, 1 if chain else 0, C.c_void_p(out.data_ptr()), stream),
+                   "k2b_ikgat_predict")
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value and _lib is not None:
+                _lib.k2b_ikgat_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass

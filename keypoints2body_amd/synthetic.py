@@ -383,3 +383,38 @@ def make_poses_h(num_frames: int, seed: int = 0) -> SyntheticPosesH:
 def target_noise(num_frames: int, num_joints: int, seed: int = 0, scale: float = 0.005) -> np.ndarray:
     """Optional observation noise added to target joints (metres)."""
     return (scale * normalish(34, (num_frames, num_joints, 3), seed)).astype(np.float32)
+
+
+def make_ikgat_state(num_joints: int = 22, input_dim: int = 9, hidden_dim: int = 128, num_layers: int = 3,
+                     num_heads: int = 4, seed: int = 0, legacy_pyg: bool = False) -> dict:
+    """Seeded weights of the reference's IK-GAT regressor (``GATRotationRegressor``, PyG ``GATConv`` layers) as a state dict
+    of float32 numpy arrays under the reference's key names; no trained weights exist, these stand in for them.  Linear
+    layers are N(0, 1/fan_in), attention vectors N(0, 0.3^2 / C), biases and LayerNorm shifts N(0, 0.1^2), LayerNorm scales
+    1 + N(0, 0.1^2).  The last head layer is scaled to 0.3 / sqrt(H/2) with bias (1, 0, 0, 0, 1, 0), so the two predicted
+    axes stay near the identity frame and every predicted rotation is moderate (qw well above 0).  ``legacy_pyg``: the GAT
+    projection under older PyG's ``lin_src.weight`` / ``lin_dst.weight`` (one tensor twice) instead of ``lin.weight``."""
+    J, IN, H, L, NH = int(num_joints), int(input_dim), int(hidden_dim), int(num_layers), int(num_heads)
+    C, H2 = H // NH, H // 2
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    stream = iter(range(900, 1000))
+    draw = lambda shape, std: f32(std * normalish(next(stream), shape, seed))
+    s = {}
+    s["input_proj.weight"], s["input_proj.bias"] = draw((H, IN), IN ** -0.5), draw((H,), 0.1)
+    for l in range(L):
+        w = draw((NH * C, H), H ** -0.5)
+        if legacy_pyg:
+            s[f"gat_layers.{l}.lin_src.weight"], s[f"gat_layers.{l}.lin_dst.weight"] = w, w.copy()
+        else:
+            s[f"gat_layers.{l}.lin.weight"] = w
+        s[f"gat_layers.{l}.att_src"] = draw((1, NH, C), 0.3 * C ** -0.5)
+        s[f"gat_layers.{l}.att_dst"] = draw((1, NH, C), 0.3 * C ** -0.5)
+        s[f"gat_layers.{l}.bias"] = draw((NH * C,), 0.1)
+    for l in range(L):
+        s[f"layer_norms.{l}.weight"], s[f"layer_norms.{l}.bias"] = f32(1.0 + draw((H,), 0.1)), draw((H,), 0.1)
+    s["joint_pos_embed.weight"] = draw((J, H), 0.5)
+    s["output_head.0.weight"], s["output_head.0.bias"] = draw((H2, H), H ** -0.5), draw((H2,), 0.1)
+    s["output_head.2.weight"], s["output_head.2.bias"] = f32(1.0 + draw((H2,), 0.1)), draw((H2,), 0.1)
+    s["output_head.4.weight"] = draw((6, H2), 0.3 * H2 ** -0.5)
+    s["output_head.4.bias"] = f32(np.array([1, 0, 0, 0, 1, 0]) + draw((6,), 0.02))
+    s["residual_proj.weight"], s["residual_proj.bias"] = draw((H, IN), IN ** -0.5), draw((H,), 0.1)
+    return s
