@@ -267,6 +267,67 @@ int k2b_fit_sequence_lbfgs(const k2b_model *model, const k2b_prior *prior, const
                            double lr, double tolerance_grad, double tolerance_change, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * k2b_fit_sequences / k2b_fit_sequences_lbfgs (ABI 1.3) — many warm-start sequences of DIFFERENT lengths side by side:
+ * k2b_fit_sequence (Adam branch) and k2b_fit_sequence_lbfgs (L-BFGS branch, one optimiser per sequence) for
+ * num_sequences = S sequences at once.  Frames are packed: sequence s owns rows offsets[s] .. offsets[s] + lengths[s] - 1.
+ *   lengths, offsets  host int32 [S]: lengths[s] >= 0 (0: an empty sequence, nothing is written for it), offsets = the
+ *                     exclusive prefix sums of lengths
+ *   j3d dev [sum T][K][3]; conf dev [K], or [sum T][K] with cfg->conf_per_frame
+ *   *_in dev [S][...]: start of every sequence's first frame
+ *   *_out dev [sum T][...], loss_out dev [sum T] (may be NULL): every frame's result / loss, in the caller's order
+ * Internally the sequences are sorted by length, longest first, so that similar lengths share a workgroup; a sequence's result
+ * is bit-identical to the same sequence fitted alone (k2b_fit_sequence / k2b_fit_sequence_lbfgs with S = 1, or the
+ * first-frame fit for a sequence of one frame), whatever its neighbours, S or the order.  ONE launch: the Adam branch for
+ * every model with kinematic targets (24 joints: the fused kernel; SMPL-H / SMPL-X: the tree kernel), the L-BFGS branch for
+ * the 24-joint model with the prior over the whole pose and kinematic targets.  Other configurations return
+ * K2B_ERR_UNSUPPORTED (fit sequence by sequence).  Bad lengths / offsets and cfg->transl_prior_weight != 0 return
+ * K2B_ERR_INVALID_ARGUMENT before anything is launched.  The slot table is uploaded stream-ordered from pinned staging; the
+ * host waits at most for the same thread's previous upload.
+ * ------------------------------------------------------------------------------- */
+int k2b_fit_sequences(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                      int32_t num_sequences, const int32_t *lengths, const int32_t *offsets, int32_t followup_iters,
+                      int32_t num_targets, const int32_t *model_joint_index,
+                      const float *j3d, const float *conf,
+                      const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                      const float *transl_in,
+                      float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                      float *loss_out, void *stream);
+/* k2b_sequence_order — the launch order of the two entries above, for inspection (host only, no device call): order_out[i] =
+ * the sequence in chain slot i (sequences with frames, longest first, ties in the caller's order), *num_slots = their count.
+ * The arguments are checked as the entries check them. */
+int k2b_sequence_order(int32_t num_sequences, const int32_t *lengths, const int32_t *offsets, int32_t *order_out,
+                       int32_t *num_slots);
+
+/* ---------------------------------------------------------------------------------
+ * k2b_shape_pass_lbfgs (ABI 1.3) — the shape pre-pass of many sequences together (reference core/shape.py:10-115,
+ * optimize_shape_multi_frame: torch.optim.LBFGS([betas], max_iter, lr, strong_wolfe) per sequence).  Sequence s owns frames
+ * seq_offsets[s] .. seq_offsets[s + 1] - 1 (dev int32 [S + 1]); per frame the kinematic targets j3d dev [N][K][3], conf dev
+ * [N][K] (or NULL), the fixed pose global_orient dev [N][3] / body_pose dev [N][3(J-1)] and the target root root_targets dev
+ * [N][3].  The loss of a sequence is the sum over its frames of the evaluate-only fit under `cfg` (the caller sets sigma, the
+ * weights and the shape prior) at shape = [betas | 0] and the root-aligned translation root_target - (J_template[root_joint] +
+ * J_dirs[root_joint] betas); the gradient takes the chain rule through that alignment.  betas_in / betas_out dev
+ * [S][num_free_betas].  Per round one small prep launch, ONE evaluate-only fit launch over all N frames, one fixed-order
+ * per-sequence reduction and the device L-BFGS step (one instance per sequence); only launches are queued.  A sequence's result
+ * does not depend on the others.  Kinematic targets only.
+ * ------------------------------------------------------------------------------- */
+int k2b_shape_pass_lbfgs(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                         int32_t num_sequences, const int32_t *seq_offsets, int32_t num_frames, int32_t num_targets,
+                         const int32_t *model_joint_index, const float *j3d, const float *conf,
+                         const float *global_orient, const float *body_pose, const float *root_targets, int32_t root_joint,
+                         int32_t num_free_betas, const float *betas_in, float *betas_out, int32_t max_iter,
+                         int32_t history_size, double lr, double tolerance_grad, double tolerance_change, void *stream);
+
+int k2b_fit_sequences_lbfgs(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                            int32_t num_sequences, const int32_t *lengths, const int32_t *offsets,
+                            int32_t num_targets, const int32_t *model_joint_index,
+                            const float *j3d, const float *conf,
+                            const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                            const float *transl_in,
+                            float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                            float *loss_out, int32_t first_iters, int32_t followup_iters, int32_t history_size,
+                            double lr, double tolerance_grad, double tolerance_change, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * k2b_lbs — full SMPL forward.  Replaces `self.smpl(**kwargs)` (smplx `SMPL.forward`,
  * call sites world_space.py:34,192,278; engine.py:114) for a batch:
  *   joints_out dev [B][J+E+L][3], vertices_out dev [B][V][3] (NULL: joints only; the E

@@ -196,3 +196,69 @@ def optimize_shape_pass(model, seq_config: SequenceOptimizeConfig, init_mean_sha
     torch.optim.LBFGS([betas], max_iter=int(seq_config.num_shape_iters), lr=1e-1,
                       line_search_fn="strong_wolfe").step(closure)
     return betas.detach()
+
+
+def optimize_shape_pass_batched(model, seq_config: SequenceOptimizeConfig, init_mean_shape, init_mean_pose, data_tensors,
+                                confidence_inputs, device, pose_prior=None) -> torch.Tensor:
+    """``optimize_shape_pass`` for S sequences together, on the device (``k2b_shape_pass_lbfgs``): one independent L-BFGS over
+    the betas of every sequence (``max_iter = num_shape_iters``, ``lr = 0.1``, strong Wolfe; the first ``num_shape_frames``
+    frames of each sequence, the same loss).  Per closure round ONE evaluate-only fused launch over all frames of all sequences,
+    a small kernel before it (root-aligned translations from each sequence's betas) and a fixed-order reduction after it; no
+    host synchronisation per round.  ``data_tensors`` / ``confidence_inputs``: per sequence (T_s, K, 3) and its confidences
+    (the first row is used, as in the single pass).  Returns (S, NB) betas.
+
+    The optimiser is this library's restatement of torch's L-BFGS, not ``torch.optim.LBFGS`` itself, so the result agrees with
+    ``optimize_shape_pass`` within a tolerance (the loss is quadratic in the betas at the fixed pose: both reach the same
+    minimiser), and a sequence's result does not depend on the other sequences of the batch."""
+    if not seq_config.frame.use_lbfgs:
+        raise RuntimeError(
+            "use_shape_optimization=True with use_lbfgs=False: the reference's Adam branch of the shape "
+            "pre-pass raises (core/shape.py:10,110-113); set use_shape_optimization=False or use_lbfgs=True")
+    from .. import native
+    from ..prior import MaxMixturePrior
+    from .constants import category_indices, root_indices
+
+    m = as_body_model(model)
+    dev = m.device
+    cat = seq_config.frame.joints_category
+    smpl_index, corr_index = category_indices(cat)
+    if smpl_index is None:
+        raise ValueError(f"No such joints category: {cat}")
+    root_model, root_target = root_indices(cat)
+    mean_shape = torch.as_tensor(init_mean_shape, dtype=torch.float32).to(dev).reshape(1, -1)
+    nb = int(mean_shape.shape[1])
+    if nb > int(m.num_betas):
+        raise ValueError(f"init_mean_shape has more coefficients than the model's {int(m.num_betas)}")
+    S = len(data_tensors)
+    ys, confs, counts = [], [], []
+    for data, c in zip(data_tensors, confidence_inputs):
+        t = int(data.shape[0])
+        n = t if (seq_config.num_shape_frames < 0 or seq_config.num_shape_frames >= t) else seq_config.num_shape_frames
+        y = torch.as_tensor(data, dtype=torch.float32).to(dev)[:n]
+        cf = torch.as_tensor(c, dtype=torch.float32).to(dev)
+        cf = (cf if cf.dim() == 1 else cf[0])[list(corr_index)]
+        ys.append(y)
+        confs.append(cf.reshape(1, -1).expand(n, -1))
+        counts.append(n)
+    y = torch.cat(ys, dim=0)
+    N = int(y.shape[0])
+    targets = y[:, list(corr_index)].contiguous()
+    root_y = y[:, root_target].contiguous()
+    conf = torch.cat(confs, dim=0).contiguous()
+    pose = torch.as_tensor(init_mean_pose, dtype=torch.float32).to(dev).reshape(1, -1).expand(N, -1).contiguous()
+    go, bp = pose[:, :3].contiguous(), pose[:, 3:].contiguous()
+    packed = getattr(m, "packed", False)
+    if packed:
+        bp = m.pack_pose(N, body_pose=bp[:, :3 * m.NUM_BODY_JOINTS]) if N > 0 else torch.zeros((0, 3 * (m.num_joints - 1)), device=dev)
+    prior = pose_prior if pose_prior is not None else MaxMixturePrior(
+        prior_folder="./data/models/", num_gaussians=seq_config.frame.pose_prior_num_gaussians, device=dev)
+    cfg = native.default_fit_config()
+    cfg.sigma, cfg.joint_loss_weight = 1.0e8, 1.0             # plain squared error (as optimize_shape_pass)
+    cfg.pose_prior_weight = cfg.angle_prior_weight = cfg.pose_preserve_weight = 0.0
+    cfg.shape_prior_weight = float(seq_config.frame.shape_prior_weight)
+    if packed:
+        cfg.prior_pose_dims, cfg.num_betas_prior = 3 * m.NUM_BODY_JOINTS, m.num_betas
+    off = torch.tensor(np.concatenate(([0], np.cumsum(counts))).astype(np.int32), device=dev)
+    return native.shape_pass_lbfgs(m.native, prior.native, cfg, off, list(smpl_index), targets, conf, go, bp, root_y,
+                                   int(root_model), mean_shape.expand(S, -1).contiguous(),
+                                   max_iter=int(seq_config.num_shape_iters), lr=0.1)

@@ -63,3 +63,7 @@ class OptimizationEstimator:
         """One sequence in warm-start mode as one launch (``WorldSpaceFitter.fit_chain``)."""
         return self._fitter.fit_chain(init_params, j3d, conf_3d, target_model_indices, run_forward=run_forward,
                                       **self._weights())
+
+    def fit_chains(self, init_params, j3d, conf_3d, lengths, target_model_indices=None):
+        """Many sequences of different lengths in warm-start mode as one launch (``WorldSpaceFitter.fit_chains``)."""
+        return self._fitter.fit_chains(init_params, j3d, conf_3d, lengths, target_model_indices, **self._weights())

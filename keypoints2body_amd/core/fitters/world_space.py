@@ -224,6 +224,43 @@ class WorldSpaceFitter:
         joints, verts = self.final_forward(out, want_vertices=want_vertices)
         return out, joints, verts, out["loss"]
 
+    def chains_supported(self, target_model_indices=None) -> bool:
+        """Whether ``fit_chains`` takes this fitter's configuration in ONE launch - the native entries' own rules: Adam with
+        kinematic targets on any model (``k2b_fit_sequences``); L-BFGS on the device driver with the 24-joint model and kinematic
+        targets (``k2b_fit_sequences_lbfgs``).  Decided before anything runs, so that a caller can route first."""
+        if not self.chain_supported(target_model_indices):
+            return False
+        if not self.use_lbfgs:
+            return True
+        idx = self.smpl_index if target_model_indices is None else torch.as_tensor(target_model_indices).reshape(-1).tolist()
+        return (self.smpl.num_joints == 24 and not self.smpl.packed and idx is not None
+                and all(0 <= int(i) < self.smpl.num_joints for i in idx))
+
+    def fit_chains(self, init_params: SMPLData, j3d, conf_3d, lengths, target_model_indices=None,
+                   joint_loss_weight: float = 600.0, pose_preserve_weight: float = 5.0, freeze_betas: bool = False):
+        """``fit_chain`` for S sequences of different lengths at once (``k2b_fit_sequences`` / ``k2b_fit_sequences_lbfgs``: ONE
+        launch): ``init_params`` with one row per sequence, ``j3d`` packed (sum T, K, 3), ``conf_3d`` packed per frame
+        (sum T, K) or shared (K,), ``lengths`` (S,).  Returns the packed params dict (``loss`` per frame); no forward.  Every
+        sequence's rows equal ``fit_chain`` on it alone, bit for bit.  ``NotImplementedError`` where the native entry does not
+        take the configuration (L-BFGS with SMPL-H / SMPL-X, surface targets): the caller fits sequence by sequence."""
+        if not self.chain_supported(target_model_indices):
+            raise NotImplementedError("fit_chains: the Adam branch with kinematic targets, or the L-BFGS branch on the device driver")
+        per_frame = conf_3d is not None and torch.as_tensor(conf_3d).dim() == 2
+        S = int(np.asarray(lengths).reshape(-1).shape[0])
+        go, bp, be, tr, model_idx, tgt, conf = self._prepare(init_params, j3d, conf_3d, target_model_indices, per_frame,
+                                                             num_init=S)
+        cfg = self._config(0, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
+        cfg.pose_preserve_weight = float(pose_preserve_weight)      # frames >= 1 (frame 0 has no preserve term)
+        if self.smpl.packed:
+            cfg.prior_pose_dims, cfg.num_betas_prior = 3 * self.smpl.NUM_BODY_JOINTS, self.smpl.num_betas
+        if self.use_lbfgs:
+            cfg.freeze_betas = int(bool(freeze_betas))
+            return native.fit_sequences_lbfgs(self.smpl.native, self.pose_prior.native, cfg, int(self.num_iters_first),
+                                              int(self.num_iters_followup), model_idx, lengths, tgt, conf, go, bp, be, tr,
+                                              lr=float(self.step_size))
+        return native.fit_sequences(self.smpl.native, self.pose_prior.native, cfg, int(self.num_iters_followup), model_idx,
+                                    lengths, tgt, conf, go, bp, be, tr)
+
     def packed_init(self, init):
         """Kernel layout of SMPL-X parameters: ``body_pose`` = all 162 non-root joint values, ``betas`` = betas | expression."""
         B = init.global_orient.shape[0]

@@ -235,7 +235,7 @@ int build_vertex_set(k2b_model* m, k2b_model::VertexSet& vs, const std::vector<i
 
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 2u; }
+uint32_t k2b_version(void) { return (1u << 16) | 3u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
@@ -900,7 +900,8 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
 int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int prior_dims, int32_t B, int32_t K,
              const int32_t* model_joint_index, const float* j3d, const float* conf, const float* go_in, const float* bp_in,
              const float* be_in, const float* tr_in, const float* preserve, const float* tr_prior, float* go_out, float* bp_out,
-             float* be_out, float* tr_out, float* loss_out, float* grad_out, void* stream, int chain_len = 1, int chain_iters = 0) {
+             float* be_out, float* tr_out, float* loss_out, float* grad_out, void* stream, int chain_len = 1, int chain_iters = 0,
+             const int* chain_meta = nullptr) {
     const int J = model->J, NB = model->NB;
     if (prior_dims < 3 || prior_dims > 64 || prior_dims % 3 != 0 || prior_dims > prior->D || prior_dims > 3 * (J - 1))
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the tree kernel takes a prior over the first 3..63 body-pose dimensions "
@@ -993,6 +994,7 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     a.opt_mask = cfg->optimize_mask & 15;
     a.chain_len = chain_len > 1 ? chain_len : 1;
     a.chain_iters = chain_iters;
+    a.chain_meta = chain_len > 1 ? chain_meta : nullptr;
     if (cfg->debug_launch_shape < 0 || cfg->debug_launch_shape > 4)
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: debug_launch_shape=%d must be 0..4", cfg->debug_launch_shape);
     a.debug_shape = cfg->debug_launch_shape <= 2 ? cfg->debug_launch_shape : 0;   // tree kernel: 1 = plain, 2 = component waves
@@ -1104,7 +1106,8 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
                    const float* bp_in, const float* be_in, const float* tr_in, const float* preserve,
                    const float* tr_prior, float* go_out,
                    float* bp_out, float* be_out, float* tr_out, float* loss_out, float* grad_out, void* stream,
-                   int chain_len, int chain_iters, int lb_mode = 0, const k2b::LbfgsArgs* lb_host = nullptr, int lb_chain_max_iter = 0) {
+                   int chain_len, int chain_iters, int lb_mode = 0, const k2b::LbfgsArgs* lb_host = nullptr, int lb_chain_max_iter = 0,
+                   const int* chain_meta = nullptr) {
     k2b_model* model = const_cast<k2b_model*>(model_c);
     if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model, prior and cfg are required");
     const int pose_dims_all = 3 * (model->J - 1);
@@ -1117,7 +1120,7 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence: no explicit preserve pose, translation prior or gradient output in a chain");
     if (!small_tree)
         return fit_tree(model, const_cast<k2b_prior*>(prior), cfg, prior_dims, B, K, model_joint_index, j3d, conf, go_in, bp_in, be_in, tr_in,
-                        preserve, tr_prior, go_out, bp_out, be_out, tr_out, loss_out, grad_out, stream, chain_len, chain_iters);
+                        preserve, tr_prior, go_out, bp_out, be_out, tr_out, loss_out, grad_out, stream, chain_len, chain_iters, chain_meta);
     if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_frames=%d", B);
     if (K < 1 || K > model->J + model->E + model->L) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_targets=%d out of range", K);
     if (!model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: model_joint_index is NULL");
@@ -1204,6 +1207,7 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
     a.force_shape = cfg->debug_launch_shape;
     a.chain_len = chain_len > 1 ? chain_len : 1;
     a.chain_iters = chain_iters;
+    a.chain_meta = chain_len > 1 ? chain_meta : nullptr;
     a.num_cus = device_cus();
     a.lb_mode = lb_mode;
     if (lb_host) { a.lbv = *lb_host; a.lb_loss = lb_host->loss_in; a.lb_grad = lb_host->grad_in; a.lb_history = lb_host->H; }
@@ -1468,6 +1472,258 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
                                      loss_out ? loss_out + t : nullptr, nullptr, iters, H, lr, tolerance_grad, tolerance_change, w, stream_v);
             rc != K2B_OK) return cleanup(rc);
     }
+#undef K2B_TRY_WS
+    return cleanup(K2B_OK);
+}
+
+namespace {
+// Ragged sequences of the k2b_fit_sequences* entries: the arguments checked, then the chain slots in launch order - sequences
+// with frames, longest first (ties in the caller's order), so that sequences of similar length share a workgroup and the long
+// chains start in the first wave of workgroups.  meta[slot] = {sequence (row of its start parameters), first frame row, frames, 0}.
+struct RaggedSlots {
+    std::vector<int> meta;
+    int slots = 0, max_len = 0;
+};
+int ragged_slots(const char* who, int32_t S, const int32_t* lengths, const int32_t* offsets, RaggedSlots* r) {
+    if (S < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_sequences=%d", who, S);
+    if (S > 0 && (!lengths || !offsets)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lengths and offsets are required", who);
+    int64_t next = 0;
+    for (int s = 0; s < S; ++s) {
+        if (lengths[s] < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lengths[%d]=%d", who, s, lengths[s]);
+        if (offsets[s] != next)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: offsets[%d]=%d, expected %lld (the exclusive prefix sum of lengths)", who, s,
+                        offsets[s], (long long)next);
+        next += lengths[s];
+        if (next > ((int64_t)1 << 30)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: more than 2^30 frames", who);
+    }
+    std::vector<int> order;
+    for (int s = 0; s < S; ++s)
+        if (lengths[s] > 0) order.push_back(s);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lengths[x] > lengths[y]; });
+    r->slots = (int)order.size();
+    r->max_len = r->slots ? lengths[order[0]] : 0;
+    r->meta.assign((size_t)r->slots * 4, 0);
+    for (int i = 0; i < r->slots; ++i) {
+        r->meta[(size_t)i * 4 + 0] = order[i];
+        r->meta[(size_t)i * 4 + 1] = offsets[order[i]];
+        r->meta[(size_t)i * 4 + 2] = lengths[order[i]];
+    }
+    return K2B_OK;
+}
+bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx) {
+    for (int k = 0; k < K; ++k)
+        if (idx[k] >= m->J) return false;
+    return true;
+}
+// every model joint index inside the model's outputs (joints, extra joints, landmarks)
+int check_targets(const char* who, const k2b_model* m, int32_t K, const int32_t* idx) {
+    if (K < 1 || !idx) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_targets=%d / model_joint_index", who, K);
+    for (int k = 0; k < K; ++k)
+        if (idx[k] < 0 || idx[k] >= m->J + m->E + m->L)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model_joint_index[%d]=%d out of range", who, k, idx[k]);
+    return K2B_OK;
+}
+// The slot table goes up through pinned staging owned by the calling thread: the copy is stream-ordered and the host never
+// waits for the stream - only, before the staging is reused, for the previous call's copy out of it (normally long done).
+// (One grow-only pinned buffer and one event per thread that calls the entries; they live as long as the thread's runtime.)
+int upload_slots(const std::vector<int>& meta, int* dev, hipStream_t stream) {
+    struct Stage { int* host = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; };
+    thread_local Stage st;
+    const size_t n = meta.size();
+    if (st.copied) HIP_TRY(hipEventSynchronize(st.copied));
+    if (n > st.cap) {
+        if (st.host) HIP_TRY(hipHostFree(st.host));
+        st.host = nullptr;
+        st.cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&st.host, n * sizeof(int), hipHostMallocDefault));
+        st.cap = n;
+    }
+    if (!st.copied) HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    memcpy(st.host, meta.data(), n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(dev, st.host, n * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(st.copied, stream));
+    return K2B_OK;
+}
+}  // namespace
+
+// Many warm-start sequences of different lengths side by side (the Adam branch): every sequence is k2b_fit_sequence's chain,
+// packed frames [sum T][...], ONE launch (the fused kernel for 24-joint models, the tree kernel for SMPL-H / SMPL-X).  A
+// sequence's result does not depend on the others, on their number or on their order.
+int k2b_fit_sequences(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                      const int32_t* lengths, const int32_t* offsets, int32_t followup_iters, int32_t K,
+                      const int32_t* model_joint_index, const float* j3d, const float* conf, const float* go_in,
+                      const float* bp_in, const float* be_in, const float* tr_in, float* go_out, float* bp_out, float* be_out,
+                      float* tr_out, float* loss_out, void* stream_v) {
+    const char* who = "k2b_fit_sequences";
+    RaggedSlots r;
+    if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
+    if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (followup_iters < 1 || followup_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
+    if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_iters=%d", who, cfg->num_iters);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
+    if (const int rc = check_targets(who, model, K, model_joint_index); rc != K2B_OK) return rc;
+    if (r.slots == 0) return K2B_OK;
+    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    if (!kinematic_only(model, K, model_joint_index))
+        return fail(K2B_ERR_UNSUPPORTED, "%s: surface targets (vertex-selected joints, landmarks) are not built into the chain", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    int* meta = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&meta, r.meta.size() * sizeof(int), stream));
+    if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) {
+        (void)hipFreeAsync(meta, stream);
+        return rc;
+    }
+    // chain_len > 1 selects the chain; the steps come from the table (a workgroup walks its longest sequence)
+    const int rc = fit_world_impl(model, prior, cfg, r.slots, K, model_joint_index, j3d, conf, go_in, bp_in, be_in, tr_in, nullptr,
+                                  nullptr, go_out, bp_out, be_out, tr_out, loss_out, nullptr, stream_v,
+                                  r.max_len > 1 ? r.max_len : 2, followup_iters, 0, nullptr, 0, meta);
+    (void)hipFreeAsync(meta, stream);
+    return rc;
+}
+
+// The default sequence mode (L-BFGS, warm start) for many sequences of different lengths: k2b_fit_sequence_lbfgs's persistent
+// chain with one optimiser per sequence, ONE launch (24-joint model, the prior over the whole pose, kinematic targets; other
+// configurations: K2B_ERR_UNSUPPORTED, the caller fits sequence by sequence).
+int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                            const int32_t* lengths, const int32_t* offsets, int32_t K, const int32_t* model_joint_index,
+                            const float* j3d, const float* conf, const float* go_in, const float* bp_in, const float* be_in,
+                            const float* tr_in, float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out,
+                            int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr, double tolerance_grad,
+                            double tolerance_change, void* stream_v) {
+    const char* who = "k2b_fit_sequences_lbfgs";
+    RaggedSlots r;
+    if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
+    if (const int rc = lbfgs_check(model_c, prior, cfg, first_iters, &history_size, lr, who); rc != K2B_OK) return rc;
+    if (followup_iters < 1 || followup_iters > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
+    if (const int rc = check_targets(who, model_c, K, model_joint_index); rc != K2B_OK) return rc;
+    if (r.slots == 0) return K2B_OK;
+    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    const int pose_dims_all = 3 * (model_c->J - 1);
+    const int prior_dims = cfg->prior_pose_dims > 0 ? cfg->prior_pose_dims : (prior->D < pose_dims_all ? prior->D : pose_dims_all);
+    if (!(model_c->fit_ok && prior->D == pose_dims_all && prior_dims == pose_dims_all &&
+          (cfg->num_betas_prior == 0 || cfg->num_betas_prior == model_c->NB) && kinematic_only(model_c, K, model_joint_index)))
+        return fail(K2B_ERR_UNSUPPORTED, "%s: one launch needs the 24-joint model, the prior over the whole pose and kinematic targets", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int NB = model_c->NB, D = pose_dims_all, P = 3 + D + NB + 3;
+    const int it_max = first_iters > followup_iters ? first_iters : followup_iters;
+    const int Hmax = history_size < it_max ? history_size : it_max;
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(r.slots, P, Hmax, &w);
+    const size_t n_meta = (r.meta.size() * sizeof(int) + 15) / 16 * 16;
+    unsigned char* ws = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&ws, n_meta + n_opt, stream));
+    auto cleanup = [&](int rc) { (void)hipFreeAsync(ws, stream); return rc; };
+    int* meta = reinterpret_cast<int*>(ws);
+    if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) return cleanup(rc);
+    if (hipMemsetAsync(ws + n_meta, 0, w.off_sv, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return cleanup(fail(K2B_ERR_HIP, "%s: HIP call failed", who));
+    }
+    (void)lbfgs_ws_assign(&w, ws + n_meta, r.slots, P);
+    // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: lb_mode 3)
+    const int me_first = first_iters * 5 / 4, me_follow = followup_iters * 5 / 4;
+    k2b::LbfgsArgs la{};
+    la.B = r.slots; la.P = P; la.D = D; la.NB = NB; la.H = Hmax;
+    la.max_iter = first_iters; la.max_eval = me_first;
+    la.lr = lr; la.tol_g = tolerance_grad; la.tol_c = tolerance_change;
+    la.go = go_out; la.bp = bp_out; la.be = be_out; la.tr = tr_out;           // frame rows of the outputs: each frame's point
+    la.loss_in = w.lbuf; la.grad_in = w.gbuf;
+    la.sd = reinterpret_cast<double*>(w.base); la.si = reinterpret_cast<int*>(w.base + w.off_si); la.sv = reinterpret_cast<float*>(w.base + w.off_sv);
+    k2b_fit_config pc = *cfg;
+    pc.num_iters = me_first + 3;                                              // rounds + the closure at the result
+    pc.step_size = 0.0;
+    return cleanup(fit_world_impl(model_c, prior, &pc, r.slots, K, model_joint_index, j3d, conf, go_in, bp_in, be_in, tr_in, nullptr,
+                                  nullptr, go_out, bp_out, be_out, tr_out, loss_out, nullptr, stream_v, r.max_len > 1 ? r.max_len : 2,
+                                  me_follow + 3, 3, &la, followup_iters, meta));
+}
+
+int k2b_sequence_order(int32_t num_sequences, const int32_t* lengths, const int32_t* offsets, int32_t* order_out, int32_t* num_slots) {
+    RaggedSlots r;
+    if (const int rc = ragged_slots("k2b_sequence_order", num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
+    if (!num_slots || (r.slots > 0 && !order_out)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_sequence_order: NULL output");
+    for (int i = 0; i < r.slots; ++i) order_out[i] = r.meta[(size_t)i * 4];
+    *num_slots = r.slots;
+    return K2B_OK;
+}
+
+// The shape pre-pass of S sequences together (reference core/shape.py:10-115, one torch.optim.LBFGS over betas per sequence):
+// per round [prep (k2b_shape.hip: shape rows, root-aligned translations) -> ONE evaluate-only fused launch over all frames ->
+// reduce (per-sequence loss and gradient in frame order) -> the L-BFGS state machine, one instance per sequence]; max_eval + 2
+// rounds and the finalise step are queued on `stream`, nothing comes back to the host.
+int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                         const int32_t* seq_offsets, int32_t num_frames, int32_t K, const int32_t* model_joint_index,
+                         const float* j3d, const float* conf, const float* global_orient, const float* body_pose,
+                         const float* root_targets, int32_t root_joint, int32_t num_free_betas, const float* betas_in,
+                         float* betas_out, int32_t max_iter, int32_t history_size, double lr, double tolerance_grad,
+                         double tolerance_change, void* stream_v) {
+    const char* who = "k2b_shape_pass_lbfgs";
+    if (const int rc = lbfgs_check(model_c, prior, cfg, max_iter, &history_size, lr, who); rc != K2B_OK) return rc;
+    if (num_sequences < 0 || num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: %d sequences, %d frames", who, num_sequences, num_frames);
+    const int J = model_c->J, NB = model_c->NB, D = 3 * (J - 1), P = 3 + D + NB + 3;
+    if (root_joint < 0 || root_joint >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: root_joint=%d", who, root_joint);
+    if (num_free_betas < 1 || num_free_betas > NB || num_free_betas > 32)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_free_betas=%d (1..min(%d, 32))", who, num_free_betas, NB);
+    if (K < 1 || !model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_targets=%d / model_joint_index", who, K);
+    for (int k = 0; k < K; ++k)
+        if (model_joint_index[k] < 0 || model_joint_index[k] >= J)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model_joint_index[%d]=%d (kinematic joints only)", who, k, model_joint_index[k]);
+    if (num_sequences == 0) return K2B_OK;
+    if (!seq_offsets || !betas_in || !betas_out || (num_frames > 0 && (!j3d || !global_orient || !body_pose || !root_targets)))
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL buffer", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int S = num_sequences, N = num_frames, nb = num_free_betas;
+    const int H = history_size < max_iter ? history_size : max_iter;
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(S, P, H, &w);
+    // behind the optimiser's workspace: its parameter arrays [S][...], then the per-frame closure buffers [N][...]
+    const size_t n_par = (size_t)S * P, n_frm = (size_t)N * (NB + 3 + 3 + D + NB + 3 + 1 + P);
+    unsigned char* ws = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&ws, n_opt + (n_par + n_frm) * sizeof(float), stream));
+    auto cleanup = [&](int rc) { (void)hipFreeAsync(ws, stream); return rc; };
+#define K2B_TRY_WS(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return cleanup(fail(K2B_ERR_HIP, "k2b_shape_pass_lbfgs: HIP call failed")); } } while (0)
+    float* go_s = lbfgs_ws_assign(&w, ws, S, P);
+    float *bp_s = go_s + (size_t)S * 3, *be_s = bp_s + (size_t)S * D, *tr_s = be_s + (size_t)S * NB;
+    float *be_f = tr_s + (size_t)S * 3, *tr_f = be_f + (size_t)N * NB;
+    float *go_o = tr_f + (size_t)N * 3, *bp_o = go_o + (size_t)N * 3, *be_o = bp_o + (size_t)N * D, *tr_o = be_o + (size_t)N * NB;
+    float *loss_f = tr_o + (size_t)N * 3, *grad_f = loss_f + N;
+    K2B_TRY_WS(hipMemsetAsync(w.base, 0, w.off_sv, stream));                              // every instance in phase INIT
+    K2B_TRY_WS(hipMemsetAsync(go_s, 0, n_par * sizeof(float), stream));                   // pose / transl of the points: 0, never move
+    K2B_TRY_WS(hipMemcpy2DAsync(be_s, (size_t)NB * sizeof(float), betas_in, (size_t)nb * sizeof(float), (size_t)nb * sizeof(float), S,
+                                hipMemcpyDeviceToDevice, stream));
+    k2b::ShapePassArgs sa{};
+    sa.S = S; sa.D = D; sa.NB = NB; sa.nb = nb; sa.seq_off = seq_offsets;
+    sa.jt0 = model_c->j_template + (size_t)root_joint * 3; sa.jd0 = model_c->j_dirs + (size_t)root_joint * 3 * NB;
+    sa.root_y = root_targets; sa.be_state = be_s; sa.be_f = be_f; sa.tr_f = tr_f; sa.grad_f = grad_f; sa.loss_f = loss_f;
+    sa.grad_state = w.gbuf; sa.loss_state = w.lbuf;
+    k2b_fit_config ec = *cfg;
+    ec.num_iters = 1;
+    ec.step_size = 0.0;                                                                  // evaluate-only: the closure
+    ec.conf_per_frame = conf ? 1 : 0;
+    k2b::LbfgsArgs la{};
+    la.B = S; la.P = P; la.D = D; la.NB = NB; la.H = H;
+    la.max_iter = max_iter; la.max_eval = max_iter * 5 / 4;                              // torch's default
+    la.lr = lr; la.tol_g = tolerance_grad; la.tol_c = tolerance_change;
+    la.go = go_s; la.bp = bp_s; la.be = be_s; la.tr = tr_s;
+    la.loss_in = w.lbuf; la.grad_in = w.gbuf;
+    la.sd = reinterpret_cast<double*>(w.base); la.si = reinterpret_cast<int*>(w.base + w.off_si); la.sv = reinterpret_cast<float*>(w.base + w.off_sv);
+    const int rounds = la.max_eval + 2;
+    for (int r = 0; r < rounds; ++r) {
+        K2B_TRY_WS(k2b::launch_shape_prep(sa, stream));
+        if (N > 0) {
+            if (const int rc = fit_world_impl(model_c, prior, &ec, N, K, model_joint_index, j3d, conf, global_orient, body_pose, be_f,
+                                              tr_f, nullptr, nullptr, go_o, bp_o, be_o, tr_o, loss_f, grad_f, stream_v, 1, 0);
+                rc != K2B_OK) return cleanup(rc);
+        }
+        K2B_TRY_WS(k2b::launch_shape_reduce(sa, stream));
+        K2B_TRY_WS(k2b::launch_lbfgs_step(la, stream));
+    }
+    la.finalize = 1;
+    K2B_TRY_WS(k2b::launch_lbfgs_step(la, stream));                                       // the accepted points
+    K2B_TRY_WS(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), be_s, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
+                                hipMemcpyDeviceToDevice, stream));
 #undef K2B_TRY_WS
     return cleanup(K2B_OK);
 }

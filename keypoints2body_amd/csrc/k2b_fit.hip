@@ -251,6 +251,33 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         f_valid[h] = slot0 + h < F && f_raw < a.num_frames;
         f[h] = f_raw < a.num_frames ? f_raw : a.num_frames - 1;
     }
+    // warm-start chains (split shapes only): slot fs is a sequence - row of its start parameters, first frame row, frame count
+    // (FitArgs::chain_meta; without it sequence fs of chain_len frames).  The workgroup walks as many steps as its longest slot
+    // (every wave takes every step's barriers); a slot whose sequence has ended stays in the loop and writes nothing.
+    auto chain_slot = [&](int fs, int& srow, int& off, int& len) {
+        if (a.chain_meta) {
+            const int4 m = reinterpret_cast<const int4*>(a.chain_meta)[fs];
+            srow = m.x; off = m.y; len = m.z;
+        } else {
+            srow = fs; off = fs * a.chain_len; len = a.chain_len;
+        }
+    };
+    int c_srow = f[0], c_off = f[0], c_len = 1, c_steps = 1;     // (independent frames: one step, frame row f)
+    if (!PAIR && a.chain_len > 1) {
+        chain_slot(f[0], c_srow, c_off, c_len);
+        for (int s = 0; s < F; ++s) {
+            const int fs = blockIdx.x * F + s;
+            if (fs >= a.num_frames) break;
+            int r_, o_, l_;
+            chain_slot(fs, r_, o_, l_);
+            c_steps = l_ > c_steps ? l_ : c_steps;
+        }
+        // (wave-uniform: scalar registers - the persistent L-BFGS shape has no vector registers to spare)
+        c_srow = __builtin_amdgcn_readfirstlane(c_srow);
+        c_off = __builtin_amdgcn_readfirstlane(c_off);
+        c_len = __builtin_amdgcn_readfirstlane(c_len);
+        c_steps = __builtin_amdgcn_readfirstlane(c_steps);
+    }
 
     const float* cmu = lds + RIM_FLOATS;                                // [m][mu | c][64]
     const half8* rimfrag = reinterpret_cast<const half8*>(lds + RIM_FLOATS + CMU_FLOATS);   // [m][fragment 4][21 entries]
@@ -382,7 +409,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     Vec3 tgt = {0.f, 0.f, 0.f};
     float wconf = 0.f;  // w_j^2 c^2
     if (tk >= 0) {
-        const size_t ft = (size_t)(PAIR ? (hb ? f[FW - 1] : f[0]) : f[0]) * (a.chain_len > 1 ? a.chain_len : 1);
+        const size_t ft = (size_t)(PAIR ? (hb ? f[FW - 1] : f[0]) : c_off);          // (a chain: its first frame)
         const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
         tgt = {y[0], y[1], y[2]};
         const float c = a.conf ? a.conf[(a.conf_per_frame ? ft * a.num_targets : 0) + tk] : 1.0f;
@@ -418,13 +445,19 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     // persistent L-BFGS (lb_mode 3): see the tree waves' loop
     const bool lb_loop = MODE == MODE_SPLIT_LBFGS && a.lb_mode == 3;
     bool lb_step = false;
-    int lb_frame = 0, lb_pairs = 0;
+    int lb_frame = 0, lb_pairs = 0, lb_off = 0, lb_len = 1;
     unsigned char* lb_stage = nullptr;
     if constexpr (MODE == MODE_SPLIT_LBFGS) {
         if (lb_loop && wave >= NROW && wave - NROW < F) {
             const int sl = wave - NROW;                           // slot whose optimiser this (idle) tree wave is
             lb_frame = blockIdx.x * F + sl;
             lb_step = lb_frame < a.num_frames;
+            if (lb_step && a.chain_len > 1) {                     // (its sequence: frame rows and count)
+                int r_;
+                chain_slot(lb_frame, r_, lb_off, lb_len);
+                lb_off = __builtin_amdgcn_readfirstlane(lb_off);
+                lb_len = __builtin_amdgcn_readfirstlane(lb_len);
+            }
             // staging LDS: the half of the lo-fragment area the split shape never writes (components 0..3 keep theirs in registers)
             constexpr int kFree = PLO_FLOATS * 4 / 2;
             const int per = (kFree / F) & ~15;
@@ -447,11 +480,12 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     float m0[FW], v0[FW], m1[FW], v1[FW], g0[FW], g1[FW], loss_total[FW];
 #pragma unroll
     for (int h = 0; h < FW; ++h) {
-        x0[h] = *param_ptr(f[h], pA, a.go_in, a.bp_in, a.be_in, a.tr_in);
-        x1[h] = actB ? *param_ptr(f[h], pB, a.go_in, a.bp_in, a.be_in, a.tr_in) : 0.f;
-        pr0[h] = prsrc[(size_t)f[h] * D + lane];
-        pr1[h] = bodyB ? prsrc[(size_t)f[h] * D + NC + lane] : 0.f;
-        tp1[h] = translB ? a.tr_prior[(size_t)f[h] * 3 + (lane - 8 - NB)] : 0.f;   // centre of the transl prior
+        const int sr = PAIR ? f[h] : c_srow;                                  // (a chain: the start row of its sequence)
+        x0[h] = *param_ptr(sr, pA, a.go_in, a.bp_in, a.be_in, a.tr_in);
+        x1[h] = actB ? *param_ptr(sr, pB, a.go_in, a.bp_in, a.be_in, a.tr_in) : 0.f;
+        pr0[h] = prsrc[(size_t)sr * D + lane];
+        pr1[h] = bodyB ? prsrc[(size_t)sr * D + NC + lane] : 0.f;
+        tp1[h] = translB ? a.tr_prior[(size_t)sr * 3 + (lane - 8 - NB)] : 0.f;   // centre of the transl prior
         m0[h] = v0[h] = m1[h] = v1[h] = g0[h] = g1[h] = loss_total[h] = 0.f;
     }
 
@@ -881,7 +915,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         // (wide shape, same-box A/B at 4096 frames: tree waves 3 / row waves 0 0.3815 ms; rows above trees 0.417; all equal 0.417 -
         //  the row waves issue few instructions and are starved either way, the tree waves are what the SIMD must keep fed)
         __builtin_amdgcn_s_setprio(3);
-        const int steps = PAIR ? 1 : a.chain_len;
+        const int steps = PAIR ? 1 : c_steps;
         // persistent L-BFGS (lb_mode 3, at most two frames per workgroup): the IDLE tree wave 4 + s is slot s's optimiser, its state -
         // 27 scalars, eight vectors, the history in LDS by ring slot - RESIDENT in registers and LDS for the whole fit (the state
         // arrays in global memory are only written at the end).  Between two more barriers per iteration it consumes the closure
@@ -909,15 +943,17 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         }
         for (int step = 0; step < steps; ++step) {
             const int nit = step == 0 ? a.num_iters : a.chain_iters;
+            bool lb_act = lb_step;                            // this wave's optimiser runs in this step (a chain: its sequence has not ended)
             if constexpr (MODE == MODE_SPLIT_LBFGS) {
                 if (lb_loop && a.chain_len > 1) {             // sequence chain: a fresh optimiser per frame, on the frame's own parameter row
-                    fr.restart(lb_frame * a.chain_len + step);
+                    lb_act = lb_step && step < lb_len;        // (an ended sequence's optimiser stays parked: no restart, no state written)
+                    if (lb_act) fr.restart(lb_off + step);
                     la.max_iter = step == 0 ? a.lbv.max_iter : a.lb_chain_max_iter;
                     la.max_eval = la.max_iter * 5 / 4;
                 }
             }
-            if (!PAIR && step > 0 && tk >= 0) {           // targets of this step's frame (sequence s, frame row s chain_len + step)
-                const size_t ft = (size_t)f[0] * a.chain_len + step;
+            if (!PAIR && step > 0 && step < c_len && tk >= 0) {   // targets of this step's frame (row off + step of the slot's sequence)
+                const size_t ft = (size_t)c_off + step;
                 const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
                 tgt = {y[0], y[1], y[2]};
                 const float c = a.conf ? a.conf[(a.conf_per_frame ? ft * a.num_targets : 0) + tk] : 1.0f;
@@ -935,7 +971,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 if constexpr (MODE == MODE_SPLIT_LBFGS) {
                     if (lb_loop) {
                         __syncthreads();
-                        if (lb_step && it < nit - 1) {
+                        if (lb_step && !lb_act && it < nit - 1 && lane == 0) lb_done_cell[wave - NROW] = 1;   // (ended: never holds the workgroup back)
+                        if (lb_act && it < nit - 1) {
                             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                             // (the closure's loss is a wave-uniform = SCALAR load, and the scalar cache is not coherent with the row wave's
                             //  vector store of a round ago: drop it)
@@ -957,7 +994,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                         // every optimiser of the workgroup is done: the closures left would evaluate the same points again - skip to
                         // the final one (the flags are read by every wave behind the same barrier: uniform)
                         const bool all_done = lb_done_cell[0] != 0 && lb_done_cell[1] != 0;
-                        if (lb_step && (it == nit - 2 || (all_done && it < nit - 2))) fr.save();
+                        if (lb_act && (it == nit - 2 || (all_done && it < nit - 2))) fr.save();
                         if (all_done && it < nit - 2) it = nit - 2;
                     }
                 }
@@ -1226,9 +1263,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             return a.tr_out + fr * 3 + (p - 3 - D - NB);
         };
         int git = 0;                 // iterations over all chain steps (the row waves' meeting counter runs on)
-        const int steps = PAIR ? 1 : a.chain_len;
+        const int steps = PAIR ? 1 : c_steps;
         for (int step = 0; step < steps; ++step) {
             const int nit = step == 0 ? a.num_iters : a.chain_iters;
+            const bool c_act = step < c_len;                  // (chain: this slot's sequence still has a frame at this step)
             if (!PAIR && step > 0) { // (chain: FW == 1) start from the previous result, preserve it, fresh Adam state
                 wpr2 = a.preserve_w * a.preserve_w;
                 cqB = bodyB ? wpr2 : cqB;
@@ -1237,8 +1275,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 m0[0] = v0[0] = m1[0] = v1[0] = 0.f;
             }
             if constexpr (MODE == MODE_SPLIT_LBFGS) {
-                if (lb_loop && chain && do_row && f_valid[0]) {   // the frame's start point into ITS row of the parameter arrays: the
-                    const size_t fr_row = (size_t)f[0] * a.chain_len + step;     // optimiser reads it there (phase INIT) and moves it
+                if (lb_loop && chain && do_row && f_valid[0] && c_act) {   // the frame's start point into ITS row of the parameter arrays:
+                    const size_t fr_row = (size_t)c_off + step;                  // the optimiser reads it there (phase INIT) and moves it
                     *out_ptr_c(fr_row, pA) = x0[0];
                     if (actB) *out_ptr_c(fr_row, pB) = x1[0];
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -1280,7 +1318,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             if constexpr (MODE == MODE_SPLIT_LBFGS) {
                 if (lb_loop) {       // closure result out, next point in (the optimiser runs on the slot's idle tree wave in between)
                     const int P_ = 3 + D + NB + 3;
-                    if (do_row && f_valid[0] && !last) {
+                    if (do_row && f_valid[0] && !last && c_act) {
                         float* gdst = const_cast<float*>(a.lb_grad) + (size_t)f[0] * P_;
                         gdst[pA] = g0[0];
                         if (actB) gdst[pB] = g1[0];
@@ -1290,11 +1328,11 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                     __syncthreads();
                     __syncthreads();
                     if (lb_done_cell[0] != 0 && lb_done_cell[1] != 0 && it < nit - 2) it = nit - 2;   // (as the tree waves: every optimiser is done)
-                    if (do_row) {    // (also behind the last closure: whatever the zero-step Adam update made of a non-finite gradient, the
-                                     //  result is the parked point in the parameter arrays)
+                    if (do_row && c_act) {    // (also behind the last closure: whatever the zero-step Adam update made of a non-finite
+                                              //  gradient, the result is the parked point in the parameter arrays)
                         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                         if (chain) {
-                            const size_t fr_row = (size_t)f[0] * a.chain_len + step;
+                            const size_t fr_row = (size_t)c_off + step;
                             x0[0] = *out_ptr_c(fr_row, pA);
                             x1[0] = actB ? *out_ptr_c(fr_row, pB) : 0.f;
                         } else {
@@ -1306,8 +1344,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             }
         }
         K2B_FSTAMP_ROW_PRINT;
-            if (!PAIR && chain && do_row && f_valid[0]) {     // this step's frame: row s chain_len + step
-                const size_t fr = (size_t)f[0] * a.chain_len + step;
+            if (!PAIR && chain && do_row && f_valid[0] && c_act) {     // this step's frame: row off + step of the slot's sequence
+                const size_t fr = (size_t)c_off + step;
                 *out_ptr_c(fr, pA) = x0[0];
                 if (actB) *out_ptr_c(fr, pB) = x1[0];
                 if (lane == 0 && a.loss_out) a.loss_out[fr] = loss_total[0];

@@ -74,6 +74,24 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     const int fr_raw = blockIdx.x * tw + (comp_role ? 0 : wave);
     const bool frame_ok = !comp_role && fr_raw < a.num_frames;
     const int fr = frame_ok ? fr_raw : a.num_frames - 1;           // idle waves shadow the last frame and write nothing
+    // warm-start chains: this wave's sequence - row of its start parameters, first frame row, frame count (FitTreeArgs::chain_meta;
+    // without it sequence fr of chain_len frames) - and the steps of the workgroup = its longest sequence (every wave, the
+    // component waves included, takes every step's barriers; a wave whose sequence has ended writes nothing)
+    int c_srow = fr, c_off = fr, c_len = 1, c_steps = 1;
+    if (CHAIN) {
+        const int4* meta = reinterpret_cast<const int4*>(a.chain_meta);
+        if (meta) { const int4 m = meta[fr]; c_srow = m.x; c_off = m.y; c_len = m.z; }
+        else { c_off = fr * a.chain_len; c_len = a.chain_len; }
+        c_steps = a.chain_len;
+        if (meta) {
+            c_steps = 1;
+            for (int s = 0; s < tw; ++s) {
+                const int fs = blockIdx.x * tw + s;
+                if (fs >= a.num_frames) break;
+                c_steps = meta[fs].z > c_steps ? meta[fs].z : c_steps;
+            }
+        }
+    }
 
     // ---- prior image -> LDS (whole workgroup) ---------------------------------------------------------------------------
     if (ncw == 0)
@@ -98,7 +116,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
                 fh[o][t][0] = fi[0]; fh[o][t][1] = fi[64]; fl[o][t][0] = fi[128]; fl[o][t][1] = fi[192];
             }
         const float isc[2] = {sIsc[cw], sIsc[cw + 4]}, pcl[2] = {sPcl[cw], sPcl[cw + 4]};
-        const int steps = CHAIN ? a.chain_len : 1;
+        const int steps = CHAIN ? c_steps : 1;
         for (int step = 0; step < steps; ++step) {
             const int nit = step == 0 ? a.num_iters : a.chain_iters;
             for (int it = 0; it < nit; ++it) {
@@ -172,7 +190,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     const int tk = isJ ? a.lane_target[lane] : -1;
     float ty0 = 0.f, ty1 = 0.f, ty2 = 0.f, wconf = 0.f;
     if (tk >= 0) {
-        const size_t f0 = (size_t)fr * (CHAIN ? a.chain_len : 1);
+        const size_t f0 = (size_t)c_off;                 // (a chain: its first frame)
         const float* y = a.j3d + (f0 * a.num_targets + tk) * 3;
         ty0 = y[0]; ty1 = y[1]; ty2 = y[2];
         const float cf = a.conf ? a.conf[(a.conf_per_frame ? f0 * a.num_targets : 0) + tk] : 1.0f;
@@ -184,11 +202,11 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     const int D = 3 * (J - 1);
     float th[3] = {0.f, 0.f, 0.f};
     if (isJ) {
-        const float* src = joint == 0 ? a.go_in + (size_t)fr * 3 : a.bp_in + (size_t)fr * D + 3 * (joint - 1);
+        const float* src = joint == 0 ? a.go_in + (size_t)c_srow * 3 : a.bp_in + (size_t)c_srow * D + 3 * (joint - 1);
         th[0] = src[0]; th[1] = src[1]; th[2] = src[2];
     }
-    float sh = lane < NB ? a.be_in[(size_t)fr * NB + lane] : 0.f;
-    float tr = lane < 3 ? a.tr_in[(size_t)fr * 3 + lane] : 0.f;
+    float sh = lane < NB ? a.be_in[(size_t)c_srow * NB + lane] : 0.f;
+    float tr = lane < 3 ? a.tr_in[(size_t)c_srow * 3 + lane] : 0.f;
     float mth[3] = {0.f, 0.f, 0.f}, vth[3] = {0.f, 0.f, 0.f}, msh = 0.f, vsh = 0.f, mtr = 0.f, vtr = 0.f;
     // which parameters the optimiser owns
     const bool opt_th = isJ && (joint == 0 ? (a.opt_mask & 1) : (a.opt_mask & 2));
@@ -196,7 +214,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     const bool opt_tr = lane < 3 && (a.opt_mask & 8);
     // prior-layout constants (lane i = prior dimension i)
     const bool isP = lane < Dv;
-    float pres0 = isP ? (a.preserve ? a.preserve[(size_t)fr * D + lane] : a.bp_in[(size_t)fr * D + lane]) : 0.f;
+    float pres0 = isP ? (a.preserve ? a.preserve[(size_t)fr * D + lane] : a.bp_in[(size_t)c_srow * D + lane]) : 0.f;
     float ang_s = 0.f;                           // sign of the bending prior on this dimension (0: none)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -206,7 +224,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     // fresh optimiser state (reference api/sequence.py:214-281, world_space.py:159,211,214); frame rows fr * chain_len + step
     // (a template parameter: the plain launch keeps its register budget - with the chain's mutable state in the same
     //  instantiation the SMPL-X kernel went from 247 registers to 256 + 40 bytes of scratch)
-    const int chain = CHAIN ? a.chain_len : 1;
+    const int chain = CHAIN ? c_steps : 1;
     const float wpp = a.pose_prior_w * a.pose_prior_w, wang = a.angle_w * a.angle_w, wsh = a.shape_w * a.shape_w;
     float wpr = CHAIN ? 0.f : a.preserve_w * a.preserve_w;
 
@@ -216,8 +234,8 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     for (int step = 0; step < chain; ++step) {
     const int nit = step == 0 ? a.num_iters : a.chain_iters;
     if (CHAIN && step > 0) {
-        if (tk >= 0) {                           // targets of this step's frame
-            const size_t ft = (size_t)fr * chain + step;
+        if (tk >= 0 && step < c_len) {           // targets of this step's frame (row off + step of the wave's sequence)
+            const size_t ft = (size_t)c_off + step;
             const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
             ty0 = y[0]; ty1 = y[1]; ty2 = y[2];
             const float cf = a.conf ? a.conf[(a.conf_per_frame ? ft * a.num_targets : 0) + tk] : 1.0f;
@@ -448,8 +466,8 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
         adam(tr, mtr, vtr, gtr, opt_tr);
     }
     // results of this step's frame (a plain launch has one step and row fr)
-    if (frame_ok) {
-        const size_t fo = CHAIN ? (size_t)fr * chain + step : (size_t)fr;
+    if (frame_ok && step < c_len) {
+        const size_t fo = CHAIN ? (size_t)c_off + step : (size_t)fr;
         if (isJ) {
             float* dst = joint == 0 ? a.go_out + fo * 3 : a.bp_out + fo * D + 3 * (joint - 1);
             dst[0] = th[0]; dst[1] = th[1]; dst[2] = th[2];

@@ -85,6 +85,10 @@ struct FitArgs {
     const float *lb_loss, *lb_grad;
     int lb_history;
     int lb_chain_max_iter;      // lb_mode 3 with chain_len > 1 (the default sequence mode in ONE launch): max_iter of the follow-up frames (lbv: the first's)
+    // ragged chains (chain_len > 1): NULL = every slot s is sequence s with chain_len frames at rows s * chain_len; else [slot][4] =
+    // {row of the start parameters, first frame row, frame count >= 1, 0} (device).  A workgroup runs as many steps as its
+    // longest slot; a slot whose sequence has ended takes the barriers and writes nothing.
+    const int* chain_meta;
 };
 
 hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
@@ -123,10 +127,25 @@ struct FitTreeArgs {
     int angle_index[4];
     float angle_sign[4];
     int chain_len, chain_iters;  // warm-start chain: num_frames SEQUENCES of chain_len frames each (<= 1: independent frames)
-    int comp_waves;              // set by launch_fit_tree: 4 = the mixture runs on four dedicated component waves (<= 4 frames per CU)
+    const int* chain_meta;       // ragged chains: as FitArgs::chain_meta
+    int comp_waves;             // set by launch_fit_tree: 4 = the mixture runs on four dedicated component waves (<= 4 frames per CU)
     int debug_shape;             // 0 = chosen by the batch size; 1 = force the plain shape, 2 = force the component-wave shape (tests)
 };
 hipError_t launch_fit_tree(const FitTreeArgs& a, hipStream_t stream);
+
+// Batched shape pre-pass (k2b_shape.hip, k2b_shape_pass_lbfgs): S sequences, sequence s owns frames seq_off[s] .. seq_off[s + 1].
+struct ShapePassArgs {
+    int S, D, NB, nb;              // sequences, body-pose width, shape coefficients of the model, betas optimised (the first nb)
+    const int* seq_off;            // dev [S + 1]
+    const float *jt0, *jd0;        // dev: J_template[root] [3], J_dirs[root] [3][NB]
+    const float* root_y;           // dev [sum n][3]: target root of every frame
+    const float* be_state;         // dev [S][NB]: the optimiser's points (betas in front)
+    float *be_f, *tr_f;            // dev [sum n][NB], [sum n][3]: per-frame shape rows and root-aligned translations
+    const float *grad_f, *loss_f;  // dev [sum n][3 + D + NB + 3], [sum n]: the evaluate-only launch's results
+    float *grad_state, *loss_state; // dev [S][3 + D + NB + 3], [S]: what the L-BFGS step consumes
+};
+hipError_t launch_shape_prep(const ShapePassArgs& a, hipStream_t stream);
+hipError_t launch_shape_reduce(const ShapePassArgs& a, hipStream_t stream);
 
 // LBS operands are f16 hi/lo pairs in MFMA fragment order: [k-step][row][16 halfs].
 constexpr float kPdScale = 256.0f;   // power-of-two scale of the vertex-GEMM B operand (keeps f16 lo terms normal)

@@ -28,7 +28,8 @@ EXPORTED_SYMBOLS = (
     "k2b_model_joint_basis", "k2b_model_reserve", "k2b_debug_read_dump", "k2b_prior_create", "k2b_prior_destroy", "k2b_fit_config_default", "k2b_fit_config_size",
     "k2b_fit_world", "k2b_fit_sequence", "k2b_lbs", "k2b_vertex_term", "k2b_adam_step", "k2b_angular_error_deg",
     "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs", "k2b_model_set_landmarks", "k2b_model_num_landmarks", "k2b_surface_term",
-    "k2b_ikgat_create", "k2b_ikgat_destroy", "k2b_ikgat_predict",
+    "k2b_ikgat_create", "k2b_ikgat_destroy", "k2b_ikgat_predict", "k2b_fit_sequences", "k2b_fit_sequences_lbfgs",
+    "k2b_sequence_order", "k2b_shape_pass_lbfgs",
 )
 
 
@@ -112,6 +113,18 @@ def load_library():
     lib.k2b_fit_sequence_lbfgs.restype = C.c_int
     lib.k2b_fit_sequence_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, C.c_int32, ip] + [fp] * 11 +
                                            [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
+    lib.k2b_fit_sequences.restype = C.c_int
+    lib.k2b_fit_sequences.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, ip, C.c_int32, C.c_int32, ip] + [fp] * 11 +
+                                      [vp])
+    lib.k2b_fit_sequences_lbfgs.restype = C.c_int
+    lib.k2b_fit_sequences_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, ip, C.c_int32, ip] + [fp] * 11 +
+                                            [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
+    lib.k2b_sequence_order.restype = C.c_int
+    lib.k2b_sequence_order.argtypes = [C.c_int32, ip, ip, ip, C.POINTER(C.c_int32)]
+    lib.k2b_shape_pass_lbfgs.restype = C.c_int
+    lib.k2b_shape_pass_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, C.c_int32, C.c_int32, ip] + [fp] * 5 +
+                                         [C.c_int32, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                          vp])
     lib.k2b_vertex_term.restype = C.c_int
     lib.k2b_vertex_term.argtypes = [vp, C.c_int32, C.c_int32, ip, fp, fp, C.c_float, C.c_float] + [fp] * 6 + [vp]
     lib.k2b_model_set_landmarks.restype = C.c_int
@@ -464,6 +477,130 @@ def fit_sequence(model: NativeModel, prior: NativePrior, cfg: FitConfigC, follow
             C.c_void_p(out["global_orient"].data_ptr()), C.c_void_p(out["body_pose"].data_ptr()),
             C.c_void_p(out["betas"].data_ptr()), C.c_void_p(out["transl"].data_ptr()),
             C.c_void_p(out["loss"].data_ptr()), stream), "k2b_fit_sequence")
+    return out
+
+
+def ragged_offsets(lengths) -> np.ndarray:
+    """Exclusive prefix sums of per-sequence frame counts (int32): sequence s owns packed rows offsets[s] .. + lengths[s]."""
+    L = _host_i32(np.asarray(lengths).reshape(-1))
+    out = np.zeros(L.shape, dtype=np.int32)
+    if L.size > 1:
+        out[1:] = np.cumsum(L[:-1], dtype=np.int64).astype(np.int32)
+    return out
+
+
+def _sequences_out(model: NativeModel, N: int):
+    dev = model.device
+    D = 3 * (model.num_joints - 1)
+    return {
+        "global_orient": torch.empty((N, 3), dtype=torch.float32, device=dev),
+        "body_pose": torch.empty((N, D), dtype=torch.float32, device=dev),
+        "betas": torch.empty((N, model.num_betas), dtype=torch.float32, device=dev),
+        "transl": torch.empty((N, 3), dtype=torch.float32, device=dev),
+        "loss": torch.empty((N,), dtype=torch.float32, device=dev),
+    }
+
+
+def _sequences_args(model: NativeModel, cfg: FitConfigC, model_joint_index, lengths, offsets, j3d, conf, global_orient,
+                    body_pose, betas, transl):
+    """Shared argument handling of the ragged entries: host int32 lengths / offsets, the packed device buffers checked."""
+    dev = model.device
+    L = _host_i32(np.asarray(lengths).reshape(-1))
+    O = ragged_offsets(L) if offsets is None else _host_i32(np.asarray(offsets).reshape(-1))
+    S, N, K = int(L.shape[0]), int(j3d.shape[0]), int(j3d.shape[1])
+    D = 3 * (model.num_joints - 1)
+    idx = _host_i32(np.asarray(list(model_joint_index)))
+    if idx.shape != (K,):
+        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
+    if O.shape != (S,):
+        raise ValueError(f"offsets has {O.shape[0]} entries for {S} sequences")
+    if S and int(L.astype(np.int64).sum()) != N and (L >= 0).all():
+        raise ValueError(f"lengths sum to {int(L.astype(np.int64).sum())}, j3d has {N} frames")
+    conf_p = None if conf is None else _dev(conf, "conf", dev, (N, K) if cfg.conf_per_frame else (K,))
+    ins = (_dev(j3d, "j3d", dev, (N, K, 3)), conf_p,
+           _dev(global_orient, "global_orient", dev, (S, 3)), _dev(body_pose, "body_pose", dev, (S, D)),
+           _dev(betas, "betas", dev, (S, model.num_betas)), _dev(transl, "transl", dev, (S, 3)))
+    return L, O, S, N, K, idx, ins
+
+
+def fit_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int,
+                  model_joint_index: Sequence[int], lengths, j3d: torch.Tensor, conf: Optional[torch.Tensor],
+                  global_orient: torch.Tensor, body_pose: torch.Tensor, betas: torch.Tensor, transl: torch.Tensor, offsets=None):
+    """Warm-start chains of different lengths side by side, Adam branch (``k2b_fit_sequences``, ONE launch): ``j3d`` packed
+    (sum T, K, 3), ``lengths`` (S,), start parameters (S, ...) of every sequence's first frame; returns packed (sum T, ...)
+    tensors in the caller's order.  Sequence s equals ``fit_sequence`` on it alone, bit for bit."""
+    L, O, S, N, K, idx, ins = _sequences_args(model, cfg, model_joint_index, lengths, offsets, j3d, conf, global_orient,
+                                              body_pose, betas, transl)
+    out = _sequences_out(model, N)
+    dev = model.device
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(load_library().k2b_fit_sequences(
+            model.handle, prior.handle, C.byref(cfg), S, _np_ptr(L), _np_ptr(O), int(followup_iters), K, _np_ptr(idx), *ins,
+            *[C.c_void_p(out[k].data_ptr()) for k in ("global_orient", "body_pose", "betas", "transl", "loss")], stream),
+            "k2b_fit_sequences")
+    return out
+
+
+def fit_sequences_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, first_iters: int, followup_iters: int,
+                        model_joint_index: Sequence[int], lengths, j3d: torch.Tensor, conf: Optional[torch.Tensor],
+                        global_orient: torch.Tensor, body_pose: torch.Tensor, betas: torch.Tensor, transl: torch.Tensor, *,
+                        lr: float, history_size: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9,
+                        offsets=None):
+    """The default sequence mode (L-BFGS, warm start) for S sequences of different lengths (``k2b_fit_sequences_lbfgs``, ONE
+    launch; ``NotImplementedError`` where it does not apply: SMPL-H / SMPL-X, surface targets).  Arguments and result as
+    ``fit_sequences``; sequence s equals ``fit_sequence_lbfgs`` on it alone, bit for bit."""
+    L, O, S, N, K, idx, ins = _sequences_args(model, cfg, model_joint_index, lengths, offsets, j3d, conf, global_orient,
+                                              body_pose, betas, transl)
+    out = _sequences_out(model, N)
+    dev = model.device
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(load_library().k2b_fit_sequences_lbfgs(
+            model.handle, prior.handle, C.byref(cfg), S, _np_ptr(L), _np_ptr(O), K, _np_ptr(idx), *ins,
+            *[C.c_void_p(out[k].data_ptr()) for k in ("global_orient", "body_pose", "betas", "transl", "loss")],
+            int(first_iters), int(followup_iters), int(history_size), float(lr), float(tolerance_grad), float(tolerance_change),
+            stream), "k2b_fit_sequences_lbfgs")
+    return out
+
+
+def sequence_order(lengths, offsets=None) -> np.ndarray:
+    """The chain-slot order of ``k2b_fit_sequences*`` (``k2b_sequence_order``, host only): the sequences with frames, longest
+    first, ties in the caller's order."""
+    L = _host_i32(np.asarray(lengths).reshape(-1))
+    O = ragged_offsets(L) if offsets is None else _host_i32(np.asarray(offsets).reshape(-1))
+    order = np.zeros(max(int(L.shape[0]), 1), dtype=np.int32)
+    n = C.c_int32(0)
+    _check(load_library().k2b_sequence_order(int(L.shape[0]), _np_ptr(L), _np_ptr(O), _np_ptr(order), C.byref(n)),
+           "k2b_sequence_order")
+    return order[: n.value].copy()
+
+
+def shape_pass_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, seq_offsets: torch.Tensor,
+                     model_joint_index: Sequence[int], j3d: torch.Tensor, conf: Optional[torch.Tensor], global_orient: torch.Tensor,
+                     body_pose: torch.Tensor, root_targets: torch.Tensor, root_joint: int, betas: torch.Tensor, *, max_iter: int,
+                     lr: float, history_size: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9):
+    """The batched shape pre-pass (``k2b_shape_pass_lbfgs``): ``seq_offsets`` device int32 (S + 1,), per-frame targets (N, K, 3),
+    confidences (N, K), pose (N, 3) / (N, D), target roots (N, 3); ``betas`` (S, nb) start; returns the fitted (S, nb)."""
+    dev = model.device
+    N, K = int(j3d.shape[0]), int(j3d.shape[1])
+    S, nb = int(betas.shape[0]), int(betas.shape[1])
+    D = 3 * (model.num_joints - 1)
+    idx = _host_i32(np.asarray(list(model_joint_index)))
+    if idx.shape != (K,):
+        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
+    if not isinstance(seq_offsets, torch.Tensor) or seq_offsets.dtype != torch.int32 or seq_offsets.device != dev \
+            or tuple(seq_offsets.shape) != (S + 1,) or not seq_offsets.is_contiguous():
+        raise ValueError("seq_offsets must be a contiguous int32 device tensor of S + 1 entries")
+    out = torch.empty((S, nb), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(load_library().k2b_shape_pass_lbfgs(
+            model.handle, prior.handle, C.byref(cfg), S, C.c_void_p(seq_offsets.data_ptr()), N, K, _np_ptr(idx),
+            _dev(j3d, "j3d", dev, (N, K, 3)), _dev(conf, "conf", dev, (N, K)), _dev(global_orient, "global_orient", dev, (N, 3)),
+            _dev(body_pose, "body_pose", dev, (N, D)), _dev(root_targets, "root_targets", dev, (N, 3)), int(root_joint), nb,
+            _dev(betas, "betas", dev, (S, nb)), C.c_void_p(out.data_ptr()), int(max_iter), int(history_size), float(lr),
+            float(tolerance_grad), float(tolerance_change), stream), "k2b_shape_pass_lbfgs")
     return out
 
 
