@@ -392,6 +392,9 @@ int k2b_angular_error_deg(int64_t n, const float *pred_rotvec, const float *gt_r
  * k2b_ikgat_create: HOST pointers, copied.
  *   parents [J]: parent of each joint, negative = none; edges run both ways between a joint and its
  *     parent; with no parent >= 0 at all the graph is the chain i <-> i+1 (gan_regressor.py:16-36).
+ *     Self loops are removed and one is added per joint (PyG GATConv), so a joint that is its own parent keeps one.
+ *     J == 1 is accepted although the reference cannot run it (its edge tensor is malformed there): the graph
+ *     is the self loop only, so every attention weight is 1 and the joint sees its own features.
  *   weights [num_weights] float32: the state dict's tensors, row-major, concatenated in this order
  *   (H = hidden_dim, H2 = H / 2, IN = input_dim):
  *     input_proj.weight [H][IN], input_proj.bias [H], joint_pos_embed.weight [J][H],

@@ -5,8 +5,8 @@ demo motion (``data/demo/test_motion1.npy``), so its own config checks, checkpoi
 (``GATRotationRegressor``), pre- and post-processing and result objects produce the numbers.  Three third-party modules are
 not installed here and are put into ``sys.modules`` before the reference is imported:
 
-* ``torch_geometric.nn`` provides ``GATConv``, RESTATED below from PyG's published formulation (eval mode, concat, self
-  loops re-added, negative slope 0.2, no edge features).  PARITY UNPINNED at that boundary;
+* ``torch_geometric.nn`` provides ``GATConv``, RESTATED in ``oracle/ikgat_torch.py`` from PyG's published formulation (eval
+  mode, concat, self loops re-added, negative slope 0.2, no edge features).  PARITY UNPINNED at that boundary;
 * ``smplx`` and ``h5py`` are empty stubs: the IK-GAT path loads neither a body model nor the mean-parameter file.
 
 No trained weights ship with the reference: ``synthetic.make_ikgat_state`` makes seeded ones, written to a temporary
@@ -21,10 +21,12 @@ weights, never the checkpoint.  Cases (``tests/golden/ikgat_<name>.npz``):
                   joints 22 and 23 extend the demo's wrists);
 * ``chainedges``  pos_to_rot6 with every parent -1 (the chain-edge graph), H 32 / 1 layer / 2 heads.
 
-Prints the reference's per-frame CPU time at B = 1.   Usage:  python tools/gen_golden_ikgat.py
+Prints the reference's per-frame CPU time at B = 1.   Usage:  python tools/gen_golden_ikgat.py [--out DIR]
+(``--out``: write there instead of ``tests/golden``, to compare a regeneration with the committed files).
 """
 from __future__ import annotations
 
+import argparse
 import os
 import sys
 import tempfile
@@ -34,49 +36,16 @@ from pathlib import Path
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
 from keypoints2body_amd import synthetic  # noqa: E402
 from oracle.gen_golden import GOLDEN, REF_ROOT, import_reference  # noqa: E402
+from oracle.ikgat_torch import GATConv  # noqa: E402
 
 LIMIT = 96
 FMT = "smplx"
-
-
-class GATConv(nn.Module):
-    """PyG ``GATConv`` restated (eval mode): x' = x W^T; a_src / a_dst = <x'_h, att_h>; self loops removed then one added
-    per node; e_ji = LeakyReLU_0.2(a_src[j] + a_dst[i]); softmax over the edges entering i with PyG's
-    exp(e - max) / (sum + 1e-16); out_i = sum_j alpha_ji x'_j, heads concatenated, + bias."""
-
-    def __init__(self, in_channels, out_channels, heads=1, dropout=0.0, concat=True, negative_slope=0.2):
-        super().__init__()
-        assert concat
-        self.heads, self.out_channels, self.negative_slope = heads, out_channels, negative_slope
-        self.lin = nn.Linear(in_channels, heads * out_channels, bias=False)
-        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
-        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
-        self.bias = nn.Parameter(torch.empty(heads * out_channels))
-
-    def forward(self, x, edge_index):
-        N, Hh, C = x.shape[0], self.heads, self.out_channels
-        xp = self.lin(x).view(N, Hh, C)
-        a_src = (xp * self.att_src).sum(-1)
-        a_dst = (xp * self.att_dst).sum(-1)
-        src, dst = edge_index
-        keep = src != dst
-        loops = torch.arange(N, device=x.device)
-        src = torch.cat([src[keep], loops])
-        dst = torch.cat([dst[keep], loops])
-        e = torch.nn.functional.leaky_relu(a_src[src] + a_dst[dst], self.negative_slope)
-        emax = torch.full((N, Hh), -float("inf"), dtype=e.dtype).scatter_reduce(0, dst[:, None].expand(-1, Hh), e, "amax")
-        ex = (e - emax[dst]).exp()
-        den = torch.zeros((N, Hh), dtype=e.dtype).index_add(0, dst, ex) + 1e-16
-        alpha = ex / den[dst]
-        out = torch.zeros((N, Hh, C), dtype=x.dtype).index_add(0, dst, alpha[..., None] * xp[src])
-        return out.reshape(N, Hh * C) + self.bias
 
 
 def install_stubs():
@@ -102,6 +71,10 @@ def unit_quats(n: int, seed: int) -> np.ndarray:
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", type=Path, default=GOLDEN)
+    out_dir = ap.parse_args().out.resolve()
+    out_dir.mkdir(parents=True, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
     install_stubs()
@@ -147,8 +120,8 @@ def main():
                       weights_checksum=np.array(synthetic.checksum(*state.values()), dtype=np.uint64), **extra)
         if q0 is not None:
             arrays["init_quaternions"] = q0
-        np.savez_compressed(GOLDEN / f"ikgat_{name}.npz", **arrays)
-        print(f"[ikgat] {name}: {out.shape[0]} frames, min qw {qw.min():.3f}, file {(GOLDEN / f'ikgat_{name}.npz').stat().st_size} B")
+        np.savez_compressed(out_dir / f"ikgat_{name}.npz", **arrays)
+        print(f"[ikgat] {name}: {out.shape[0]} frames, min qw {qw.min():.3f}, file {(out_dir / f'ikgat_{name}.npz').stat().st_size} B")
 
     q22 = unit_quats(22, seed=1)
     st, out, dt = run_seq(motion, "pos_to_rot6", parents22, 128, 3, 4, 0, True)
