@@ -1,0 +1,356 @@
+// k2b_api_lbfgs.hip — the L-BFGS entries of the C ABI (include/k2b.h): the optimiser's workspace, one device-driven fit
+// (lbfgs_run), the entries for frames, a warm-start sequence and ragged sequences, and the shape pre-pass.  The closure is
+// the evaluate-only fit launch of k2b_api_fit.hip, the optimiser k2b_lbfgs.hip's state machine; only launches are queued.
+#include <cstdlib>
+
+#include "k2b_host.h"
+
+using namespace k2b::host;
+
+namespace {
+
+// development switch K2B_LBFGS_SCHEME: 1 forces two launches per round, 2 the fused rounds wherever they apply, any other
+// value but 0 keeps a sequence out of the one-launch chain (tools/dev_lbfgs_schemes.py)
+int lbfgs_scheme() {
+    static const int scheme = [] { const char* e = getenv("K2B_LBFGS_SCHEME"); return e ? atoi(e) : 0; }();
+    return scheme;
+}
+
+// Workspace of the optimiser: its state, then two closure-result buffers (the fused rounds alternate).
+struct LbfgsWs { unsigned char* base; size_t off_si, off_sv, n_state, n_res; float *gbuf, *lbuf, *gbuf2, *lbuf2; bool state_cleared; };   // (state_cleared: the caller did)
+size_t lbfgs_ws_layout(int B, int P, int H, LbfgsWs* w) {
+    w->n_state = (k2b::lbfgs_state_bytes(B, P, H, &w->off_si, &w->off_sv) + 15) / 16 * 16;
+    w->n_res = (2 * ((size_t)B * P + B) * sizeof(float) + 15) / 16 * 16;
+    return w->n_state + w->n_res;
+}
+// pointers into the workspace laid out above; returns the first byte behind it (the caller's own scratch)
+float* lbfgs_ws_assign(LbfgsWs* w, unsigned char* ws, int B, int P) {
+    w->base = ws;
+    w->gbuf = reinterpret_cast<float*>(ws + w->n_state);
+    w->lbuf = w->gbuf + (size_t)B * P;
+    w->gbuf2 = w->lbuf + B;
+    w->lbuf2 = w->gbuf2 + (size_t)B * P;
+    return reinterpret_cast<float*>(ws + w->n_state + w->n_res);
+}
+
+struct LbfgsOpts {
+    int max_iter, history;                   // (history: already cut to what a fit of max_iter iterations can fill)
+    double lr, tol_g, tol_c;
+};
+// B optimiser instances over the points `p`, reading closure result buffer A of `w`
+k2b::LbfgsArgs make_lbfgs_args(int B, const k2b_model* model, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
+    const int NB = model->NB, D = 3 * (model->J - 1);
+    k2b::LbfgsArgs la{};
+    la.B = B; la.P = 3 + D + NB + 3; la.D = D; la.NB = NB; la.H = o.history;
+    la.max_iter = o.max_iter; la.max_eval = o.max_iter * 5 / 4;          // torch's default
+    la.lr = o.lr; la.tol_g = o.tol_g; la.tol_c = o.tol_c;
+    la.go = p.go; la.bp = p.bp; la.be = p.be; la.tr = p.tr;
+    la.loss_in = w.lbuf; la.grad_in = w.gbuf;
+    la.sd = reinterpret_cast<double*>(w.base); la.si = reinterpret_cast<int*>(w.base + w.off_si); la.sv = reinterpret_cast<float*>(w.base + w.off_sv);
+    return la;
+}
+
+// One device-driven L-BFGS fit of the frames of `at`, whose start is ALREADY in the parameter arrays at.out (in place): state
+// cleared, max_eval + 2 rounds of [closure, step], finalise, loss (+ gradient) at the result.  `w` = lbfgs_ws_layout() of
+// stream-ordered scratch, at.preserve / at.tr_prior = preserve pose / translation prior centre (device, outside the arrays).
+int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& at, const LbfgsOpts& o,
+              LbfgsWs& w) {
+    hipStream_t stream = at.stream;
+    const int B = at.B;
+    if (!w.state_cleared) HIP_TRY(hipMemsetAsync(w.base, 0, w.off_sv, stream));   // scalars and integers: phase INIT (vectors are written before they are read)
+    w.state_cleared = false;
+    k2b_fit_config ec = *cfg;
+    ec.num_iters = 1;
+    ec.step_size = 0.0;                                                  // evaluate-only: the closure
+    FitCall ev = at;
+    ev.in = at.out.as_const();
+    auto launch = [&](const k2b_fit_config& c, int mode, const k2b::LbfgsArgs* args, float* loss, float* grad) {
+        ev.lbfgs.mode = mode; ev.lbfgs.args = args;
+        ev.loss_out = loss; ev.grad_out = grad;
+        return fit_world_impl(model, prior, &c, ev);
+    };
+    auto closure = [&](float* loss, float* grad) { return launch(ec, 0, nullptr, loss, grad); };
+    k2b::LbfgsArgs la = make_lbfgs_args(B, model, o, at.out, w);
+    const int rounds = la.max_eval + 2;
+    // One launch per round where the fused kernel takes the frames (24-joint model, the prior over the whole pose, kinematic
+    // targets only, at most four frames per CU): launch r = [step on the result of launch r - 1 | closure]; the last launch =
+    // [finalise | closure] with the caller's outputs.  Two result buffers alternate (a launch reads the one its predecessor
+    // wrote while writing the other).  Otherwise two launches per round.
+    const int frames_per_cu = (B + device_cus() - 1) / device_cus();
+    const bool fused = lbfgs_scheme() != 1 && frames_per_cu <= 4 && fused_eligibility(model, prior, cfg).fused &&
+                       kinematic_only(model, at.K, at.model_joint_index);
+    if (fused) {
+        // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
+        k2b::LbfgsArgs both[2] = {la, la};
+        both[1].loss_in = w.lbuf2; both[1].grad_in = w.gbuf2;
+        if (lbfgs_scheme() != 2 && frames_per_cu <= 2) {
+            // at most two frames per CU: the whole fit is ONE persistent launch - rounds closures, each followed by its step on an
+            // idle wave of the workgroup, the finalise pass and the closure at the result (k2b_fit.hip, lb_mode 3)
+            k2b_fit_config pc = ec;
+            pc.num_iters = rounds + 1;
+            return launch(pc, 3, &both[0], at.loss_out ? at.loss_out : w.lbuf2, at.grad_out);
+        }
+        // launch 0: closure only, writes A; launch r >= 1 reads (r - 1) & 1 and writes r & 1
+        if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
+        for (int r = 1; r <= rounds; ++r) {
+            const int rd = (r - 1) & 1, wr = r & 1;
+            if (const int rc = launch(ec, 1, &both[rd], wr ? w.lbuf2 : w.lbuf, wr ? w.gbuf2 : w.gbuf); rc != K2B_OK) return rc;
+            // the last step has consumed result r - 1: the finalise launch parks every frame and evaluates the result
+            if (r == rounds) return launch(ec, 2, &both[wr], at.loss_out ? at.loss_out : (rd ? w.lbuf2 : w.lbuf), at.grad_out);
+        }
+    }
+    for (int r = 0; r < rounds; ++r) {
+        if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
+        HIP_TRY(k2b::launch_lbfgs_step(la, stream));
+    }
+    la.finalize = 1;
+    HIP_TRY(k2b::launch_lbfgs_step(la, stream));
+    // loss (and gradient) at the result (world_space.py:245-246 evaluates the loss once more behind the optimiser)
+    return closure(at.loss_out ? at.loss_out : w.lbuf, at.grad_out);
+}
+
+int lbfgs_check(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int max_iter, int* history_size, double lr,
+                const char* who) {
+    if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (max_iter < 1 || max_iter > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: max_iter=%d", who, max_iter);
+    if (*history_size <= 0) *history_size = k2b::kLbfgsMaxHistory;
+    if (*history_size > k2b::kLbfgsMaxHistory)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: history_size=%d (at most %d)", who, *history_size, k2b::kLbfgsMaxHistory);
+    if (!(lr > 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lr must be positive", who);
+    if (3 + 3 * (model->J - 1) + model->NB + 3 > 192)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 192)", who, 3 + 3 * (model->J - 1) + model->NB + 3);
+    return K2B_OK;
+}
+
+// The default sequence mode in ONE launch (k2b_fit.hip: chain + lb_mode 3): the frame loop runs inside the persistent launch -
+// per frame a fresh optimiser on the workgroup's idle wave, the start and the preserve pose from the predecessor's result in
+// registers.  `c` = the chain's call (slots, targets, parameters, chain.len / chain.meta), `la` = the first frame's optimiser.
+int lbfgs_chain_launch(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, FitCall c, const k2b::LbfgsArgs& la,
+                       int followup_iters) {
+    k2b_fit_config pc = *cfg;
+    pc.num_iters = la.max_eval + 3;                                       // rounds + the closure at the result
+    pc.step_size = 0.0;
+    c.chain.iters = followup_iters * 5 / 4 + 3;
+    c.lbfgs.mode = 3; c.lbfgs.args = &la; c.lbfgs.chain_max_iter = followup_iters;
+    return fit_world_impl(model, prior, &pc, c);
+}
+
+}  // namespace
+
+extern "C" {
+
+// L-BFGS branch of the fitters on the device (world_space.py:231-247, camera_space.py:144-182,229-267): per frame
+// torch.optim.LBFGS(max_iter, lr, line_search_fn="strong_wolfe").step(closure), the closure = this library's evaluate-only fit
+// launch, the optimiser = k2b_lbfgs.hip's state machine.  Only launches are queued: max_eval + 2 rounds of [closure, step], then
+// the accepted points go back into the parameter arrays and one more closure launch leaves the final loss (+ gradient).
+int k2b_fit_world_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t B, int32_t K,
+                        const int32_t* model_joint_index, const float* j3d, const float* conf, const float* go_in,
+                        const float* bp_in, const float* be_in, const float* tr_in, const float* preserve, const float* tr_prior,
+                        float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out, float* grad_out,
+                        int32_t max_iter, int32_t history_size, double lr, double tolerance_grad, double tolerance_change,
+                        void* stream_v) {
+    if (const int rc = lbfgs_check(model_c, prior, cfg, max_iter, &history_size, lr, "k2b_fit_world_lbfgs"); rc != K2B_OK) return rc;
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world_lbfgs: num_frames=%d", B);
+    if (B == 0) return K2B_OK;
+    if (!go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world_lbfgs: NULL parameter buffer");
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int NB = model_c->NB, D = 3 * (model_c->J - 1), P = 3 + D + NB + 3;
+    const int H = history_size < max_iter ? history_size : max_iter;      // (a fit makes at most max_iter - 1 pairs)
+    // stream-ordered workspace: optimiser state, closure results, the preserve pose and the translation prior's centre (their
+    // defaults are the INITIAL parameters, which the parameter arrays stop holding after the first step)
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(B, P, H, &w);
+    StreamWorkspace ws(stream);
+    HIP_TRY(ws.alloc(n_opt + ((size_t)B * D + (size_t)B * 3) * sizeof(float)));
+#define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_world_lbfgs: HIP call failed")
+    float *pres = lbfgs_ws_assign(&w, ws.get(), B, P), *trp = pres + (size_t)B * D;
+    TRY_Q(hipMemcpyAsync(pres, preserve ? preserve : bp_in, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    TRY_Q(hipMemcpyAsync(trp, tr_prior ? tr_prior : tr_in, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    const struct { const float* src; float* dst; size_t n; } cp[] = {
+        {go_in, go_out, (size_t)B * 3}, {bp_in, bp_out, (size_t)B * D}, {be_in, be_out, (size_t)B * NB}, {tr_in, tr_out, (size_t)B * 3}};
+    for (const auto& c : cp)
+        if (c.src != c.dst) TRY_Q(hipMemcpyAsync(c.dst, c.src, c.n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+#undef TRY_Q
+    FitCall at = fit_call(B, K, model_joint_index, j3d, conf, stream_v);
+    at.out = {go_out, bp_out, be_out, tr_out};
+    at.preserve = pres; at.loss_out = loss_out; at.grad_out = grad_out;
+    at.tr_prior = (tr_prior || cfg->transl_prior_weight != 0.0f) ? trp : nullptr;   // (the tree kernel has no translation prior)
+    return lbfgs_run(model_c, prior, cfg, at, {max_iter, H, lr, tolerance_grad, tolerance_change}, w);
+}
+
+// The reference's DEFAULT sequence mode in one call: the frame loop of optimize_params_sequence with use_previous_frame_init=True
+// (api/sequence.py:214-281) over the L-BFGS branch (world_space.py:231-247).  Frame 0 is fitted from the given start with
+// first_iters iterations and no preserve term; every later frame starts from its predecessor's RESULT, preserves that result's
+// body pose with cfg->pose_preserve_weight (world_space.py:159,211) and runs followup_iters iterations; each frame is one
+// device-driven L-BFGS fit (k2b_fit_world_lbfgs) and only launches are queued - no host work between the frames.
+int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t T, int32_t K,
+                           const int32_t* model_joint_index, const float* j3d, const float* conf, const float* go_in,
+                           const float* bp_in, const float* be_in, const float* tr_in, float* go_out, float* bp_out, float* be_out,
+                           float* tr_out, float* loss_out, int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr,
+                           double tolerance_grad, double tolerance_change, void* stream_v) {
+    if (const int rc = lbfgs_check(model_c, prior, cfg, first_iters, &history_size, lr, "k2b_fit_sequence_lbfgs"); rc != K2B_OK) return rc;
+    if (followup_iters < 1 || followup_iters > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: followup_iters=%d", followup_iters);
+    if (T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: frames=%d", T);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence_lbfgs: no translation prior in a chain");
+    if (T == 0) return K2B_OK;
+    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: NULL parameter / target buffer");
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int NB = model_c->NB, D = 3 * (model_c->J - 1), P = 3 + D + NB + 3;
+    const int it_max = first_iters > followup_iters ? first_iters : followup_iters;
+    const int Hmax = history_size < it_max ? history_size : it_max;
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(1, P, Hmax, &w);
+    StreamWorkspace ws(stream);
+    HIP_TRY(ws.alloc(n_opt + (size_t)D * sizeof(float)));
+#define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_sequence_lbfgs: HIP call failed")
+    float* pres = lbfgs_ws_assign(&w, ws.get(), 1, P);
+    // the whole sequence in ONE launch where the fused kernel takes it (24-joint model, the prior over the whole pose, kinematic targets)
+    if (lbfgs_scheme() == 0 && T > 1 && fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)) {
+        FitCall c = fit_call(1, K, model_joint_index, j3d, conf, stream_v);
+        c.in = {go_in, bp_in, be_in, tr_in};
+        c.out = {go_out, bp_out, be_out, tr_out};                             // rows t of the outputs: frame t's point
+        c.loss_out = loss_out; c.chain.len = T;
+        const k2b::LbfgsArgs la = make_lbfgs_args(1, model_c, {first_iters, Hmax, lr, tolerance_grad, tolerance_change}, c.out, w);
+        TRY_Q(hipMemsetAsync(w.base, 0, w.off_sv, stream));
+        return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
+    }
+    k2b_fit_config fc = *cfg;
+    fc.conf_per_frame = 0;                                        // (one frame per fit: its row of a per-frame array is a shared row)
+    for (int t = 0; t < T; ++t) {
+        float *go = go_out + (size_t)t * 3, *bp = bp_out + (size_t)t * D, *be = be_out + (size_t)t * NB, *tr = tr_out + (size_t)t * 3;
+        const float *sgo = t ? go - 3 : go_in, *sbp = t ? bp - D : bp_in, *sbe = t ? be - NB : be_in, *str = t ? tr - 3 : tr_in;
+        // start of this frame = the start given (frame 0) or the previous frame's result; its body pose is also what is preserved
+        // (one small launch: the four parameter rows, the preserve pose and the cleared optimiser state)
+        TRY_Q(k2b::launch_lbfgs_frame_prep(go, sgo, bp, sbp, be, sbe, tr, str, pres, D, NB, w.base, w.off_sv, stream));
+        w.state_cleared = true;
+        fc.pose_preserve_weight = t ? cfg->pose_preserve_weight : 0.0f;
+        const int iters = t ? followup_iters : first_iters;
+        const int H = history_size < iters ? history_size : iters;
+        FitCall at = fit_call(1, K, model_joint_index, j3d + (size_t)t * K * 3,
+                              conf ? conf + (cfg->conf_per_frame ? (size_t)t * K : 0) : nullptr, stream_v);
+        at.out = {go, bp, be, tr}; at.preserve = pres; at.loss_out = loss_out ? loss_out + t : nullptr;
+        if (const int rc = lbfgs_run(model_c, prior, &fc, at, {iters, H, lr, tolerance_grad, tolerance_change}, w); rc != K2B_OK) return rc;
+    }
+#undef TRY_Q
+    return K2B_OK;
+}
+
+// The default sequence mode (L-BFGS, warm start) for many sequences of different lengths: k2b_fit_sequence_lbfgs's persistent
+// chain with one optimiser per sequence, ONE launch (24-joint model, the prior over the whole pose, kinematic targets; other
+// configurations: K2B_ERR_UNSUPPORTED, the caller fits sequence by sequence).
+int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                            const int32_t* lengths, const int32_t* offsets, int32_t K, const int32_t* model_joint_index,
+                            const float* j3d, const float* conf, const float* go_in, const float* bp_in, const float* be_in,
+                            const float* tr_in, float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out,
+                            int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr, double tolerance_grad,
+                            double tolerance_change, void* stream_v) {
+    const char* who = "k2b_fit_sequences_lbfgs";
+    RaggedSlots r;
+    if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
+    if (const int rc = lbfgs_check(model_c, prior, cfg, first_iters, &history_size, lr, who); rc != K2B_OK) return rc;
+    if (followup_iters < 1 || followup_iters > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
+    if (const int rc = check_targets(who, model_c, K, model_joint_index); rc != K2B_OK) return rc;
+    if (r.slots == 0) return K2B_OK;
+    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    if (!(fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)))
+        return fail(K2B_ERR_UNSUPPORTED, "%s: one launch needs the 24-joint model, the prior over the whole pose and kinematic targets", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int P = 3 + 3 * (model_c->J - 1) + model_c->NB + 3;
+    const int it_max = first_iters > followup_iters ? first_iters : followup_iters;
+    const int Hmax = history_size < it_max ? history_size : it_max;
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(r.slots, P, Hmax, &w);
+    const size_t n_meta = (r.meta.size() * sizeof(int) + 15) / 16 * 16;
+    StreamWorkspace ws(stream);
+    HIP_TRY(ws.alloc(n_meta + n_opt));
+    int* meta = reinterpret_cast<int*>(ws.get());
+    if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) return rc;
+    HIP_TRY_MSG(hipMemsetAsync(ws.get() + n_meta, 0, w.off_sv, stream), "%s: HIP call failed", who);
+    (void)lbfgs_ws_assign(&w, ws.get() + n_meta, r.slots, P);
+    // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: lb_mode 3)
+    FitCall c = fit_call(r.slots, K, model_joint_index, j3d, conf, stream_v);
+    c.in = {go_in, bp_in, be_in, tr_in};
+    c.out = {go_out, bp_out, be_out, tr_out};                                 // frame rows of the outputs: each frame's point
+    c.loss_out = loss_out; c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.meta = meta;
+    const k2b::LbfgsArgs la = make_lbfgs_args(r.slots, model_c, {first_iters, Hmax, lr, tolerance_grad, tolerance_change}, c.out, w);
+    return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
+}
+
+// The shape pre-pass of S sequences together (reference core/shape.py:10-115, one torch.optim.LBFGS over betas per sequence):
+// per round [prep (k2b_shape.hip: shape rows, root-aligned translations) -> ONE evaluate-only fused launch over all frames ->
+// reduce (per-sequence loss and gradient in frame order) -> the L-BFGS state machine, one instance per sequence]; max_eval + 2
+// rounds and the finalise step are queued on `stream`, nothing comes back to the host.
+int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                         const int32_t* seq_offsets, int32_t num_frames, int32_t K, const int32_t* model_joint_index,
+                         const float* j3d, const float* conf, const float* global_orient, const float* body_pose,
+                         const float* root_targets, int32_t root_joint, int32_t num_free_betas, const float* betas_in,
+                         float* betas_out, int32_t max_iter, int32_t history_size, double lr, double tolerance_grad,
+                         double tolerance_change, void* stream_v) {
+    const char* who = "k2b_shape_pass_lbfgs";
+    if (const int rc = lbfgs_check(model_c, prior, cfg, max_iter, &history_size, lr, who); rc != K2B_OK) return rc;
+    if (num_sequences < 0 || num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: %d sequences, %d frames", who, num_sequences, num_frames);
+    const int J = model_c->J, NB = model_c->NB, D = 3 * (J - 1), P = 3 + D + NB + 3;
+    if (root_joint < 0 || root_joint >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: root_joint=%d", who, root_joint);
+    if (num_free_betas < 1 || num_free_betas > NB || num_free_betas > 32)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_free_betas=%d (1..min(%d, 32))", who, num_free_betas, NB);
+    if (K < 1 || !model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_targets=%d / model_joint_index", who, K);
+    for (int k = 0; k < K; ++k)
+        if (model_joint_index[k] < 0 || model_joint_index[k] >= J)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model_joint_index[%d]=%d (kinematic joints only)", who, k, model_joint_index[k]);
+    if (num_sequences == 0) return K2B_OK;
+    if (!seq_offsets || !betas_in || !betas_out || (num_frames > 0 && (!j3d || !global_orient || !body_pose || !root_targets)))
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL buffer", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int S = num_sequences, N = num_frames, nb = num_free_betas;
+    const int H = history_size < max_iter ? history_size : max_iter;
+    LbfgsWs w{};
+    const size_t n_opt = lbfgs_ws_layout(S, P, H, &w);
+    // behind the optimiser's workspace: its parameter arrays [S][...], then the per-frame closure buffers [N][...]
+    const size_t n_par = (size_t)S * P, n_frm = (size_t)N * (NB + 3 + 3 + D + NB + 3 + 1 + P);
+    StreamWorkspace ws(stream);
+    HIP_TRY(ws.alloc(n_opt + (n_par + n_frm) * sizeof(float)));
+#define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_shape_pass_lbfgs: HIP call failed")
+    float* go_s = lbfgs_ws_assign(&w, ws.get(), S, P);
+    float *bp_s = go_s + (size_t)S * 3, *be_s = bp_s + (size_t)S * D, *tr_s = be_s + (size_t)S * NB;
+    float *be_f = tr_s + (size_t)S * 3, *tr_f = be_f + (size_t)N * NB;
+    float *go_o = tr_f + (size_t)N * 3, *bp_o = go_o + (size_t)N * 3, *be_o = bp_o + (size_t)N * D, *tr_o = be_o + (size_t)N * NB;
+    float *loss_f = tr_o + (size_t)N * 3, *grad_f = loss_f + N;
+    TRY_Q(hipMemsetAsync(w.base, 0, w.off_sv, stream));                                   // every instance in phase INIT
+    TRY_Q(hipMemsetAsync(go_s, 0, n_par * sizeof(float), stream));                        // pose / transl of the points: 0, never move
+    TRY_Q(hipMemcpy2DAsync(be_s, (size_t)NB * sizeof(float), betas_in, (size_t)nb * sizeof(float), (size_t)nb * sizeof(float), S,
+                           hipMemcpyDeviceToDevice, stream));
+    k2b::ShapePassArgs sa{};
+    sa.S = S; sa.D = D; sa.NB = NB; sa.nb = nb; sa.seq_off = seq_offsets;
+    sa.jt0 = model_c->j_template.get() + (size_t)root_joint * 3; sa.jd0 = model_c->j_dirs.get() + (size_t)root_joint * 3 * NB;
+    sa.root_y = root_targets; sa.be_state = be_s; sa.be_f = be_f; sa.tr_f = tr_f; sa.grad_f = grad_f; sa.loss_f = loss_f;
+    sa.grad_state = w.gbuf; sa.loss_state = w.lbuf;
+    k2b_fit_config ec = *cfg;
+    ec.num_iters = 1;
+    ec.step_size = 0.0;                                                                  // evaluate-only: the closure
+    ec.conf_per_frame = conf ? 1 : 0;
+    FitCall ev = fit_call(N, K, model_joint_index, j3d, conf, stream_v);
+    ev.in = {global_orient, body_pose, be_f, tr_f};
+    ev.out = {go_o, bp_o, be_o, tr_o};
+    ev.loss_out = loss_f; ev.grad_out = grad_f;
+    k2b::LbfgsArgs la = make_lbfgs_args(S, model_c, {max_iter, H, lr, tolerance_grad, tolerance_change}, {go_s, bp_s, be_s, tr_s}, w);
+    const int rounds = la.max_eval + 2;
+    for (int r = 0; r < rounds; ++r) {
+        TRY_Q(k2b::launch_shape_prep(sa, stream));
+        if (N > 0)
+            if (const int rc = fit_world_impl(model_c, prior, &ec, ev); rc != K2B_OK) return rc;
+        TRY_Q(k2b::launch_shape_reduce(sa, stream));
+        TRY_Q(k2b::launch_lbfgs_step(la, stream));
+    }
+    la.finalize = 1;
+    TRY_Q(k2b::launch_lbfgs_step(la, stream));                                            // the accepted points
+    TRY_Q(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), be_s, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
+                           hipMemcpyDeviceToDevice, stream));
+#undef TRY_Q
+    return K2B_OK;
+}
+
+}  // extern "C"

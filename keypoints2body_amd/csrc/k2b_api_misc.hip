@@ -1,0 +1,337 @@
+// k2b_api_misc.hip — the entries of the C ABI (include/k2b.h) that are one launch or none: version, the calling thread's
+// error message, config defaults, the LBS forward, the vertex / surface terms, the Adam step, the angular error and the
+// IK-GAT regressor.
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <memory>
+
+#include "k2b_host.h"
+
+using namespace k2b::host;
+
+namespace {
+
+thread_local std::string g_err;
+
+constexpr size_t kIkgatBatchLds = 80 * 1024;     // two workgroups per CU for batched launches
+constexpr int kIkgatMaxFrames = 16;
+
+int64_t ikgat_num_weights(int J, int IN, int H, int L) {
+    const int64_t h = H, h2 = H / 2;
+    return h * IN + h + (int64_t)J * h + h * IN + h + (int64_t)L * (h * h + 5 * h) + h2 * h + 3 * h2 + 6 * h2 + 6;
+}
+
+}  // namespace
+
+namespace k2b {
+namespace host {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+int device_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
+}  // namespace host
+}  // namespace k2b
+
+extern "C" {
+
+uint32_t k2b_version(void) { return (1u << 16) | 3u; }
+const char* k2b_last_error(void) { return g_err.c_str(); }
+
+uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
+
+void k2b_fit_config_default(k2b_fit_config* c) {
+    if (!c) return;
+    c->num_iters = 30;           // FrameOptimizeConfig.num_iters_first (core/config.py:32)
+    c->step_size = 1e-2;
+    c->adam_beta1 = 0.9;
+    c->adam_beta2 = 0.999;
+    c->adam_eps = 1e-8;
+    c->sigma = 100.0f;
+    c->joint_loss_weight = 600.0f;
+    c->pose_prior_weight = (float)(4.78 * 1.5);
+    c->angle_prior_weight = 15.2f;
+    c->shape_prior_weight = 5.0f;
+    c->pose_preserve_weight = 0.0f;
+    c->freeze_betas = 0;
+    c->conf_per_frame = 0;
+    const int idx[4] = {52, 55, 9, 12};
+    const float sg[4] = {1.f, -1.f, -1.f, -1.f};
+    for (int i = 0; i < 4; ++i) { c->angle_prior_index[i] = idx[i]; c->angle_prior_sign[i] = sg[i]; }
+    c->optimize_mask = 15;
+    c->transl_prior_weight = 0.0f;
+    c->debug_launch_shape = 0;
+    c->prior_pose_dims = 0;
+    c->num_betas_prior = 0;
+}
+
+int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* bp, const float* be, const float* tr,
+            float* joints_out, float* vertices_out, void* stream_v) {
+    k2b_model* m = const_cast<k2b_model*>(model_c);
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: model is NULL");
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: num_frames=%d", B);
+    if (B == 0) return K2B_OK;
+    if (!go || !bp || !be) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: NULL parameter buffer");
+    if (!joints_out && !vertices_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: no output requested");
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int bpad = k2b::lbs_frames_padded(B);
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        if (const int rc = reserve_lbs_workspace(m, bpad); rc != K2B_OK) return rc;
+    }
+    k2b::PoseArgs pa{};
+    pa.j_basis_lane = m->j_basis_lane.get(); pa.parents = m->parents.get();
+    const int L = m->lmk.L, ostride = m->J + m->E + L;                  // rows of joints_out: J kinematic, E extra vertices, L landmarks
+    pa.num_joints = m->J; pa.num_betas = m->NB; pa.num_out_joints = ostride;
+    pa.num_frames = B; pa.frames_padded = bpad; pa.k_steps_x = m->k_steps_x;
+    pa.go = go; pa.bp = bp; pa.be = be; pa.tr = tr;
+    if (m->groups_a != 3 && m->groups_a != 7)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs: %d joints; the vertex kernel is built for 17-24 (SMPL) and 49-56 (SMPL-H / SMPL-X) joints", m->J);
+    pa.xh = m->wsXh.get(); pa.xl = m->wsXl.get(); pa.a2 = m->wsA2.get(); pa.joints_out = joints_out;
+    pa.a2_stream_order = (m->stream || m->stream_x) ? 1 : 0;
+    HIP_TRY(k2b::launch_pose_setup(pa, stream));
+    auto skin = [&](const VertexSet& vs, float* out, int stride, int row0, float* joint_copies) -> hipError_t {
+        if (m->stream || m->stream_x) {
+            k2b::StreamArgs sa{};
+            sa.xh = pa.xh; sa.xl = pa.xl; sa.a2 = pa.a2; sa.pd = vs.spd.get(); sa.w = vs.sw.get();
+            sa.f32_tiles = bpad / 32; sa.nv16 = vs.nv16;
+            sa.num_frames = B; sa.num_out = vs.num; sa.out = out; sa.out_stride = stride; sa.out_row0 = row0;
+            sa.dump = m->dump.get();
+            sa.joints_out = joint_copies; sa.joints_stride = ostride; sa.joints_row0 = m->J;
+            return m->stream ? k2b::launch_skin_stream(sa, device_cus(), stream) : k2b::launch_skin_stream_x(sa, device_cus(), stream);
+        }
+        k2b::TileArgs ta{};
+        ta.xh = pa.xh; ta.xl = pa.xl; ta.a2 = pa.a2; ta.pdh = vs.pdh.get(); ta.pdl = vs.pdl.get(); ta.w2 = vs.w2.get();
+        ta.groups_a = m->groups_a; ta.k_steps_x = m->k_steps_x; ta.f_tiles = bpad / 32; ta.v_tiles = vs.v_tiles;
+        ta.num_frames = B; ta.num_out = vs.num; ta.out = out; ta.out_stride = stride; ta.out_row0 = row0;
+        ta.dump = m->dump.get();
+        ta.joints_out = joint_copies; ta.joints_stride = ostride; ta.joints_row0 = m->J;
+        return k2b::launch_skin_tiles(ta, device_cus(), stream);
+    };
+    if (vertices_out) {
+        // the mesh launch also writes the vertex-selected joints (their vertices are tagged in the W image)
+        const bool copies = joints_out && m->E > 0 && m->joints_in_mesh;
+        HIP_TRY(skin(m->mesh, vertices_out, m->V, 0, copies ? joints_out : nullptr));
+        if (joints_out && m->E > 0 && !copies)
+            HIP_TRY(k2b::launch_gather_joints(vertices_out, m->extra_ids.get(), joints_out, B, m->V, m->J, m->E, ostride, stream));
+        // landmarks: a stream-ordered pass over this call's vertices
+        if (joints_out && L > 0)
+            HIP_TRY(k2b::launch_landmarks(vertices_out, m->V, m->lmk.ids.get(), m->lmk.w.get(), joints_out, ostride, m->J + m->E, B, L, stream));
+        return K2B_OK;
+    }
+    if (joints_out && m->E > 0) HIP_TRY(skin(m->extra, joints_out, ostride, m->J, nullptr));
+    if (joints_out && L > 0) {
+        // landmarks without the mesh: the 3L vertices skinned alone into the model's workspace (sized above), then combined
+        HIP_TRY(skin(m->lmk.verts, m->lmk.ws.get(), 3 * L, 0, nullptr));
+        HIP_TRY(k2b::launch_landmarks(m->lmk.ws.get(), 3 * L, m->lmk.seq.get(), m->lmk.w.get(), joints_out, ostride, m->J + m->E, B, L, stream));
+    }
+    return K2B_OK;
+}
+
+int k2b_vertex_term(const k2b_model* model_c, int32_t B, int32_t E_sel, const int32_t* extra_index, const float* targets,
+                    const float* conf, float sigma, float joint_loss_weight, const float* go, const float* bp, const float* be,
+                    const float* tr, float* loss_out, float* grad_out, void* stream_v) {
+    k2b_model* m = const_cast<k2b_model*>(model_c);
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_vertex_term: model is NULL");
+    if (B < 0 || E_sel < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_vertex_term: negative size");
+    if (B == 0 || E_sel == 0) return K2B_OK;
+    if (m->J > 64 || m->NB > 32) return fail(K2B_ERR_UNSUPPORTED, "k2b_vertex_term: %d joints / %d shape coefficients, at most 64 / 32", m->J, m->NB);
+    if (E_sel > 32) return fail(K2B_ERR_UNSUPPORTED, "k2b_vertex_term: %d vertex-selected joints, at most 32 per call", E_sel);
+    if (!extra_index || !targets || !go || !bp || !be || !tr || !loss_out || !grad_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_vertex_term: NULL buffer");
+    for (int e = 0; e < E_sel; ++e)
+        if (extra_index[e] < 0 || extra_index[e] >= m->E)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_vertex_term: extra_index[%d]=%d outside [0,%d)", e, extra_index[e], m->E);
+    hipStream_t stream = (hipStream_t)stream_v;
+    k2b::VertexTermArgs a{};
+    a.v_template = m->v_template.get(); a.shapedirs = m->shapedirs.get(); a.posedirs = m->posedirs.get(); a.lbs_weights = m->lbs_weights.get();
+    a.j_template = m->j_template.get(); a.j_dirs = m->j_dirs.get(); a.parents = m->parents.get(); a.extra_ids = m->extra_ids.get();
+    a.num_vertices = m->V; a.num_betas = m->NB; a.num_joints = m->J;
+    a.num_frames = B; a.num_sel = E_sel; a.targets = targets; a.conf = conf;
+    for (int e = 0; e < E_sel; ++e) { a.sel[e] = extra_index[e]; a.sel_k[e] = e; }
+    a.num_targets = E_sel;
+    a.sigma = sigma; a.joint_w = joint_loss_weight;
+    a.go = go; a.bp = bp; a.be = be; a.tr = tr; a.loss_out = loss_out; a.grad_out = grad_out;
+    HIP_TRY(k2b::launch_vertex_term(a, stream));
+    return K2B_OK;
+}
+
+int k2b_surface_term(const k2b_model* model_c, int32_t B, int32_t T, const int32_t* model_joint_index, const float* targets,
+                     const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight, const float* go, const float* bp,
+                     const float* be, const float* tr, float* loss_out, float* grad_out, void* stream_v) {
+    k2b_model* m = const_cast<k2b_model*>(model_c);
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model is NULL");
+    if (B < 0 || T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: negative size");
+    if (B == 0 || T == 0) return K2B_OK;
+    if (T > k2b::kSurfMaxTargets) return fail(K2B_ERR_UNSUPPORTED, "k2b_surface_term: %d targets, at most %d per call", T, k2b::kSurfMaxTargets);
+    if (!model_joint_index || !targets || !go || !bp || !be || !tr || !loss_out || !grad_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: NULL buffer");
+    std::vector<int> sel(T), col(T);
+    for (int t = 0; t < T; ++t) {
+        const int j = model_joint_index[t];
+        if (j < m->J || j >= m->J + m->E + m->lmk.L)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model_joint_index[%d]=%d outside [%d,%d)", t, j, m->J, m->J + m->E + m->lmk.L);
+        sel[t] = j;
+        col[t] = t;
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    k2b::SurfaceTermArgs a{};
+    if (const int rc = surface_table(m, sel, col, stream, &a); rc != K2B_OK) return rc;
+    a.num_frames = B; a.num_targets = T; a.targets = targets; a.conf = conf; a.conf_per_frame = conf_per_frame ? 1 : 0;
+    a.sigma = sigma; a.joint_w = joint_loss_weight;
+    a.go = go; a.bp = bp; a.be = be; a.tr = tr; a.loss_out = loss_out; a.grad_out = grad_out;
+    HIP_TRY(k2b::launch_surface_term(a, stream));
+    return K2B_OK;
+}
+
+int k2b_adam_step(int64_t n, float* params, const float* grad, float* mbuf, float* vbuf, int32_t step, double step_size,
+                  double beta1, double beta2, double eps, void* stream_v) {
+    if (n < 0 || step < 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_adam_step: n=%lld step=%d", (long long)n, step);
+    if (n == 0) return K2B_OK;
+    if (!params || !grad || !mbuf || !vbuf) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_adam_step: NULL buffer");
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    HIP_TRY(k2b::launch_adam(params, grad, mbuf, vbuf, (long long)n, (float)(step_size / bc1), (float)std::sqrt(bc2),
+                             (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (hipStream_t)stream_v));
+    return K2B_OK;
+}
+
+int k2b_angular_error_deg(int64_t n, const float* pred_rotvec, const float* gt_rotvec, float* err_deg_out, void* stream_v) {
+    if (n < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_angular_error_deg: n=%lld must be >= 0", (long long)n);
+    if (n == 0) return K2B_OK;
+    if (!pred_rotvec || !gt_rotvec || !err_deg_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_angular_error_deg: NULL buffer");
+    if (n > (int64_t)0x7fffffff * 256) return fail(K2B_ERR_UNSUPPORTED, "k2b_angular_error_deg: n=%lld exceeds one launch", (long long)n);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(K2B_ERR_NO_DEVICE, "k2b_angular_error_deg: no HIP device visible (this engine has no CPU path)");
+    HIP_TRY(k2b::launch_angular_error(pred_rotvec, gt_rotvec, err_deg_out, (long long)n, (hipStream_t)stream_v));
+    return K2B_OK;
+}
+
+// ---- IK-GAT regressor (k2b_ikgat.hip) ----
+int k2b_ikgat_create(k2b_ikgat** out, int32_t J, int32_t IN, int32_t H, int32_t L, int32_t NH, const int32_t* parents,
+                     const float* weights, int64_t num_weights) {
+    if (!out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: out is NULL");
+    *out = nullptr;
+    if (!parents || !weights) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: NULL array");
+    if (J < 1 || J > 64) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: %d joints, supported 1..64", J);
+    if (IN != 3 && IN != 9) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: input_dim=%d, supported 3 or 9", IN);
+    if (H < 16 || H > 256 || H % 16 != 0)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: hidden_dim=%d, supported multiples of 16 up to 256", H);
+    if (L < 1 || L > 8) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: num_layers=%d, supported 1..8", L);
+    if (NH < 1 || H % NH != 0) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: num_heads=%d does not divide hidden_dim=%d", NH, H);
+    for (int i = 0; i < J; ++i)
+        if (parents[i] >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: parents[%d]=%d, only %d joints", i, parents[i], J);
+    const int64_t expect = ikgat_num_weights(J, IN, H, L);
+    if (num_weights != expect)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: %lld weights, the dimensions need %lld", (long long)num_weights,
+                    (long long)expect);
+    // edges of gan_regressor.py:16-36 (source -> target), then PyG's remove_self_loops + add_self_loops: CSR of in-edges
+    std::vector<std::pair<int, int>> edges;
+    for (int c = 0; c < J; ++c)
+        if (parents[c] >= 0) { edges.emplace_back(parents[c], c); edges.emplace_back(c, parents[c]); }
+    if (edges.empty())
+        for (int i = 0; i + 1 < J; ++i) { edges.emplace_back(i, i + 1); edges.emplace_back(i + 1, i); }
+    std::vector<std::vector<int>> in_nb(J);
+    for (const auto& e : edges)
+        if (e.first != e.second) in_nb[e.second].push_back(e.first);
+    for (int i = 0; i < J; ++i) in_nb[i].push_back(i);
+    std::vector<int> csr(J + 1, 0);
+    for (int i = 0; i < J; ++i) csr[i + 1] = csr[i] + (int)in_nb[i].size();
+    for (int i = 0; i < J; ++i) csr.insert(csr.end(), in_nb[i].begin(), in_nb[i].end());
+    const int nedges = csr[J];
+
+    const int KC = std::min(H / 2, (k2b::kIkgatChunkFloats / k2b::ikgat_ldx(H, NH)) & ~3);   // >= 4: LDX <= 3 H + 3 <= 771
+    const size_t one = k2b::ikgat_lds_bytes(J, H, NH, IN, nedges, 1, KC);
+    if (one > k2b::kIkgatMaxLds)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: one frame needs %zu B of LDS (J=%d H=%d heads=%d), the limit is %zu", one, J,
+                    H, NH, k2b::kIkgatMaxLds);
+    int F = 1;
+    while (F < kIkgatMaxFrames && k2b::ikgat_lds_bytes(J, H, NH, IN, nedges, F + 1, KC) <= kIkgatBatchLds) ++F;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(K2B_ERR_NO_DEVICE, "k2b_ikgat_create: no HIP device visible (this engine has no CPU path)");
+    // device layout (k2b_ikgat.hip): the input layers as given; per layer the projection extended by the attention vectors,
+    // [W^T | W^T att_src | W^T att_dst | 0] (H x LDX, folded in double), then bias and LayerNorm; the head's matrices transposed
+    const int LDX = k2b::ikgat_ldx(H, NH), C = H / NH, H2 = H / 2;
+    std::vector<float> dw(weights, weights + (size_t)2 * H * IN + 2 * H + (size_t)J * H);
+    const float* src = weights + dw.size();
+    for (int l = 0; l < L; ++l) {
+        const float *W = src, *as = W + (size_t)H * H, *ad = as + H;
+        std::vector<float> ext((size_t)H * LDX, 0.f);
+        for (int k = 0; k < H; ++k) {
+            for (int c = 0; c < H; ++c) ext[(size_t)k * LDX + c] = W[(size_t)c * H + k];
+            for (int hd = 0; hd < NH; ++hd) {
+                double s0 = 0.0, s1 = 0.0;
+                for (int c = hd * C; c < (hd + 1) * C; ++c) {
+                    s0 += (double)W[(size_t)c * H + k] * as[c];
+                    s1 += (double)W[(size_t)c * H + k] * ad[c];
+                }
+                ext[(size_t)k * LDX + H + hd] = (float)s0;
+                ext[(size_t)k * LDX + H + NH + hd] = (float)s1;
+            }
+        }
+        dw.insert(dw.end(), ext.begin(), ext.end());
+        dw.insert(dw.end(), ad + H, ad + 4 * H);          // bias, LayerNorm weight, LayerNorm bias
+        src = ad + 4 * H;
+    }
+    const float *w1 = src, *b1 = w1 + (size_t)H2 * H, *w2 = b1 + 3 * H2, *b2 = w2 + 6 * H2;
+    for (int k = 0; k < H; ++k)
+        for (int c = 0; c < H2; ++c) dw.push_back(w1[(size_t)c * H + k]);
+    dw.insert(dw.end(), b1, b1 + 3 * H2);                  // bias, LayerNorm weight, LayerNorm bias
+    for (int k = 0; k < H2; ++k)
+        for (int c = 0; c < 8; ++c) dw.push_back(c < 6 ? w2[(size_t)c * H2 + k] : 0.f);
+    dw.insert(dw.end(), b2, b2 + 6);
+    std::unique_ptr<k2b_ikgat> owner(new k2b_ikgat);          // released with its buffers if an upload fails
+    k2b_ikgat* n = owner.get();
+    n->J = J; n->IN = IN; n->H = H; n->L = L; n->NH = NH; n->nedges = nedges; n->F = F; n->KC = KC; n->LDX = LDX;
+    hipError_t e = n->w.upload(dw.data(), dw.size());
+    if (e == hipSuccess) e = n->csr.upload(csr.data(), csr.size());
+    if (e != hipSuccess) return fail(K2B_ERR_HIP, "k2b_ikgat_create: upload failed: %s", hipGetErrorString(e));
+    *out = owner.release();
+    return K2B_OK;
+}
+
+void k2b_ikgat_destroy(k2b_ikgat* n) {
+    if (!n) return;
+    (void)hipDeviceSynchronize();
+    delete n;
+}
+
+int k2b_ikgat_predict(const k2b_ikgat* n, int32_t num_frames, const float* positions, const float* quat_in, int32_t chain,
+                      float* quat_out, void* stream_v) {
+    if (!n) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: net is NULL");
+    if (num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: num_frames=%d must be >= 0", num_frames);
+    if (num_frames == 0) return K2B_OK;
+    if (!positions || !quat_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: NULL buffer");
+    if (n->IN == 9 && !quat_in)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: the pos-rot6 network (input_dim 9) needs input quaternions");
+    k2b::IkgatArgs a{};
+    a.w = n->w.get(); a.csr = n->csr.get(); a.pos = positions; a.quat_in = n->IN == 9 ? quat_in : nullptr; a.quat_out = quat_out;
+    a.B = num_frames; a.J = n->J; a.H = n->H; a.heads = n->NH; a.L = n->L; a.in = n->IN; a.KC = n->KC; a.ldx = n->LDX; a.nedges = n->nedges;
+    a.chain = chain ? 1 : 0;
+    a.F = a.chain ? 1 : std::min(n->F, (int)num_frames);
+    const size_t lds = k2b::ikgat_lds_bytes(n->J, n->H, n->NH, n->IN, n->nedges, a.F, n->KC);
+    HIP_TRY(k2b::launch_ikgat(a, lds, (hipStream_t)stream_v));
+    return K2B_OK;
+}
+
+}  // extern "C"

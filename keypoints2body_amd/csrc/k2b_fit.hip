@@ -78,7 +78,7 @@ constexpr int NR = D - NC;              // 5 rim rows / columns
 // parameters (row role -> tree / component roles), gradients (tree -> row), theta[0..63] as f16 hi | lo.
 constexpr int RIM_FLOATS = 2 * NR * 64 * 4;
 constexpr int CMU_FLOATS = MG * 2 * NC;
-constexpr int RF_FLOATS = MG * kPriorRimFragEntries * 4;   // rim rows 64..68 as a fifth MFMA row tile, compact (k2b_api.hip)
+constexpr int RF_FLOATS = MG * kPriorRimFragEntries * 4;   // rim rows 64..68 as a fifth MFMA row tile, compact (k2b_api_prior.hip)
 static_assert(RIM_FLOATS + CMU_FLOATS + RF_FLOATS == kPriorImageFloats, "host image size");
 constexpr int XS = 96;                  // strip: go@0, body@4, betas@76, transl@92, joint loss@95
 constexpr int XS_BODY = 4, XS_BETA = 76, XS_TRANSL = 92;
@@ -1461,7 +1461,7 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
     static const int forced[5] = {0, MODE_SPLIT, MODE_SPLIT_PAIRED, MODE_PAIRED, MODE_WIDE};
     auto cap_of = [](int m) { return (m == MODE_SPLIT || m == MODE_SPLIT_LBFGS) ? 4 : ((m == MODE_PAIRED || m == MODE_WIDE) ? MAXS : MAXW); };
     if (a.lb_mode != 0) {
-        if (fpw > (a.lb_mode == 3 ? 2 : 4)) return hipErrorInvalidValue;     // the caller checks (k2b_api.hip: lbfgs_run)
+        if (fpw > (a.lb_mode == 3 ? 2 : 4)) return hipErrorInvalidValue;     // the caller checks (k2b_api_lbfgs.hip: lbfgs_run)
         mode = MODE_SPLIT_LBFGS;
     } else if (a.force_shape) {
         mode = forced[a.force_shape];

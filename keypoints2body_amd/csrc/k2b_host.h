@@ -1,0 +1,239 @@
+// k2b_host.h — private to the host units of the C ABI (k2b_api_*.hip): the handle types behind include/k2b.h, error
+// reporting, owning device buffers and what the units call in one another.  Nothing here reaches a kernel: kernel argument
+// structs (k2b_internal.h) keep raw pointers, filled with .get().
+#pragma once
+#include <cstdint>
+#include <map>
+#include <mutex>
+#include <string>
+#include <tuple>
+#include <utility>
+#include <vector>
+
+#include "../../include/k2b.h"
+#include "k2b_internal.h"
+
+namespace k2b {
+namespace host __attribute__((visibility("hidden"))) {
+
+// records the calling thread's message for k2b_last_error() and returns `code` (k2b_api_misc.hip)
+int fail(int code, const char* fmt, ...);
+int device_cus();
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e__ = (expr);                                                               \
+        if (e__ != hipSuccess)                                                                 \
+            return ::k2b::host::fail(K2B_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+// for calls queued between other launches: clears the sticky error and reports a fixed message ("who: text")
+#define HIP_TRY_MSG(expr, ...)                                                                 \
+    do {                                                                                       \
+        if ((expr) != hipSuccess) {                                                            \
+            (void)hipGetLastError();                                                           \
+            return ::k2b::host::fail(K2B_ERR_HIP, __VA_ARGS__);                                \
+        }                                                                                      \
+    } while (0)
+
+// Owning device pointer: hipFree in the destructor, move-only.
+template <class T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }   // (o releases what this held)
+    ~DevBuf() { (void)reset(); }
+    T* get() const { return p_; }
+    hipError_t reset() {
+        const hipError_t e = p_ ? hipFree(p_) : hipSuccess;
+        p_ = nullptr;
+        return e;
+    }
+    // n elements (at least one is allocated); what the buffer held is released first
+    hipError_t alloc(size_t n) {
+        (void)reset();
+        return hipMalloc(reinterpret_cast<void**>(&p_), (n ? n : 1) * sizeof(T));
+    }
+    hipError_t upload(const T* src, size_t n) {
+        hipError_t e = alloc(n);
+        if (e == hipSuccess && n) e = hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+
+private:
+    T* p_ = nullptr;
+};
+
+// Stream-ordered scratch of one call: hipMallocAsync on the stream, hipFreeAsync behind whatever the call queued.
+class StreamWorkspace {
+public:
+    explicit StreamWorkspace(hipStream_t stream) : stream_(stream) {}
+    StreamWorkspace(const StreamWorkspace&) = delete;
+    ~StreamWorkspace() { if (p_) (void)hipFreeAsync(p_, stream_); }
+    hipError_t alloc(size_t bytes) { return hipMallocAsync(reinterpret_cast<void**>(&p_), bytes, stream_); }
+    unsigned char* get() const { return p_; }
+
+private:
+    hipStream_t stream_;
+    unsigned char* p_ = nullptr;
+};
+
+// The least recently used entry of a cache (values with `dev` and `last_use`) leaves.  The caller has waited for every launch
+// that may still read it.
+template <class Map>
+hipError_t evict_lru(Map& cache) {
+    auto victim = cache.begin();
+    for (auto it = cache.begin(); it != cache.end(); ++it)
+        if (it->second.last_use < victim->second.last_use) victim = it;
+    const hipError_t e = victim->second.dev.reset();
+    cache.erase(victim);
+    return e;
+}
+
+// LBS B operands of a vertex set (f16 hi/lo, MFMA fragment order)
+struct VertexSet {
+    DevBuf<k2b_half> pdh, pdl;
+    DevBuf<k2b_half> w2;                     // W in the tile kernel's group layout (k2b_internal.h, TileArgs)
+    DevBuf<k2b_half> spd, sw;                // stream kernel's Pd / W (k2b_internal.h, StreamArgs), or null
+    int v_tiles = 0, num = 0, nv16 = 0;
+};
+
+}  // namespace host
+}  // namespace k2b
+
+struct __attribute__((visibility("hidden"))) k2b_model {
+    template <class T> using DevBuf = k2b::host::DevBuf<T>;
+    using VertexSet = k2b::host::VertexSet;
+    int V = 0, J = 0, NB = 0, E = 0, P = 0;
+    DevBuf<float> v_template, shapedirs, posedirs, j_regressor, lbs_weights;
+    DevBuf<int> parents, extra_ids;
+    DevBuf<float> j_template, j_dirs;                        // device
+    DevBuf<float> j_basis_lane;                              // device: [3][1 + NB][64 lanes] = template | directions, lane = joint (pose set-up)
+    std::vector<float> h_j_template, h_j_dirs;               // host copies
+    // fused-fit tables (J == 24 only)
+    bool fit_ok = false;
+    std::string fit_why;
+    DevBuf<float> dt, dd;
+    DevBuf<int> tree;
+    std::vector<int> depth;                                  // depth of every joint (root 0)
+    VertexSet mesh, extra;                                   // the whole mesh and the E extra-joint vertices
+    bool joints_in_mesh = false;                             // every extra joint's vertex is tagged in mesh.w2 (no gather launch)
+    bool stream = false;                                     // 17-24 joints and 7 pose k-steps: the stream kernel skins this model
+    bool stream_x = false;                                   // 49-56 joints and 16 pose k-steps (SMPL-X): k2b_lbs_stream_x_kernel
+    // tables of the tree fit kernel (any J <= 64), lane order = DFS pre-order
+    DevBuf<float> tt_dt, tt_dd;
+    DevBuf<int> tt_tab, tt_anc;
+    int tt_prior_dims = -1;                                  // what the prior columns of tt_tab currently describe (guarded by mu)
+    std::vector<int> tt_lane_of;                             // lane of every joint
+    int groups_a = 0;                                        // GA = ceil(J / 8)
+    DevBuf<k2b::k2b_half> wsA2;                              // per-frame A operand of the tile kernel
+    DevBuf<float> dump;                                      // 64 x 3 floats: store target of lanes outside the batch
+    int k_steps_x = 0;
+    // LBS per-frame operand workspace (grow-only)
+    DevBuf<k2b::k2b_half> wsXh, wsXl;
+    int ws_bpad = 0;
+    // Adam coefficient tables, one per (iters, lr, b1, b2); at most kMaxAdamTables, least recently used evicted
+    struct AdamTable { DevBuf<float2> dev; uint64_t last_use; };
+    std::map<std::tuple<int, double, double, double>, AdamTable> adam_tables;
+    uint64_t adam_clock = 0;
+    std::vector<int> h_extra_ids;                            // host copy of extra_vertex_ids
+    // landmarks (k2b_model_set_landmarks): output joint J + E + l = sum_k w[l][k] v[ids[l][k]]
+    struct Landmarks {
+        int L = 0;
+        std::vector<int> h_ids;
+        std::vector<float> h_w;
+        DevBuf<int> ids, seq;                                // device [L][3]; seq[l][k] = 3 l + k (rows of the set below)
+        DevBuf<float> w;                                     // device [L][3]
+        VertexSet verts;                                     // LBS operands of the 3L landmark vertices (joints-only forward)
+        DevBuf<float> ws;                                    // LBS workspace (grow-only, with wsXh ...): the 3L vertices of a
+        int ws_bpad = 0;                                     // joints-only call, [ws_bpad][3L][3]
+    } lmk;
+    bool lmk_set = false;
+    // compact tables of the surface-point term (k2b_surface.hip), one per selection of (model index, target column) pairs;
+    // at most kMaxSurfaceTables, least recently used evicted
+    struct SurfaceTable {
+        DevBuf<unsigned char> dev;
+        k2b::SurfaceTermArgs a{};                            // table pointers and sizes filled, call fields not
+        uint64_t last_use = 0;
+    };
+    std::map<std::vector<int>, SurfaceTable> surface_tables;
+    uint64_t surface_clock = 0;
+    std::mutex mu;
+};
+
+struct __attribute__((visibility("hidden"))) k2b_prior {
+    template <class T> using DevBuf = k2b::host::DevBuf<T>;
+    int M = 0, D = 0;
+    DevBuf<float> pa_image, row_const, nlw;
+    DevBuf<k2b::k2b_half> frag32;
+    float inv_scale[k2b::kPriorMaxGauss] = {};
+    // host copies (symmetrised precisions in double, means, nll weights) and the mixture folded to its first Dv
+    // dimensions for the tree fit kernel, built on first use per Dv
+    std::vector<double> Ps, mu;
+    std::vector<float> nllw;
+    struct Folded { DevBuf<float> pA, ph, pb, pmu, pcl; };
+    std::map<int, Folded> folded;
+    std::mutex mu_lock;
+};
+
+struct __attribute__((visibility("hidden"))) k2b_ikgat {
+    int J = 0, IN = 0, H = 0, L = 0, NH = 0, nedges = 0;
+    int F = 1, KC = 4, LDX = 4;              // frames per workgroup of a batched launch; k-chunk of the staged weights; x' stride
+    k2b::host::DevBuf<float> w;
+    k2b::host::DevBuf<int> csr;
+};
+
+namespace k2b {
+namespace host __attribute__((visibility("hidden"))) {
+
+// ---- k2b_api_model.hip, k2b_api_prior.hip: per-handle tables built on first use ----------------------------------------------
+int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, float2** out);
+int folded_prior(k2b_prior* p, int Dv, const k2b_prior::Folded** out);
+int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<int>& col, hipStream_t stream, SurfaceTermArgs* out);
+int reserve_lbs_workspace(k2b_model* m, int bpad);           // caller holds m->mu
+
+// ---- k2b_api_fit.hip: one description of a fit call --------------------------------------------------------------------------
+struct ConstParams { const float *go = nullptr, *bp = nullptr, *be = nullptr, *tr = nullptr; };
+struct Params {
+    float *go = nullptr, *bp = nullptr, *be = nullptr, *tr = nullptr;
+    ConstParams as_const() const { return {go, bp, be, tr}; }
+};
+struct FitCall {
+    int32_t B = 0, K = 0;                    // frames (in a chain: sequences or slots), targets
+    const int32_t* model_joint_index = nullptr;
+    const float *j3d = nullptr, *conf = nullptr;
+    ConstParams in;
+    Params out;
+    const float *preserve = nullptr, *tr_prior = nullptr;
+    float *loss_out = nullptr, *grad_out = nullptr;
+    hipStream_t stream = nullptr;
+    // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta)
+    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; } chain;
+    // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
+    struct Lbfgs { int mode = 0; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
+};
+// what every entry knows of its call; the parameter arrays and the outputs are set by name
+inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, void* stream) {
+    FitCall c;
+    c.B = B; c.K = K; c.model_joint_index = model_joint_index; c.j3d = j3d; c.conf = conf; c.stream = (hipStream_t)stream;
+    return c;
+}
+int fit_world_impl(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& call);
+
+// Whether the fused 24-lane kernel takes calls of (model, prior, cfg), and the prior width the call means.  k2b_fit.hip relies
+// on `fused` having been checked here.
+struct FusedEligibility { int prior_dims; bool fused; };
+FusedEligibility fused_eligibility(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg);
+bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx);
+int check_targets(const char* who, const k2b_model* m, int32_t K, const int32_t* idx);
+
+// Ragged sequences of the k2b_fit_sequences* entries: the chain slots in launch order.
+struct RaggedSlots {
+    std::vector<int> meta;                   // [slot][4] = {sequence (row of its start parameters), first frame row, frames, 0}
+    int slots = 0, max_len = 0;
+};
+int ragged_slots(const char* who, int32_t S, const int32_t* lengths, const int32_t* offsets, RaggedSlots* r);
+int upload_slots(const std::vector<int>& meta, int* dev, hipStream_t stream);
+
+}  // namespace host
+}  // namespace k2b

@@ -21,7 +21,7 @@ constexpr int kLaneTabStride = 8;   // ints per lane: joint, parent lane, anc[kM
 // LDS image of the prior: rim rows 64..68 over columns 0..63 as [m][5][64], then mu | c = P mu of rows 0..63 as [m][2][64]
 constexpr int kPriorRimFragEntries = 4 * 21;   // per component: 4 fragments [k-step 2][hi | lo] of 20 live lanes + one zero entry, 16 B each
 constexpr int kPriorImageFloats = 2 * 5 * 64 * 4 + kPriorMaxGauss * 2 * 64 + kPriorMaxGauss * kPriorRimFragEntries * 4;
-// the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api.hip):
+// the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api_prior.hip):
 //   [m][tile 4][ks0 hi, ks1 hi, ks0 lo, ks1 lo][64 lanes][8 halfs]
 constexpr int kPriorFrag32Halfs = kPriorMaxGauss * 4 * 4 * 64 * 8;
 
@@ -48,7 +48,7 @@ struct FitArgs {
     int num_rounds;             // pointer-doubling rounds needed by the targeted joints of this call
     int num_betas;
     // prior (device)
-    const float* pa_image;      // LDS image, kPriorImageFloats floats (see k2b_api.hip)
+    const float* pa_image;      // LDS image, kPriorImageFloats floats (see k2b_api_prior.hip)
     const void* pa_frag32;      // kPriorFrag32Halfs f16
     const float* row_const;     // [8][64] per-lane rim constants: P_BB row (5), (P mu)_B, (P_BA mu_A), mu_B
     const float* neg_log_nllw;  // [8]
@@ -339,7 +339,7 @@ hipError_t launch_angular_error(const float* pred, const float* gt, float* out, 
 // quaternions per frame.  Batched: ceil(B / F) workgroups of F frames; chain: one workgroup walks the B frames in order,
 // frame t + 1 reading frame t's outputs as its input quaternions.
 struct IkgatArgs {
-    const float* w;          // device weight layout (k2b_ikgat_create in k2b_api.hip)
+    const float* w;          // device weight layout (k2b_ikgat_create in k2b_api_misc.hip)
     const int* csr;          // [J + 1] in-edge offsets, then the source node of every in-edge (self loops included)
     const float* pos;        // [B][J][3]
     const float* quat_in;    // [B][J][4] xyzw (in == 9), or NULL

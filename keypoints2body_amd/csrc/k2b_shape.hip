@@ -1,5 +1,5 @@
 // k2b_shape.hip — the two small kernels around the fused kernel's evaluate-only launch in the batched shape pre-pass
-// (k2b_shape_pass_lbfgs, k2b_api.hip): one independent L-BFGS over the betas of every sequence, all sequences together.
+// (k2b_shape_pass_lbfgs, k2b_api_lbfgs.hip): one independent L-BFGS over the betas of every sequence, all sequences together.
 //
 //   prep:   every frame's parameters from its sequence's current point - the shape row (betas, the model's remaining
 //           coefficients 0) and the root-aligned translation  transl = y_root - (J_template[root] + J_dirs[root] beta)

@@ -13,7 +13,7 @@
 //
 // Per call the host collects the selection's U distinct vertices (at most 3 x kSurfMaxTargets) and gathers their rows of
 // v_template, shapedirs, posedirs ([PF][3U]: one row of pose features reads 3U contiguous floats) and lbs_weights into a
-// compact table (k2b_surface_gather_kernel), cached per model and selection (k2b_api.hip).  Per iteration one 256-lane
+// compact table (k2b_surface_gather_kernel), cached per model and selection (k2b_api_model.hip).  Per iteration one 256-lane
 // workgroup handles one frame: joints on the first wave, vertices / targets / pose features spread over all four waves,
 // every reduction a fixed-order loop (a frame's result does not depend on the batch it rides in).
 #include "k2b_internal.h"

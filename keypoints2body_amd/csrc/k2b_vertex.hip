@@ -7,7 +7,7 @@
 // (core/fitters/world_space.py:198-201).  This file is the path for that case: k2b_fit_world then queues, per Adam
 // iteration, (1) the fused kernel in evaluate-only mode for the kinematic targets and all priors and (2)
 // `k2b_vertex_term_kernel` with its Adam tail: vertex term, sum of both gradients, the frame's optimiser step
-// (k2b_api.hip::fit_world_vertex_joints; no host work between the launches).  Without the tail the kernel is the
+// (k2b_api_fit.hip::fit_world_vertex_joints; no host work between the launches).  Without the tail the kernel is the
 // stand-alone term behind k2b_vertex_term (L-BFGS closures, tests).
 //
 // Vertex term, one 64-lane workgroup per frame (a handful of vertices: written for clarity, not speed).

@@ -520,3 +520,53 @@ def test_camera_mode_warm_start_sequence_equals_the_frame_loop(assets):
                                 joint_loss_weight=cfg.frame.joint_loss_weight, pose_preserve_weight=cfg.frame.pose_preserve_weight,
                                 freeze_betas=cfg.frame.freeze_betas)
         assert not torch.equal(cold.params.body_pose, res[1].params.body_pose)
+
+
+def test_handles_give_their_device_memory_back():
+    """200 cycles of create / set_landmarks / fit / destroy over model, prior and IK-GAT handles of a small synthetic model, with
+    several Adam configurations and surface selections per cycle (both per-model caches fill): device free memory ends where it
+    started.  The bound is one allocation granule (2 MiB): the model of a cycle alone owns more than that, so a handle that kept
+    its buffers, or a cache that kept its tables, would lose hundreds of granules."""
+    from keypoints2body_amd import native, synthetic
+    dev = torch.device("cuda:0")
+    V, E, NL, B = 1200, 4, 6, 3
+    c = synthetic.make_body_model(0, num_vertices=V, num_extra=E)
+    g = synthetic.make_gmm(0)
+    mb = MixtureBuffers.from_mixture(g.means, g.covars, g.weights)
+    lmk = synthetic.make_landmarks(num_vertices=V, num_joints=24, num_landmarks=NL, joints=(15, 12))
+    J, IN, HID, L, NH = 22, 9, 32, 2, 4
+    num_w = 2 * (HID * IN + HID) + J * HID + L * (HID * HID + 5 * HID) + (HID // 2) * HID + 9 * (HID // 2) + 6
+    weights = (0.1 * np.random.default_rng(0).standard_normal(num_w)).astype(np.float32)
+    parents = np.asarray(synthetic.SMPL_PARENTS[:J], np.int32)
+    p = synthetic.make_poses(B, seed=1)
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float32), device=dev).contiguous()
+    z = lambda k: torch.zeros(B, k, device=dev)
+
+    def cycle(i):
+        model = native.NativeModel(c.v_template, c.shapedirs, c.posedirs, c.J_regressor, c.lbs_weights, c.parents,
+                                   c.extra_vertex_ids, device=dev, landmarks=lmk)
+        prior = native.NativePrior(mb.means, mb.precisions, mb.nll_weights, device=dev)
+        net = native.NativeIkgat(parents, weights, IN, HID, L, NH, device=dev)
+        joints, _ = model.lbs(t(p.global_orient), t(p.body_pose), t(p.betas), t(p.transl), want_vertices=False)
+        cfg = native.default_fit_config()
+        for k in range(3):
+            cfg.num_iters = 2 + (i + k) % 5
+            idx = list(range(22)) + [24 + (i + k) % E, 24 + E + (i + 2 * k) % NL]
+            out = native.fit_world(model, prior, cfg, idx, joints[:, idx].contiguous(), None, z(3), z(69), z(10), t(p.transl))
+            assert bool(torch.isfinite(out["loss"]).all())
+        out = native.fit_world_lbfgs(model, prior, cfg, list(range(22)), joints[:, :22].contiguous(), None, z(3), z(69), z(10),
+                                     t(p.transl), max_iter=4, lr=1.0)
+        net.predict(joints[:, :J].contiguous(), torch.zeros(B, J, 4, device=dev))
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out["loss"]).all())
+
+    for i in range(5):                       # the allocators' own pools reach their steady size
+        cycle(i)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(dev)[0]
+    for i in range(200):
+        cycle(i)
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info(dev)[0]
+    print(f"free device memory before {free_before} B, after {free_after} B, lost {free_before - free_after} B")
+    assert free_before - free_after <= 2 << 20

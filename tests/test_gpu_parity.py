@@ -247,7 +247,7 @@ def test_ill_conditioned_prior_matches_oracle():
 @pytest.mark.parametrize("shape", [1, 2, 3, 4])
 def test_rim_heavy_prior_matches_oracle_in_every_shape(shape):
     """Rows 64..68 of every precision matrix ride on the matrix cores as a fifth row tile whose f16 fragments share the
-    component's power-of-two scale (k2b_api.hip, k2b_fit.hip).  Here the last five pose dimensions are near-linear functions
+    component's power-of-two scale (k2b_api_prior.hip, k2b_fit.hip).  Here the last five pose dimensions are near-linear functions
     of the first 64 (x_B = C x_A + noise of variance 1e-4), so P_BA = -C / sigma^2 carries entries as large as anything in the
     core and P_BB = I / sigma^2 the largest of all: the fit must still follow the CPU float32 arithmetic of the reference's
     formulation (oracle) within the parity budget, in each launch shape."""

@@ -7,6 +7,7 @@ make -s -j8
 DIAG="$(cd ../../tools && pwd)/fit_diag.h"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -ffp-contract=fast -fno-slp-vectorize \
     -DK2B_FIT_DIAG_HEADER="\"$DIAG\"" -c k2b_fit.hip -o /tmp/k2b_fit_fstamp.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/libk2b_fstamp.so k2b_api.o /tmp/k2b_fit_fstamp.o k2b_fit_tree.o k2b_lbs.o \
-    k2b_lbs_stream.o k2b_precompute.o k2b_metrics.o k2b_vertex.o k2b_lbfgs.o
+# every other object as the Makefile lists it
+objs=$(make -s print-objs | sed "s| k2b_fit\.o | /tmp/k2b_fit_fstamp.o |")
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/libk2b_fstamp.so $objs
 echo "built tools/libk2b_fstamp.so"
