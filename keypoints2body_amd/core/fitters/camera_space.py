@@ -37,10 +37,11 @@ from typing import Optional
 import torch
 
 from ... import native
-from ...models.body_model import BodyModel, as_body_model, check_target_indices
+from ...models.body_model import check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData
 from ...prior import MaxMixturePrior
-from ..constants import JOINT_MAP, TORSO_JOINTS, category_indices
+from ..constants import JOINT_MAP, TORSO_JOINTS
+from .common import FitterBase, torch_lbfgs
 
 _TORSO_IDX = [JOINT_MAP[name] for name in TORSO_JOINTS]     # same indices in the AMASS numbering
 _SQUARED_ERROR_SIGMA = 1.0e8                                # gmof(e, sigma) -> e^2 in fp32
@@ -60,26 +61,13 @@ def guess_init_3d(model_joints, j3d, joints_category="SMPL24", torso_index: Opti
     return (tgt - model_joints.index_select(1, torso_index)).sum(dim=1) / 4.0
 
 
-class CameraSpaceFitter:
+class CameraSpaceFitter(FitterBase):
     """Per-frame optimizer operating in camera coordinates, executed on one MI355X."""
 
     def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=True, joints_category="SMPL24",
                  device=None, pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None):
-        self.smpl: BodyModel = as_body_model(smpl_model, device=device)
-        self.device = self.smpl.device
-        self.step_size = step_size
+        super().__init__(smpl_model, step_size, use_lbfgs, joints_category, device, pose_prior_num_gaussians, pose_prior)
         self.num_iters = num_iters
-        self.use_lbfgs = use_lbfgs
-        self.joints_category = joints_category
-        self.smpl_index, self.corr_index = category_indices(joints_category)
-        self.pose_prior = pose_prior if pose_prior is not None else MaxMixturePrior(
-            prior_folder="./data/models/", num_gaussians=pose_prior_num_gaussians, device=self.device)
-
-    def _dev(self, x, cols) -> torch.Tensor:
-        t = torch.as_tensor(x, dtype=torch.float32).detach().to(self.device)
-        if t.dim() != 2 or t.shape[1] != cols:
-            raise ValueError(f"expected a (B,{cols}) tensor, got {tuple(t.shape)}")
-        return t.contiguous()
 
     def stage_configs(self, seq_ind, joint_loss_weight=600.0, pose_preserve_weight=5.0, freeze_betas=True,
                       depth_w=200.0):
@@ -118,17 +106,12 @@ class CameraSpaceFitter:
             raise ValueError("init_params and j3d disagree on the number of frames")
         tg = self._gather_targets(j3d, target_model_indices)
         model_idx, targets = tg["model_idx"], tg["targets"]
-        conf = None if conf_3d is None else torch.as_tensor(conf_3d, dtype=torch.float32).to(self.device).contiguous()
-        if conf is not None and conf.dim() == 2 and not per_frame_conf:
-            conf = conf[0].contiguous()                                          # (the reference reads row 0 only)
+        conf = self._confidence(conf_3d, per_frame_conf)
         s2 = self._stages(go, bp, be, j3d, tg, conf, seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas, init_cam_t)
 
-        out = {k: s2[k] for k in ("global_orient", "body_pose", "betas", "transl")}
+        out = {k: s2[k] for k in native.PARAM_KEYS}
         out["loss"] = self._loss_at(out, model_idx, targets, conf)
-        if not run_forward:
-            return out, None, None, out["loss"]
-        joints, verts = self.final_forward(out, want_vertices=want_vertices)
-        return out, joints, verts, out["loss"]
+        return self._result(out, run_forward, want_vertices)
 
     def _start_rows(self, init_params):
         J = self.smpl.num_joints
@@ -146,15 +129,12 @@ class CameraSpaceFitter:
     def _gather_targets(self, j3d, target_model_indices):
         """Targets of both stages for however many frames `j3d` holds: stage 2 fits ``model_idx`` to ``targets``, stage 1 the
         four torso joints (``camera_space.py:183-198``) or, with caller-chosen indices, all of them (``:199-210``)."""
+        model_idx, rows = self._target_selection(target_model_indices, j3d.shape[1])
         if target_model_indices is None:
-            if self.smpl_index is None:
-                raise ValueError("joints_category='GENERIC' needs target_model_indices")
             torso = self._device_index(_TORSO_IDX)
-            identity = list(self.corr_index) == list(range(j3d.shape[1]))
-            return dict(custom=False, model_idx=list(self.smpl_index),
-                        targets=(j3d if identity else j3d.index_select(1, self._device_index(self.corr_index))).contiguous(),
+            return dict(custom=False, model_idx=model_idx,
+                        targets=(j3d if rows is None else j3d.index_select(1, self._device_index(rows))).contiguous(),
                         stage1_idx=_TORSO_IDX, stage1_tgt=j3d.index_select(1, torso).contiguous(), depth_w=200.0, torso=torso)
-        model_idx = [int(i) for i in torch.as_tensor(target_model_indices).reshape(-1).tolist()]
         check_target_indices(self.smpl, model_idx)
         targets = j3d.contiguous()
         return dict(custom=True, model_idx=model_idx, targets=targets, stage1_idx=model_idx, stage1_tgt=targets, depth_w=100.0,
@@ -224,12 +204,12 @@ class CameraSpaceFitter:
         fitter's own ``fit_frame`` loop (``tests/test_gpu_api.py``)."""
         j3d = torch.as_tensor(j3d, dtype=torch.float32).to(self.device)
         T = j3d.shape[0]
-        conf = None if conf_3d is None else torch.as_tensor(conf_3d, dtype=torch.float32).to(self.device).contiguous()
+        conf = self._confidence(conf_3d, True)                            # (K,), or one row per frame
         go, bp, be = self._start_rows(init_params)
         if not (go.shape[0] == bp.shape[0] == be.shape[0] == 1):
             raise ValueError("fit_chain starts from ONE row of parameters")
         tg = self._gather_targets(j3d, target_model_indices)             # both stages' targets of all T frames, gathered once
-        keys, rows = ("global_orient", "body_pose", "betas", "transl"), []
+        keys, rows = native.PARAM_KEYS, []
         for t in range(T):
             cf = None if conf is None else (conf[t] if conf.dim() == 2 else conf)
             o = self._stages(go, bp, be, j3d, tg, cf, t, joint_loss_weight, pose_preserve_weight, freeze_betas,
@@ -238,10 +218,7 @@ class CameraSpaceFitter:
             go, bp, be = o["global_orient"], o["body_pose"], o["betas"]
         out = {k: torch.cat([r[k] for r in rows], dim=0).contiguous() for k in keys}
         out["loss"] = self._loss_at(out, tg["model_idx"], tg["targets"], conf)
-        if not run_forward:
-            return out, None, None, out["loss"]
-        joints, verts = self.final_forward(out, want_vertices=want_vertices)
-        return out, joints, verts, out["loss"]
+        return self._result(out, run_forward, want_vertices)
 
     def final_forward(self, out, want_vertices=True):
         """Final forward of the reference (camera_space.py:300-314): model-space joints / vertices - the camera translation
@@ -267,10 +244,8 @@ class CameraSpaceFitter:
         ``torch.optim.LBFGS(params, max_iter=num_iters, lr=step_size, line_search_fn="strong_wolfe")`` with
         loss and gradient of every closure call from an evaluate-only launch."""
         max_iter, lr = int(self.num_iters), float(self.step_size)
-        B, D = start["global_orient"].shape[0], start["body_pose"].shape[1]
-        NB = start["betas"].shape[1]
         preserve = start["body_pose"].clone()                     # camera_space.py:136
-        if getattr(self, "lbfgs_driver", "device") == "device":
+        if self.lbfgs_driver == "device":
             # both stages on the device (k2b_fit_world_lbfgs): the stages' optimize_mask keeps the parameters outside the
             # optimiser fixed (stage 1: global_orient + camera translation, camera_space.py:142; stage 2: :219-224)
             cur = start
@@ -279,39 +254,23 @@ class CameraSpaceFitter:
                 cur = native.fit_world_lbfgs(self.smpl.native, self.pose_prior.native, cfg, idx, tgt, cf, cur["global_orient"],
                                              cur["body_pose"], cur["betas"], cur["transl"], max_iter=max_iter, lr=lr,
                                              preserve_pose=preserve, transl_prior_target=cam_t0)
-            return {k: cur[k] for k in ("global_orient", "body_pose", "betas", "transl")}
+            return {k: cur[k] for k in native.PARAM_KEYS}
         for cfg in (cfg1, cfg2):
             cfg.num_iters, cfg.step_size = 1, 0.0
-        rows = {k: [] for k in ("global_orient", "body_pose", "betas", "transl")}
-        # (the optimiser's own arithmetic runs on HOST tensors, as in the reference: see WorldSpaceFitter._fit_lbfgs)
+        rows = {k: [] for k in native.PARAM_KEYS}
+        cols = native.param_columns(start["body_pose"].shape[1], start["betas"].shape[1])
         dev = self.device
-        order = ("global_orient", "body_pose", "betas", "transl")
-        for f in range(B):
+        for f in range(start["global_orient"].shape[0]):          # torch.optim.LBFGS itself, frame by frame (common.torch_lbfgs)
             sl = slice(f, f + 1)
             p = {k: start[k][sl].detach().to("cpu").clone() for k in rows}
             cf = conf[sl].contiguous() if (conf is not None and conf.dim() == 2) else conf
             pres_f, cam_f = preserve[sl].contiguous(), cam_t0[sl].contiguous()
 
             def run(cfg, idx, tgt, cfv, opt_keys):
-                params = [p[k].requires_grad_(True) for k in opt_keys]
-                cols = {"global_orient": slice(0, 3), "body_pose": slice(3, 3 + D), "betas": slice(3 + D, 3 + D + NB),
-                        "transl": slice(3 + D + NB, 3 + D + NB + 3)}
                 tgt_f = tgt[sl].contiguous()
-
-                def closure():
-                    with torch.no_grad():
-                        flat = torch.cat([p[k].detach() for k in order], dim=1).to(dev)
-                        cur = tuple(flat[:, cols[k]].contiguous() for k in order)
-                        r = native.fit_world(self.smpl.native, self.pose_prior.native, cfg, idx, tgt_f, cfv, *cur,
-                                             preserve_pose=pres_f, want_grad=True, transl_prior_target=cam_f)
-                        back = torch.cat((r["grad"], r["loss"][:, None]), dim=1).cpu()
-                    for k in opt_keys:
-                        p[k].grad = back[:, cols[k]].clone()
-                    return back[:, -1].sum()
-
-                torch.optim.LBFGS(params, max_iter=max_iter, lr=lr, line_search_fn="strong_wolfe").step(closure)
-                for k in opt_keys:
-                    p[k] = p[k].detach()
+                evaluate = lambda cur: native.fit_world(self.smpl.native, self.pose_prior.native, cfg, idx, tgt_f, cfv, *cur,
+                                                        preserve_pose=pres_f, want_grad=True, transl_prior_target=cam_f)
+                torch_lbfgs(evaluate, p, opt_keys, cols, dev, max_iter, lr)
 
             run(cfg1, idx1, tgt1, None, ["global_orient", "transl"])                       # camera_space.py:142
             run(cfg2, idx2, tgt2, cf, ["body_pose"] + (["betas"] if fit_betas else []) + ["global_orient", "transl"])  # :219-224

@@ -45,10 +45,11 @@ import numpy as np
 import torch
 
 from ... import native
-from ...models.body_model import BodyModel, as_body_model, check_target_indices
+from ...models.body_model import as_body_model, check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData, SMPLHData, SMPLXData
 from ...prior import MaxMixturePrior
-from ..constants import category_indices, root_indices
+from ..constants import root_indices
+from .common import FitterBase, split_params, torch_lbfgs, upload_params
 
 
 def guess_init_transl_from_root(smpl_model, pose_aa, betas, j3d_world_frame, joints_category="SMPL24"):
@@ -62,27 +63,20 @@ def guess_init_transl_from_root(smpl_model, pose_aa, betas, j3d_world_frame, joi
     return (target[:, root_target, :] - out.joints[:, root_model, :]).detach()
 
 
-class WorldSpaceFitter:
+class WorldSpaceFitter(FitterBase):
     """Per-frame optimizer operating in world coordinates, executed on one MI355X."""
 
     def __init__(self, smpl_model, step_size=1e-2, num_iters_first=30, num_iters_followup=10, use_lbfgs=True,
                  joints_category="SMPL24", device=None, pose_prior_num_gaussians=8,
                  pose_prior: Optional[MaxMixturePrior] = None):
-        self.smpl: BodyModel = as_body_model(smpl_model, device=device)
-        if self.smpl.num_joints not in (24, 52, 55):
+        smpl = as_body_model(smpl_model, device=device)
+        if smpl.num_joints not in (24, 52, 55):
             raise NotImplementedError(
-                f"a body model with {self.smpl.num_joints} joints: the fit kernels are built for the 24-joint SMPL tree "
+                f"a body model with {smpl.num_joints} joints: the fit kernels are built for the 24-joint SMPL tree "
                 "(SMPL-H / SMPL-X parameter sets ride on it unfitted), the 52-joint SMPL-H and the 55-joint SMPL-X tree")
-        self.device = self.smpl.device
-        self.step_size = step_size
+        super().__init__(smpl, step_size, use_lbfgs, joints_category, device, pose_prior_num_gaussians, pose_prior)
         self.num_iters_first = num_iters_first
         self.num_iters_followup = num_iters_followup
-        self.use_lbfgs = use_lbfgs
-        self.joints_category = joints_category
-        self.smpl_index, self.corr_index = category_indices(joints_category)   # raises on unknown category
-        # the reference loads ./data/models/gmm_XX.pkl relative to the CWD (world_space.py:87-91)
-        self.pose_prior = pose_prior if pose_prior is not None else MaxMixturePrior(
-            prior_folder="./data/models/", num_gaussians=pose_prior_num_gaussians, device=self.device)
 
     # ------------------------------------------------------------------------------------
     def _config(self, seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame_conf):
@@ -95,11 +89,25 @@ class WorldSpaceFitter:
         cfg.conf_per_frame = int(bool(per_frame_conf))
         return cfg
 
-    def _dev(self, x, cols=None) -> torch.Tensor:
-        t = torch.as_tensor(x, dtype=torch.float32).detach().to(self.device)
-        if cols is not None and (t.dim() != 2 or t.shape[1] != cols):
-            raise ValueError(f"expected a (B,{cols}) tensor, got {tuple(t.shape)}")
-        return t.contiguous()
+    def _chain_config(self, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame):
+        """Configuration of the warm-start entries: frame 0 as ``seq_ind == 0``, the preserve weight for frames >= 1."""
+        cfg = self._config(0, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
+        cfg.pose_preserve_weight = float(pose_preserve_weight)      # frames >= 1 (frame 0 has no preserve term)
+        return self._packed_config(cfg)
+
+    def _packed_config(self, cfg):
+        if self.smpl.packed:
+            cfg.prior_pose_dims = 3 * self.smpl.NUM_BODY_JOINTS       # 63: what the mixture, bending and preserve terms see
+            cfg.num_betas_prior = self.smpl.num_betas                 # 10: shape prior / freeze_betas leave the expression alone
+        return cfg
+
+    def _pack(self, init, B):
+        """SMPL-H / SMPL-X starts in kernel layout: one pose vector of all non-root joints, one of all shape coefficients."""
+        get = lambda name: getattr(init, name, None)
+        return (self.smpl.pack_pose(B, body_pose=init.body_pose, jaw_pose=get("jaw_pose"), leye_pose=get("leye_pose"),
+                                    reye_pose=get("reye_pose"), left_hand_pose=get("left_hand_pose"),
+                                    right_hand_pose=get("right_hand_pose")),
+                self.smpl.pack_shape(B, init.betas, get("expression")))
 
     def _prepare(self, init_params, j3d, conf_3d, target_model_indices, per_frame_conf, num_init=None):
         """Argument handling shared by ``fit_batch`` and ``fit_chain``: device tensors in kernel layout, the joint
@@ -112,14 +120,9 @@ class WorldSpaceFitter:
             raise ValueError(f"j3d must be (B,K,3), got {tuple(j3d.shape)}")
         J = self.smpl.num_joints
         B = j3d.shape[0]
-        smplx = self.smpl.packed                         # 52- / 55-joint trees (SMPL-H / SMPL-X)
         go = self._dev(init_params.global_orient, 3)
-        if smplx:                                        # one pose vector of all non-root joints, one of all shape coefficients
-            get = lambda name: getattr(init_params, name, None)
-            bp = self.smpl.pack_pose(go.shape[0], body_pose=init_params.body_pose, jaw_pose=get("jaw_pose"),
-                                     leye_pose=get("leye_pose"), reye_pose=get("reye_pose"),
-                                     left_hand_pose=get("left_hand_pose"), right_hand_pose=get("right_hand_pose"))
-            be = self.smpl.pack_shape(go.shape[0], init_params.betas, get("expression"))
+        if self.smpl.packed:                             # 52- / 55-joint trees (SMPL-H / SMPL-X)
+            bp, be = self._pack(init_params, go.shape[0])
         else:
             bp = self._dev(init_params.body_pose, 3 * (J - 1))
             be = self._dev(init_params.betas, self.smpl.num_betas)
@@ -127,35 +130,15 @@ class WorldSpaceFitter:
         if not (go.shape[0] == bp.shape[0] == be.shape[0] == tr.shape[0] == (B if num_init is None else num_init)):
             raise ValueError("init_params and j3d disagree on the number of frames")
 
-        # joint gather (world_space.py:194-201): model joint per target, and the target rows
-        if target_model_indices is None:
-            if self.smpl_index is None:
-                raise ValueError("joints_category='GENERIC' needs target_model_indices")
-            model_idx = list(self.smpl_index)
-            conf_sel = list(self.corr_index)
-            if conf_sel == list(range(j3d.shape[1])):    # AMASS / SMPL24 inputs arrive in target order: the gather is the
-                tgt, conf_sel = j3d, None                # identity (on a device tensor it would upload its index list per call)
-            else:
-                tgt = j3d[:, conf_sel, :]
-        else:
-            model_idx = [int(i) for i in torch.as_tensor(target_model_indices).reshape(-1).tolist()]
+        # joint gather (world_space.py:194-201): model joint per target, and the target rows.  AMASS / SMPL24 inputs arrive in
+        # target order: the gather is the identity (on a device tensor it would upload its index list per call)
+        model_idx, rows = self._target_selection(target_model_indices, j3d.shape[1])
+        if target_model_indices is not None:
             if len(model_idx) != j3d.shape[1]:
                 raise ValueError("target_model_indices must have one entry per target joint")
             check_target_indices(self.smpl, model_idx)
-            tgt = j3d
-            conf_sel = None
-        tgt = tgt.to(self.device).contiguous()
-        if conf_3d is not None:
-            conf = torch.as_tensor(conf_3d, dtype=torch.float32)
-            if conf.dim() == 2 and not per_frame_conf:
-                conf = conf[0]                           # reference quirk, world_space.py:163-164
-            if conf_sel is not None:
-                conf = conf[..., conf_sel]
-            conf = conf.to(self.device).contiguous()
-        else:
-            conf = None
-
-        return go, bp, be, tr, model_idx, tgt, conf
+        tgt = (j3d if rows is None else j3d[:, rows, :]).to(self.device).contiguous()
+        return go, bp, be, tr, model_idx, tgt, self._confidence(conf_3d, per_frame_conf, rows)
 
     def fit_batch(self, init_params: SMPLData, j3d, conf_3d=None, seq_ind: int = 0, target_model_indices=None,
                   joint_loss_weight: float = 600.0, pose_preserve_weight: float = 5.0, freeze_betas: bool = False,
@@ -167,29 +150,27 @@ class WorldSpaceFitter:
         are ``None`` - the sharded sequence path gathers the parameters first.
         """
         go, bp, be, tr, model_idx, tgt, conf = self._prepare(init_params, j3d, conf_3d, target_model_indices, per_frame_conf)
-        J = self.smpl.num_joints
-        smplx = self.smpl.packed
-        cfg = self._config(seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas,
-                           per_frame_conf and conf is not None and conf.dim() == 2)
-        if smplx:
-            cfg.prior_pose_dims = 3 * self.smpl.NUM_BODY_JOINTS       # 63: what the mixture, bending and preserve terms see
-            cfg.num_betas_prior = self.smpl.num_betas                 # 10: shape prior / freeze_betas leave the expression alone
+        cfg = self._packed_config(self._config(seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas,
+                                               per_frame_conf and conf is not None and conf.dim() == 2))
         if self.use_lbfgs:
             out = self._fit_lbfgs(cfg, model_idx, tgt, conf, go, bp, be, tr, freeze_betas)
         else:
             out = native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt, conf, go, bp, be, tr)
-        if not run_forward:
-            return out, None, None, out["loss"]
-        joints, verts = self.final_forward(out, want_vertices=want_vertices)
-        return out, joints, verts, out["loss"]
+        return self._result(out, run_forward, want_vertices)
+
+    def _target_index(self, target_model_indices):
+        """Model joint per target as ``chain_supported`` / ``chains_supported`` judge it (None: a category without a list)."""
+        if target_model_indices is None:
+            return self.smpl_index
+        return torch.as_tensor(target_model_indices).reshape(-1).tolist()
 
     def chain_supported(self, target_model_indices=None) -> bool:
         """Whether ``fit_chain`` can run this fitter's sequence mode in one call: the Adam branch with kinematic targets (ONE
         launch, ``k2b_fit_sequence``), or the L-BFGS branch on the device driver (``k2b_fit_sequence_lbfgs``: one device-driven
         fit per frame, no host work between the frames); otherwise the caller fits frame by frame."""
         if self.use_lbfgs:
-            return getattr(self, "lbfgs_driver", "device") == "device" and (self.smpl_index is not None or target_model_indices is not None)
-        idx = self.smpl_index if target_model_indices is None else torch.as_tensor(target_model_indices).reshape(-1).tolist()
+            return self.lbfgs_driver == "device" and (self.smpl_index is not None or target_model_indices is not None)
+        idx = self._target_index(target_model_indices)
         return idx is not None and all(int(i) < self.smpl.num_joints for i in idx)
 
     def fit_chain(self, init_params: SMPLData, j3d, conf_3d=None, target_model_indices=None,
@@ -205,13 +186,9 @@ class WorldSpaceFitter:
         per_frame = conf_3d is not None and torch.as_tensor(conf_3d).dim() == 2
         go, bp, be, tr, model_idx, tgt, conf = self._prepare(init_params, j3d, conf_3d, target_model_indices, per_frame,
                                                              num_init=1)
-        cfg = self._config(0, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
-        cfg.pose_preserve_weight = float(pose_preserve_weight)      # frames >= 1 (frame 0 has no preserve term)
-        if self.smpl.packed:
-            cfg.prior_pose_dims, cfg.num_betas_prior = 3 * self.smpl.NUM_BODY_JOINTS, self.smpl.num_betas
+        cfg = self._chain_config(joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
         T = tgt.shape[0]
         if self.use_lbfgs:
-            cfg.freeze_betas = int(bool(freeze_betas))
             out = native.fit_sequence_lbfgs(self.smpl.native, self.pose_prior.native, cfg, int(self.num_iters_first),
                                             int(self.num_iters_followup), model_idx, tgt, conf, go, bp, be, tr, lr=float(self.step_size))
         else:
@@ -219,10 +196,7 @@ class WorldSpaceFitter:
                                       tgt.unsqueeze(0), None if conf is None else (conf.unsqueeze(0) if per_frame else conf),
                                       go, bp, be, tr)
             out = {k: v.reshape((T,) + tuple(v.shape[2:])) for k, v in out.items()}
-        if not run_forward:
-            return out, None, None, out["loss"]
-        joints, verts = self.final_forward(out, want_vertices=want_vertices)
-        return out, joints, verts, out["loss"]
+        return self._result(out, run_forward, want_vertices)
 
     def chains_supported(self, target_model_indices=None) -> bool:
         """Whether ``fit_chains`` takes this fitter's configuration in ONE launch - the native entries' own rules: Adam with
@@ -232,7 +206,7 @@ class WorldSpaceFitter:
             return False
         if not self.use_lbfgs:
             return True
-        idx = self.smpl_index if target_model_indices is None else torch.as_tensor(target_model_indices).reshape(-1).tolist()
+        idx = self._target_index(target_model_indices)
         return (self.smpl.num_joints == 24 and not self.smpl.packed and idx is not None
                 and all(0 <= int(i) < self.smpl.num_joints for i in idx))
 
@@ -249,12 +223,8 @@ class WorldSpaceFitter:
         S = int(np.asarray(lengths).reshape(-1).shape[0])
         go, bp, be, tr, model_idx, tgt, conf = self._prepare(init_params, j3d, conf_3d, target_model_indices, per_frame,
                                                              num_init=S)
-        cfg = self._config(0, joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
-        cfg.pose_preserve_weight = float(pose_preserve_weight)      # frames >= 1 (frame 0 has no preserve term)
-        if self.smpl.packed:
-            cfg.prior_pose_dims, cfg.num_betas_prior = 3 * self.smpl.NUM_BODY_JOINTS, self.smpl.num_betas
+        cfg = self._chain_config(joint_loss_weight, pose_preserve_weight, freeze_betas, per_frame)
         if self.use_lbfgs:
-            cfg.freeze_betas = int(bool(freeze_betas))
             return native.fit_sequences_lbfgs(self.smpl.native, self.pose_prior.native, cfg, int(self.num_iters_first),
                                               int(self.num_iters_followup), model_idx, lengths, tgt, conf, go, bp, be, tr,
                                               lr=float(self.step_size))
@@ -263,13 +233,8 @@ class WorldSpaceFitter:
 
     def packed_init(self, init):
         """Kernel layout of SMPL-X parameters: ``body_pose`` = all 162 non-root joint values, ``betas`` = betas | expression."""
-        B = init.global_orient.shape[0]
-        get = lambda name: getattr(init, name, None)
-        return SMPLData(global_orient=init.global_orient, transl=init.transl,
-                        body_pose=self.smpl.pack_pose(B, body_pose=init.body_pose, jaw_pose=get("jaw_pose"), leye_pose=get("leye_pose"),
-                                                      reye_pose=get("reye_pose"), left_hand_pose=get("left_hand_pose"),
-                                                      right_hand_pose=get("right_hand_pose")),
-                        betas=self.smpl.pack_shape(B, init.betas, get("expression")))
+        body_pose, betas = self._pack(init, init.global_orient.shape[0])
+        return SMPLData(global_orient=init.global_orient, transl=init.transl, body_pose=body_pose, betas=betas)
 
     def fit_params(self, cfg, targets, init, model_idx=None):
         """The hot call alone: ONE fused-fit launch on device tensors that are already in kernel layout
@@ -296,68 +261,32 @@ class WorldSpaceFitter:
         "host" (the lock-step numpy restatement ``core/lbfgs_batched.py``) or "torch" (``torch.optim.LBFGS`` itself, one frame
         at a time) - the two host drivers are the device path's twins in the tests."""
         max_iter = int(cfg.num_iters)
-        B, D = go.shape[0], bp.shape[1]
-        NB = be.shape[1]
+        B = go.shape[0]
         preserve = bp.clone()                          # world_space.py:159
-        driver = getattr(self, "lbfgs_driver", "device")
-        if driver == "device":
+        if self.lbfgs_driver == "device":
             # the optimiser's state machine runs in a kernel of its own, one instance per frame; the call only queues launches
             # (k2b_fit_world_lbfgs: max_eval + 2 rounds of [evaluate-only launch, step launch] + the final loss evaluation)
-            cfg.freeze_betas = int(bool(freeze_betas))
             out = native.fit_world_lbfgs(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt, conf, go, bp, be, tr,
                                          max_iter=max_iter, lr=float(self.step_size), preserve_pose=preserve)
             self.last_lbfgs_rounds = max_iter * 5 // 4 + 2
             return out
         cfg.num_iters, cfg.step_size = 1, 0.0          # evaluate-only launches, driven from the host (the round-2 / round-3 drivers,
-        if B > 1 or driver == "host":                  #  kept as the device path's twins: tests, diagnostics)
+        if B > 1 or self.lbfgs_driver == "host":       #  kept as the device path's twins: tests, diagnostics)
             return self._fit_lbfgs_lockstep(cfg, max_iter, model_idx, tgt, conf, go, bp, be, tr, preserve, freeze_betas)
-        outs = {k: [] for k in ("global_orient", "body_pose", "betas", "transl", "loss")}
-        # The optimiser's own arithmetic (two-loop recursion, strong-Wolfe bookkeeping: hundreds of tiny tensor operations per
-        # iteration) runs on HOST tensors, as it does in the reference (whose default device is the CPU): on device tensors every
-        # one of them is a kernel launch, and a 30-iteration fit took 21 ms of which the evaluate-only launches were 0.3 ms.
-        # Per closure call: one upload of the packed parameters, one launch, one download of [gradient | loss].
-        dev = self.device
-        host = lambda t: t.detach().to("cpu").clone()
-        for f in range(B):
-            sl = slice(f, f + 1)
-            p = [host(go[sl]).requires_grad_(True), host(bp[sl]).requires_grad_(True), host(tr[sl]).requires_grad_(True)]
-            beta = host(be[sl])
-            # (SMPL-X: the packed shape vector = betas | expression always joins the optimiser; with frozen betas their part of
-            #  the gradient is zero (``num_betas_prior``), which leaves them - and L-BFGS's inner products - untouched)
-            shape_in_optimiser = not freeze_betas or self.smpl.packed
-            if shape_in_optimiser:
-                beta.requires_grad_(True)
-                p.append(beta)                         # parameter order of world_space.py:215-229
-            cf = conf[sl].contiguous() if (conf is not None and conf.dim() == 2) else conf
-            pres = preserve[sl].contiguous()
-            tgt_f = tgt[sl].contiguous()
-
-            def evaluate(want_grad):
-                with torch.no_grad():
-                    flat = torch.cat((p[0].detach(), p[1].detach(), beta.detach(), p[2].detach()), dim=1).to(dev)
-                    cur = (flat[:, 0:3].contiguous(), flat[:, 3:3 + D].contiguous(), flat[:, 3 + D:3 + D + NB].contiguous(),
-                           flat[:, 3 + D + NB:].contiguous())
-                    r = native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt_f, cf, *cur,
-                                         preserve_pose=pres, want_grad=want_grad)
-                    if not want_grad:
-                        return r["loss"], None
-                    back = torch.cat((r["grad"], r["loss"][:, None]), dim=1).cpu()
-                    return back[:, -1], back[:, :-1]
-
-            def closure():
-                loss, g = evaluate(True)
-                p[0].grad = g[:, 0:3].clone()
-                p[1].grad = g[:, 3:3 + D].clone()
-                p[2].grad = g[:, 3 + D + NB:].clone()
-                if shape_in_optimiser:
-                    beta.grad = g[:, 3 + D:3 + D + NB].clone()
-                return loss.sum()
-
-            torch.optim.LBFGS(p, max_iter=max_iter, lr=float(self.step_size), line_search_fn="strong_wolfe").step(closure)
-            final_loss, _ = evaluate(False)            # world_space.py:245-246
-            outs["global_orient"].append(p[0].detach().to(dev)); outs["body_pose"].append(p[1].detach().to(dev))
-            outs["transl"].append(p[2].detach().to(dev)); outs["betas"].append(beta.detach().to(dev)); outs["loss"].append(final_loss)
-        return {k: torch.cat(v, dim=0).contiguous() for k, v in outs.items()}
+        # one frame under torch.optim.LBFGS itself (common.torch_lbfgs).  Parameter order of world_space.py:215-229.
+        # (SMPL-X: the packed shape vector = betas | expression always joins the optimiser; with frozen betas their part of
+        #  the gradient is zero (``num_betas_prior``), which leaves them - and L-BFGS's inner products - untouched)
+        opt_keys = ["global_orient", "body_pose", "transl"] + (["betas"] if not freeze_betas or self.smpl.packed else [])
+        cols = native.param_columns(bp.shape[1], be.shape[1])
+        p = {k: t.detach().to("cpu").clone() for k, t in zip(native.PARAM_KEYS, (go, bp, be, tr))}
+        evaluate = lambda cur, want_grad=True: native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt,
+                                                                conf, *cur, preserve_pose=preserve, want_grad=want_grad)
+        torch_lbfgs(evaluate, p, opt_keys, cols, self.device, max_iter, float(self.step_size))
+        with torch.no_grad():
+            loss = evaluate(upload_params(p, cols, self.device), False)["loss"]            # world_space.py:245-246
+        out = {k: p[k].detach().to(self.device).contiguous() for k in native.PARAM_KEYS}
+        out["loss"] = loss.contiguous()
+        return out
 
     def _fit_lbfgs_lockstep(self, cfg, max_iter, model_idx, tgt, conf, go, bp, be, tr, preserve, freeze_betas):
         """B > 1 frames in the L-BFGS branch: the B per-frame optimisers advance in lock-step (``core/lbfgs_batched.py``, torch's
@@ -367,21 +296,20 @@ class WorldSpaceFitter:
         operations.  Frames stay independent (each has its own history, line search and stopping rule).  Per round: one
         upload of the (B, P) points, one launch, one download of [gradient | loss]."""
         from ..lbfgs_batched import BatchedLBFGS
-        B, D, NB = go.shape[0], bp.shape[1], be.shape[1]
+        cols = native.param_columns(bp.shape[1], be.shape[1])
         dev = self.device
-        shape_in_optimiser = not freeze_betas or self.smpl.packed          # as in the per-frame path below
+        shape_in_optimiser = not freeze_betas or self.smpl.packed          # as in the per-frame path
         start = torch.cat((go, bp, be, tr), dim=1)                         # kernel layout [go | pose | shape | transl]
-        free = np.ones(3 + D + NB + 3, dtype=bool)
+        free = np.ones(start.shape[1], dtype=bool)
         if not shape_in_optimiser:
-            free[3 + D: 3 + D + NB] = False
+            free[cols["betas"]] = False
         free_t = torch.as_tensor(free, device=dev)
         flat = start.clone()
 
         def launch(x_free, want_grad):
             with torch.no_grad():
                 flat[:, free_t] = torch.from_numpy(np.ascontiguousarray(x_free, dtype=np.float32)).to(dev)
-                cur = (flat[:, 0:3].contiguous(), flat[:, 3:3 + D].contiguous(), flat[:, 3 + D:3 + D + NB].contiguous(),
-                       flat[:, 3 + D + NB:].contiguous())
+                cur = split_params(flat, cols)
                 return native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt, conf, *cur,
                                         preserve_pose=preserve, want_grad=want_grad), cur
 

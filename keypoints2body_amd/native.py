@@ -23,16 +23,6 @@ K2B_ERR_UNSUPPORTED = -2
 K2B_ERR_HIP = -3
 K2B_ERR_NO_DEVICE = -4
 
-EXPORTED_SYMBOLS = (
-    "k2b_version", "k2b_last_error", "k2b_model_create", "k2b_model_destroy", "k2b_model_dims",
-    "k2b_model_joint_basis", "k2b_model_reserve", "k2b_debug_read_dump", "k2b_prior_create", "k2b_prior_destroy", "k2b_fit_config_default", "k2b_fit_config_size",
-    "k2b_fit_world", "k2b_fit_sequence", "k2b_lbs", "k2b_vertex_term", "k2b_adam_step", "k2b_angular_error_deg",
-    "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs", "k2b_model_set_landmarks", "k2b_model_num_landmarks", "k2b_surface_term",
-    "k2b_ikgat_create", "k2b_ikgat_destroy", "k2b_ikgat_predict", "k2b_fit_sequences", "k2b_fit_sequences_lbfgs",
-    "k2b_sequence_order", "k2b_shape_pass_lbfgs",
-)
-
-
 class FitConfigC(C.Structure):
     """Mirror of ``k2b_fit_config`` (include/k2b.h)."""
 
@@ -64,6 +54,52 @@ def library_path() -> Path:
     return _LIB_PATH
 
 
+_vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+_FIT_HEAD = (_vp, _vp, C.POINTER(FitConfigC))       # model, prior, cfg
+_FIT_IN = (_i32, _vp) + (_vp,) * 6                  # num_targets, model_joint_index, j3d, conf, the four start parameters
+_FIT_OUT = (_vp,) * 5                               # the four fitted parameters, loss
+_LBFGS_TAIL = (_i32, _f64, _f64, _f64)              # history_size, lr, tolerance_grad, tolerance_change
+_STREAM = (_vp,)
+
+# (symbol, restype, argtypes) of every declaration of include/k2b.h; tests/test_host_logic.py holds the two together
+_PROTOTYPES = (
+    ("k2b_version", C.c_uint32, ()),
+    ("k2b_last_error", C.c_char_p, ()),
+    ("k2b_model_create", C.c_int, (C.POINTER(_vp),) + (_i32,) * 4 + (_vp,) * 7),
+    ("k2b_model_destroy", None, (_vp,)),
+    ("k2b_model_dims", C.c_int, (_vp,) + (C.POINTER(_i32),) * 4),
+    ("k2b_model_joint_basis", C.c_int, (_vp, _vp, _vp)),
+    ("k2b_model_reserve", C.c_int, (_vp, _i32)),
+    ("k2b_debug_read_dump", C.c_int, (_vp, _vp, _i64)),
+    ("k2b_prior_create", C.c_int, (C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp)),
+    ("k2b_prior_destroy", None, (_vp,)),
+    ("k2b_fit_config_default", None, (C.POINTER(FitConfigC),)),
+    ("k2b_fit_config_size", C.c_uint32, ()),
+    ("k2b_fit_world", C.c_int, _FIT_HEAD + (_i32,) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + _STREAM),
+    ("k2b_fit_sequence", C.c_int, _FIT_HEAD + (_i32, _i32, _i32) + _FIT_IN + _FIT_OUT + _STREAM),
+    ("k2b_lbs", C.c_int, (_vp, _i32) + (_vp,) * 6 + _STREAM),
+    ("k2b_vertex_term", C.c_int, (_vp, _i32, _i32, _vp, _vp, _vp, _f32, _f32) + (_vp,) * 6 + _STREAM),
+    ("k2b_adam_step", C.c_int, (_i64,) + (_vp,) * 4 + (_i32,) + (_f64,) * 4 + _STREAM),
+    ("k2b_angular_error_deg", C.c_int, (_i64, _vp, _vp, _vp) + _STREAM),
+    ("k2b_fit_world_lbfgs", C.c_int,
+     _FIT_HEAD + (_i32,) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + (_i32,) + _LBFGS_TAIL + _STREAM),
+    ("k2b_fit_sequence_lbfgs", C.c_int, _FIT_HEAD + (_i32,) + _FIT_IN + _FIT_OUT + (_i32, _i32) + _LBFGS_TAIL + _STREAM),
+    ("k2b_model_set_landmarks", C.c_int, (_vp, _i32, _vp, _vp)),
+    ("k2b_model_num_landmarks", C.c_int, (_vp, C.POINTER(_i32))),
+    ("k2b_surface_term", C.c_int, (_vp, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32) + (_vp,) * 6 + _STREAM),
+    ("k2b_ikgat_create", C.c_int, (C.POINTER(_vp),) + (_i32,) * 5 + (_vp, _vp, _i64)),
+    ("k2b_ikgat_destroy", None, (_vp,)),
+    ("k2b_ikgat_predict", C.c_int, (_vp, _i32, _vp, _vp, _i32, _vp) + _STREAM),
+    ("k2b_fit_sequences", C.c_int, _FIT_HEAD + (_i32, _vp, _vp, _i32) + _FIT_IN + _FIT_OUT + _STREAM),
+    ("k2b_fit_sequences_lbfgs", C.c_int,
+     _FIT_HEAD + (_i32, _vp, _vp) + _FIT_IN + _FIT_OUT + (_i32, _i32) + _LBFGS_TAIL + _STREAM),
+    ("k2b_sequence_order", C.c_int, (_i32, _vp, _vp, _vp, C.POINTER(_i32))),
+    ("k2b_shape_pass_lbfgs", C.c_int,
+     _FIT_HEAD + (_i32, _vp, _i32, _i32, _vp) + (_vp,) * 5 + (_i32, _i32, _vp, _vp, _i32) + _LBFGS_TAIL + _STREAM),
+)
+EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
+
+
 def load_library():
     """dlopen ``libk2b.so`` and declare prototypes (no device call is made)."""
     global _lib
@@ -76,73 +112,11 @@ def load_library():
             "keypoints2body_amd has no CPU fallback."
         )
     lib = C.CDLL(str(_LIB_PATH))
-    vp, fp, ip = C.c_void_p, C.c_void_p, C.c_void_p
-    lib.k2b_version.restype = C.c_uint32
-    lib.k2b_last_error.restype = C.c_char_p
-    lib.k2b_model_create.restype = C.c_int
-    lib.k2b_model_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     fp, fp, fp, fp, fp, ip, ip]
-    lib.k2b_model_destroy.restype = None
-    lib.k2b_model_destroy.argtypes = [vp]
-    lib.k2b_model_dims.restype = C.c_int
-    lib.k2b_model_dims.argtypes = [vp] + [C.POINTER(C.c_int32)] * 4
-    lib.k2b_debug_read_dump.restype = C.c_int
-    lib.k2b_debug_read_dump.argtypes = [vp, vp, C.c_int64]
-    lib.k2b_model_reserve.restype = C.c_int
-    lib.k2b_model_reserve.argtypes = [vp, C.c_int32]
-    lib.k2b_model_joint_basis.restype = C.c_int
-    lib.k2b_model_joint_basis.argtypes = [vp, fp, fp]
-    lib.k2b_prior_create.restype = C.c_int
-    lib.k2b_prior_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, fp, fp, fp]
-    lib.k2b_prior_destroy.restype = None
-    lib.k2b_prior_destroy.argtypes = [vp]
-    lib.k2b_fit_config_default.restype = None
-    lib.k2b_fit_config_default.argtypes = [C.POINTER(FitConfigC)]
-    lib.k2b_fit_config_size.restype = C.c_uint32
-    if lib.k2b_fit_config_size() != C.sizeof(FitConfigC):
-        raise RuntimeError("libk2b.so was built with a different k2b_fit_config layout than native.FitConfigC")
-    lib.k2b_fit_world.restype = C.c_int
-    lib.k2b_fit_world.argtypes = [vp, vp, C.POINTER(FitConfigC), C.c_int32, C.c_int32, ip] + [fp] * 14 + [vp]
-    lib.k2b_fit_sequence.restype = C.c_int
-    lib.k2b_fit_sequence.argtypes = [vp, vp, C.POINTER(FitConfigC)] + [C.c_int32] * 4 + [ip] + [fp] * 11 + [vp]
-    lib.k2b_lbs.restype = C.c_int
-    lib.k2b_lbs.argtypes = [vp, C.c_int32] + [fp] * 6 + [vp]
-    lib.k2b_fit_world_lbfgs.restype = C.c_int
-    lib.k2b_fit_world_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, C.c_int32, ip] + [fp] * 14 +
-                                        [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
-    lib.k2b_fit_sequence_lbfgs.restype = C.c_int
-    lib.k2b_fit_sequence_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, C.c_int32, ip] + [fp] * 11 +
-                                           [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
-    lib.k2b_fit_sequences.restype = C.c_int
-    lib.k2b_fit_sequences.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, ip, C.c_int32, C.c_int32, ip] + [fp] * 11 +
-                                      [vp])
-    lib.k2b_fit_sequences_lbfgs.restype = C.c_int
-    lib.k2b_fit_sequences_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, ip, C.c_int32, ip] + [fp] * 11 +
-                                            [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp])
-    lib.k2b_sequence_order.restype = C.c_int
-    lib.k2b_sequence_order.argtypes = [C.c_int32, ip, ip, ip, C.POINTER(C.c_int32)]
-    lib.k2b_shape_pass_lbfgs.restype = C.c_int
-    lib.k2b_shape_pass_lbfgs.argtypes = ([vp, vp, C.POINTER(FitConfigC), C.c_int32, ip, C.c_int32, C.c_int32, ip] + [fp] * 5 +
-                                         [C.c_int32, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
-                                          vp])
-    lib.k2b_vertex_term.restype = C.c_int
-    lib.k2b_vertex_term.argtypes = [vp, C.c_int32, C.c_int32, ip, fp, fp, C.c_float, C.c_float] + [fp] * 6 + [vp]
-    lib.k2b_model_set_landmarks.restype = C.c_int
-    lib.k2b_model_set_landmarks.argtypes = [vp, C.c_int32, ip, fp]
-    lib.k2b_model_num_landmarks.restype = C.c_int
-    lib.k2b_model_num_landmarks.argtypes = [vp, C.POINTER(C.c_int32)]
-    lib.k2b_surface_term.restype = C.c_int
-    lib.k2b_surface_term.argtypes = [vp, C.c_int32, C.c_int32, ip, fp, fp, C.c_int32, C.c_float, C.c_float] + [fp] * 6 + [vp]
-    lib.k2b_adam_step.restype = C.c_int
-    lib.k2b_adam_step.argtypes = [C.c_int64, fp, fp, fp, fp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.k2b_angular_error_deg.restype = C.c_int
-    lib.k2b_angular_error_deg.argtypes = [C.c_int64, fp, fp, fp, vp]
-    lib.k2b_ikgat_create.restype = C.c_int
-    lib.k2b_ikgat_create.argtypes = [C.POINTER(vp)] + [C.c_int32] * 5 + [ip, fp, C.c_int64]
-    lib.k2b_ikgat_destroy.restype = None
-    lib.k2b_ikgat_destroy.argtypes = [vp]
-    lib.k2b_ikgat_predict.restype = C.c_int
-    lib.k2b_ikgat_predict.argtypes = [vp, C.c_int32, fp, fp, C.c_int32, fp, vp]
+    for name, restype, argtypes in _PROTOTYPES:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+        if name == "k2b_fit_config_size" and fn() != C.sizeof(FitConfigC):     # before any prototype that takes the struct is used
+            raise RuntimeError("libk2b.so was built with a different k2b_fit_config layout than native.FitConfigC")
     _lib = lib
     return lib
 
@@ -200,8 +174,36 @@ def require_device(device=None) -> torch.device:
     return dev
 
 
-class NativeModel:
+class _Handle:
+    """Owner of one library handle in ``_h``; ``_destroy`` names the symbol that frees it when the owner goes."""
+
+    _destroy = ""
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value and _lib is not None:
+                getattr(_lib, self._destroy)(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def _launch(name: str, dev: torch.device, *args):
+    """The one way into a stream-ordered entry: on `dev`, ``<name>(*args, current stream)``, a failure status raised.
+    (``getattr`` on the CDLL is the attribute read ``lib.<name>`` is: ctypes caches the function on first use.)"""
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(getattr(load_library(), name)(*args, stream), name)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class NativeModel(_Handle):
     """Owner of a ``k2b_model`` handle (body-model constants in HBM)."""
+
+    _destroy = "k2b_model_destroy"
 
     def __init__(self, v_template, shapedirs, posedirs, J_regressor, lbs_weights, parents,
                  extra_vertex_ids, device=None, landmarks=None):
@@ -265,30 +267,17 @@ class NativeModel:
         """Full forward: returns (joints (B,J+E+L,3), vertices (B,V,3) or None)."""
         dev = self.device
         B = global_orient.shape[0]
-        D = 3 * (self.num_joints - 1)
-        go = _dev(global_orient, "global_orient", dev, (B, 3))
-        bp = _dev(body_pose, "body_pose", dev, (B, D))
-        be = _dev(betas, "betas", dev, (B, self.num_betas))
-        tr = _dev(transl, "transl", dev, (B, 3))
+        params = _param_ptrs(self, B, global_orient, body_pose, betas, transl)
         joints = torch.empty((B, self.num_output_joints, 3), dtype=torch.float32, device=dev)
         verts = torch.empty((B, self.num_vertices, 3), dtype=torch.float32, device=dev) if want_vertices else None
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _check(load_library().k2b_lbs(self._h, B, go, bp, be, tr, C.c_void_p(joints.data_ptr()),
-                                          C.c_void_p(verts.data_ptr()) if verts is not None else None, stream), "k2b_lbs")
+        _launch("k2b_lbs", dev, self._h, B, *params, _ptr(joints), _ptr(verts))
         return joints, verts
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value and _lib is not None:
-                _lib.k2b_model_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
-
-class NativePrior:
+class NativePrior(_Handle):
     """Owner of a ``k2b_prior`` handle built from the reference prior's buffers."""
+
+    _destroy = "k2b_prior_destroy"
 
     def __init__(self, means, precisions, nll_weights, device=None):
         self.device = require_device(device)
@@ -308,14 +297,6 @@ class NativePrior:
     def handle(self):
         return self._h
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value and _lib is not None:
-                _lib.k2b_prior_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
 
 def default_fit_config() -> FitConfigC:
     cfg = FitConfigC()
@@ -323,46 +304,80 @@ def default_fit_config() -> FitConfigC:
     return cfg
 
 
+# ---- the one description of a fit call -----------------------------------------------------------------------------
+PARAM_KEYS = ("global_orient", "body_pose", "betas", "transl")   # order of the packed parameter / gradient row (k2b.h, grad_out)
+
+
+def param_columns(D: int, NB: int) -> dict:
+    """Column slices of the packed row ``[global_orient | body_pose | betas | transl]`` for a pose of `D` = 3 (J - 1) values and
+    `NB` shape coefficients: the layout of ``grad`` and of the host-driven L-BFGS twins' parameter rows."""
+    edges = (0, 3, 3 + D, 3 + D + NB, 3 + D + NB + 3)
+    return {k: slice(a, b) for k, a, b in zip(PARAM_KEYS, edges, edges[1:])}
+
+
+def _param_widths(model: NativeModel):
+    return 3, 3 * (model.num_joints - 1), model.num_betas, 3
+
+
+def _param_ptrs(model: NativeModel, rows: int, global_orient, body_pose, betas, transl):
+    """Validated pointers of `rows` rows of parameters."""
+    return [_dev(t, k, model.device, (rows, w))
+            for k, w, t in zip(PARAM_KEYS, _param_widths(model), (global_orient, body_pose, betas, transl))]
+
+
+def _joint_index(index, count: int, name: str = "model_joint_index") -> np.ndarray:
+    """Host int32 joint per target, one entry per target."""
+    idx = _host_i32(np.asarray(list(index)))
+    if idx.shape != (count,):
+        raise ValueError(f"{name} has {idx.shape[0]} entries for {count} targets")
+    return idx
+
+
+def _fit_outputs(model: NativeModel, lead: tuple, want_grad: bool = False) -> dict:
+    """The result tensors of a fit over frames of leading shape `lead` (+ ``grad`` in the packed layout)."""
+    new = lambda *shape: torch.empty(lead + shape, dtype=torch.float32, device=model.device)
+    widths = _param_widths(model)
+    out = {k: new(w) for k, w in zip(PARAM_KEYS, widths)}
+    out["loss"] = new()
+    if want_grad:
+        out["grad"] = new(sum(widths))
+    return out
+
+
+def _lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change):
+    return int(history_size), float(lr), float(tolerance_grad), float(tolerance_change)
+
+
+def _fit_call(name: str, model: NativeModel, prior: NativePrior, cfg: FitConfigC, head: tuple, idx: np.ndarray, lead: tuple,
+              starts: int, j3d, conf, global_orient, body_pose, betas, transl, tail: tuple = (), world: Optional[tuple] = None):
+    """Set-up and launch of every fit entry.  The C arguments are (model, prior, cfg, *`head`, K, joint index, targets of
+    leading shape `lead`, confidences, `starts` rows of start parameters, [preserve_pose, transl_prior_target], the five
+    outputs, [grad], *`tail`, stream); the bracketed ones belong to ``k2b_fit_world*`` and come with
+    `world` = (preserve_pose, transl_prior_target, want_grad)."""
+    dev, K = model.device, idx.shape[0]
+    conf_p = _dev(conf, "conf", dev, lead + (K,) if cfg.conf_per_frame else (K,))
+    ins = [_dev(j3d, "j3d", dev, lead + (K, 3)), conf_p, *_param_ptrs(model, starts, global_orient, body_pose, betas, transl)]
+    want_grad = False
+    if world is not None:
+        preserve_pose, transl_prior_target, want_grad = world
+        ins += [_dev(preserve_pose, "preserve_pose", dev, (starts, _param_widths(model)[1])),
+                _dev(transl_prior_target, "transl_prior_target", dev, (starts, 3))]
+    out = _fit_outputs(model, lead, want_grad)
+    outs = [_ptr(out[k]) for k in PARAM_KEYS + ("loss",)]
+    if world is not None:
+        outs.append(_ptr(out.get("grad")))
+    _launch(name, dev, model.handle, prior.handle, C.byref(cfg), *head, K, _np_ptr(idx), *ins, *outs, *tail)
+    return out
+
+
 def fit_world(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joint_index: Sequence[int],
               j3d: torch.Tensor, conf: Optional[torch.Tensor], global_orient: torch.Tensor, body_pose: torch.Tensor,
               betas: torch.Tensor, transl: torch.Tensor, preserve_pose: Optional[torch.Tensor] = None,
               want_grad: bool = False, transl_prior_target: Optional[torch.Tensor] = None):
     """Launch the fused fit on the current stream; returns a dict of device tensors."""
-    dev = model.device
-    B, K = j3d.shape[0], j3d.shape[1]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
-    if conf is not None:
-        want = (B, K) if cfg.conf_per_frame else (K,)
-        conf_p = _dev(conf, "conf", dev, want)
-    else:
-        conf_p = None
-    out = {
-        "global_orient": torch.empty((B, 3), dtype=torch.float32, device=dev),
-        "body_pose": torch.empty((B, D), dtype=torch.float32, device=dev),
-        "betas": torch.empty((B, model.num_betas), dtype=torch.float32, device=dev),
-        "transl": torch.empty((B, 3), dtype=torch.float32, device=dev),
-        "loss": torch.empty((B,), dtype=torch.float32, device=dev),
-    }
-    P = 3 + D + model.num_betas + 3
-    if want_grad:
-        out["grad"] = torch.empty((B, P), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_world(
-            model.handle, prior.handle, C.byref(cfg), B, K, _np_ptr(idx),
-            _dev(j3d, "j3d", dev, (B, K, 3)), conf_p,
-            _dev(global_orient, "global_orient", dev, (B, 3)), _dev(body_pose, "body_pose", dev, (B, D)),
-            _dev(betas, "betas", dev, (B, model.num_betas)), _dev(transl, "transl", dev, (B, 3)),
-            _dev(preserve_pose, "preserve_pose", dev, (B, D)),
-            _dev(transl_prior_target, "transl_prior_target", dev, (B, 3)),
-            C.c_void_p(out["global_orient"].data_ptr()), C.c_void_p(out["body_pose"].data_ptr()),
-            C.c_void_p(out["betas"].data_ptr()), C.c_void_p(out["transl"].data_ptr()),
-            C.c_void_p(out["loss"].data_ptr()),
-            C.c_void_p(out["grad"].data_ptr()) if want_grad else None, stream), "k2b_fit_world")
-    return out
+    B = j3d.shape[0]
+    return _fit_call("k2b_fit_world", model, prior, cfg, (B,), _joint_index(model_joint_index, j3d.shape[1]), (B,), B,
+                     j3d, conf, global_orient, body_pose, betas, transl, world=(preserve_pose, transl_prior_target, want_grad))
 
 
 def fit_world_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joint_index: Sequence[int],
@@ -375,39 +390,11 @@ def fit_world_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, mod
     line_search_fn="strong_wolfe").step(closure)`` with this library's evaluate-only launch as the closure and the optimiser's
     state machine in a kernel of its own; only launches are queued on the current stream.  Returns the dict of ``fit_world``
     (``loss`` = the loss at the result, ``grad`` with `want_grad`)."""
-    dev = model.device
-    B, K = j3d.shape[0], j3d.shape[1]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
-    conf_p = None
-    if conf is not None:
-        conf_p = _dev(conf, "conf", dev, (B, K) if cfg.conf_per_frame else (K,))
-    out = {
-        "global_orient": torch.empty((B, 3), dtype=torch.float32, device=dev),
-        "body_pose": torch.empty((B, D), dtype=torch.float32, device=dev),
-        "betas": torch.empty((B, model.num_betas), dtype=torch.float32, device=dev),
-        "transl": torch.empty((B, 3), dtype=torch.float32, device=dev),
-        "loss": torch.empty((B,), dtype=torch.float32, device=dev),
-    }
-    if want_grad:
-        out["grad"] = torch.empty((B, 3 + D + model.num_betas + 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_world_lbfgs(
-            model.handle, prior.handle, C.byref(cfg), B, K, _np_ptr(idx),
-            _dev(j3d, "j3d", dev, (B, K, 3)), conf_p,
-            _dev(global_orient, "global_orient", dev, (B, 3)), _dev(body_pose, "body_pose", dev, (B, D)),
-            _dev(betas, "betas", dev, (B, model.num_betas)), _dev(transl, "transl", dev, (B, 3)),
-            _dev(preserve_pose, "preserve_pose", dev, (B, D)),
-            _dev(transl_prior_target, "transl_prior_target", dev, (B, 3)),
-            C.c_void_p(out["global_orient"].data_ptr()), C.c_void_p(out["body_pose"].data_ptr()),
-            C.c_void_p(out["betas"].data_ptr()), C.c_void_p(out["transl"].data_ptr()),
-            C.c_void_p(out["loss"].data_ptr()), C.c_void_p(out["grad"].data_ptr()) if want_grad else None,
-            int(max_iter), int(history_size), float(lr), float(tolerance_grad), float(tolerance_change), stream),
-            "k2b_fit_world_lbfgs")
-    return out
+    B = j3d.shape[0]
+    return _fit_call("k2b_fit_world_lbfgs", model, prior, cfg, (B,), _joint_index(model_joint_index, j3d.shape[1]), (B,), B,
+                     j3d, conf, global_orient, body_pose, betas, transl,
+                     tail=(int(max_iter), *_lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change)),
+                     world=(preserve_pose, transl_prior_target, want_grad))
 
 
 def fit_sequence_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, first_iters: int, followup_iters: int,
@@ -416,33 +403,10 @@ def fit_sequence_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, 
                        history_size: int = 100, tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9):
     """ONE warm-start sequence under the L-BFGS branch (``k2b_fit_sequence_lbfgs``): ``j3d`` (T, K, 3), start (1, ...) of frame
     0; every later frame starts from its predecessor's result with ``cfg.pose_preserve_weight``; returns (T, ...) tensors."""
-    dev = model.device
-    T, K = j3d.shape[0], j3d.shape[1]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
-    conf_p = None
-    if conf is not None:
-        conf_p = _dev(conf, "conf", dev, (T, K) if cfg.conf_per_frame else (K,))
-    out = {
-        "global_orient": torch.empty((T, 3), dtype=torch.float32, device=dev),
-        "body_pose": torch.empty((T, D), dtype=torch.float32, device=dev),
-        "betas": torch.empty((T, model.num_betas), dtype=torch.float32, device=dev),
-        "transl": torch.empty((T, 3), dtype=torch.float32, device=dev),
-        "loss": torch.empty((T,), dtype=torch.float32, device=dev),
-    }
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_sequence_lbfgs(
-            model.handle, prior.handle, C.byref(cfg), T, K, _np_ptr(idx), _dev(j3d, "j3d", dev, (T, K, 3)), conf_p,
-            _dev(global_orient, "global_orient", dev, (1, 3)), _dev(body_pose, "body_pose", dev, (1, D)),
-            _dev(betas, "betas", dev, (1, model.num_betas)), _dev(transl, "transl", dev, (1, 3)),
-            C.c_void_p(out["global_orient"].data_ptr()), C.c_void_p(out["body_pose"].data_ptr()),
-            C.c_void_p(out["betas"].data_ptr()), C.c_void_p(out["transl"].data_ptr()), C.c_void_p(out["loss"].data_ptr()),
-            int(first_iters), int(followup_iters), int(history_size), float(lr), float(tolerance_grad), float(tolerance_change),
-            stream), "k2b_fit_sequence_lbfgs")
-    return out
+    T = j3d.shape[0]
+    return _fit_call("k2b_fit_sequence_lbfgs", model, prior, cfg, (T,), _joint_index(model_joint_index, j3d.shape[1]), (T,), 1,
+                     j3d, conf, global_orient, body_pose, betas, transl,
+                     tail=(int(first_iters), int(followup_iters), *_lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change)))
 
 
 def fit_sequence(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int,
@@ -451,33 +415,9 @@ def fit_sequence(model: NativeModel, prior: NativePrior, cfg: FitConfigC, follow
     """Warm-start chains in one launch (``k2b_fit_sequence``): ``j3d`` (S, T, K, 3), start parameters (S, ...) of every
     sequence's first frame; returns (S, T, ...) tensors.  ``cfg.num_iters`` iterations for frame 0, ``followup_iters``
     for the others, ``cfg.pose_preserve_weight`` on frames >= 1."""
-    dev = model.device
-    S, T, K = j3d.shape[0], j3d.shape[1], j3d.shape[2]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
-    conf_p = None
-    if conf is not None:
-        conf_p = _dev(conf, "conf", dev, (S, T, K) if cfg.conf_per_frame else (K,))
-    out = {
-        "global_orient": torch.empty((S, T, 3), dtype=torch.float32, device=dev),
-        "body_pose": torch.empty((S, T, D), dtype=torch.float32, device=dev),
-        "betas": torch.empty((S, T, model.num_betas), dtype=torch.float32, device=dev),
-        "transl": torch.empty((S, T, 3), dtype=torch.float32, device=dev),
-        "loss": torch.empty((S, T), dtype=torch.float32, device=dev),
-    }
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_sequence(
-            model.handle, prior.handle, C.byref(cfg), S, T, int(followup_iters), K, _np_ptr(idx),
-            _dev(j3d, "j3d", dev, (S, T, K, 3)), conf_p,
-            _dev(global_orient, "global_orient", dev, (S, 3)), _dev(body_pose, "body_pose", dev, (S, D)),
-            _dev(betas, "betas", dev, (S, model.num_betas)), _dev(transl, "transl", dev, (S, 3)),
-            C.c_void_p(out["global_orient"].data_ptr()), C.c_void_p(out["body_pose"].data_ptr()),
-            C.c_void_p(out["betas"].data_ptr()), C.c_void_p(out["transl"].data_ptr()),
-            C.c_void_p(out["loss"].data_ptr()), stream), "k2b_fit_sequence")
-    return out
+    S, T = j3d.shape[0], j3d.shape[1]
+    return _fit_call("k2b_fit_sequence", model, prior, cfg, (S, T, int(followup_iters)),
+                     _joint_index(model_joint_index, j3d.shape[2]), (S, T), S, j3d, conf, global_orient, body_pose, betas, transl)
 
 
 def ragged_offsets(lengths) -> np.ndarray:
@@ -489,38 +429,18 @@ def ragged_offsets(lengths) -> np.ndarray:
     return out
 
 
-def _sequences_out(model: NativeModel, N: int):
-    dev = model.device
-    D = 3 * (model.num_joints - 1)
-    return {
-        "global_orient": torch.empty((N, 3), dtype=torch.float32, device=dev),
-        "body_pose": torch.empty((N, D), dtype=torch.float32, device=dev),
-        "betas": torch.empty((N, model.num_betas), dtype=torch.float32, device=dev),
-        "transl": torch.empty((N, 3), dtype=torch.float32, device=dev),
-        "loss": torch.empty((N,), dtype=torch.float32, device=dev),
-    }
-
-
-def _sequences_args(model: NativeModel, cfg: FitConfigC, model_joint_index, lengths, offsets, j3d, conf, global_orient,
-                    body_pose, betas, transl):
-    """Shared argument handling of the ragged entries: host int32 lengths / offsets, the packed device buffers checked."""
-    dev = model.device
+def _fit_sequences_call(name, model, prior, cfg, followup, model_joint_index, lengths, offsets, j3d, *params, tail=()):
+    """Shared body of the ragged entries: host int32 lengths / offsets checked against the packed frames, then the fit call
+    with (S, lengths, offsets, *`followup`) in front."""
     L = _host_i32(np.asarray(lengths).reshape(-1))
     O = ragged_offsets(L) if offsets is None else _host_i32(np.asarray(offsets).reshape(-1))
-    S, N, K = int(L.shape[0]), int(j3d.shape[0]), int(j3d.shape[1])
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
+    S, N = int(L.shape[0]), int(j3d.shape[0])
+    idx = _joint_index(model_joint_index, int(j3d.shape[1]))
     if O.shape != (S,):
         raise ValueError(f"offsets has {O.shape[0]} entries for {S} sequences")
     if S and int(L.astype(np.int64).sum()) != N and (L >= 0).all():
         raise ValueError(f"lengths sum to {int(L.astype(np.int64).sum())}, j3d has {N} frames")
-    conf_p = None if conf is None else _dev(conf, "conf", dev, (N, K) if cfg.conf_per_frame else (K,))
-    ins = (_dev(j3d, "j3d", dev, (N, K, 3)), conf_p,
-           _dev(global_orient, "global_orient", dev, (S, 3)), _dev(body_pose, "body_pose", dev, (S, D)),
-           _dev(betas, "betas", dev, (S, model.num_betas)), _dev(transl, "transl", dev, (S, 3)))
-    return L, O, S, N, K, idx, ins
+    return _fit_call(name, model, prior, cfg, (S, _np_ptr(L), _np_ptr(O), *followup), idx, (N,), S, j3d, *params, tail=tail)
 
 
 def fit_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int,
@@ -529,17 +449,8 @@ def fit_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, follo
     """Warm-start chains of different lengths side by side, Adam branch (``k2b_fit_sequences``, ONE launch): ``j3d`` packed
     (sum T, K, 3), ``lengths`` (S,), start parameters (S, ...) of every sequence's first frame; returns packed (sum T, ...)
     tensors in the caller's order.  Sequence s equals ``fit_sequence`` on it alone, bit for bit."""
-    L, O, S, N, K, idx, ins = _sequences_args(model, cfg, model_joint_index, lengths, offsets, j3d, conf, global_orient,
-                                              body_pose, betas, transl)
-    out = _sequences_out(model, N)
-    dev = model.device
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_sequences(
-            model.handle, prior.handle, C.byref(cfg), S, _np_ptr(L), _np_ptr(O), int(followup_iters), K, _np_ptr(idx), *ins,
-            *[C.c_void_p(out[k].data_ptr()) for k in ("global_orient", "body_pose", "betas", "transl", "loss")], stream),
-            "k2b_fit_sequences")
-    return out
+    return _fit_sequences_call("k2b_fit_sequences", model, prior, cfg, (int(followup_iters),), model_joint_index, lengths,
+                               offsets, j3d, conf, global_orient, body_pose, betas, transl)
 
 
 def fit_sequences_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, first_iters: int, followup_iters: int,
@@ -550,18 +461,10 @@ def fit_sequences_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC,
     """The default sequence mode (L-BFGS, warm start) for S sequences of different lengths (``k2b_fit_sequences_lbfgs``, ONE
     launch; ``NotImplementedError`` where it does not apply: SMPL-H / SMPL-X, surface targets).  Arguments and result as
     ``fit_sequences``; sequence s equals ``fit_sequence_lbfgs`` on it alone, bit for bit."""
-    L, O, S, N, K, idx, ins = _sequences_args(model, cfg, model_joint_index, lengths, offsets, j3d, conf, global_orient,
-                                              body_pose, betas, transl)
-    out = _sequences_out(model, N)
-    dev = model.device
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_fit_sequences_lbfgs(
-            model.handle, prior.handle, C.byref(cfg), S, _np_ptr(L), _np_ptr(O), K, _np_ptr(idx), *ins,
-            *[C.c_void_p(out[k].data_ptr()) for k in ("global_orient", "body_pose", "betas", "transl", "loss")],
-            int(first_iters), int(followup_iters), int(history_size), float(lr), float(tolerance_grad), float(tolerance_change),
-            stream), "k2b_fit_sequences_lbfgs")
-    return out
+    return _fit_sequences_call(
+        "k2b_fit_sequences_lbfgs", model, prior, cfg, (), model_joint_index, lengths, offsets, j3d, conf, global_orient,
+        body_pose, betas, transl,
+        tail=(int(first_iters), int(followup_iters), *_lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change)))
 
 
 def sequence_order(lengths, offsets=None) -> np.ndarray:
@@ -586,21 +489,16 @@ def shape_pass_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, se
     N, K = int(j3d.shape[0]), int(j3d.shape[1])
     S, nb = int(betas.shape[0]), int(betas.shape[1])
     D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (K,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {K} targets")
+    idx = _joint_index(model_joint_index, K)
     if not isinstance(seq_offsets, torch.Tensor) or seq_offsets.dtype != torch.int32 or seq_offsets.device != dev \
             or tuple(seq_offsets.shape) != (S + 1,) or not seq_offsets.is_contiguous():
         raise ValueError("seq_offsets must be a contiguous int32 device tensor of S + 1 entries")
     out = torch.empty((S, nb), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_shape_pass_lbfgs(
-            model.handle, prior.handle, C.byref(cfg), S, C.c_void_p(seq_offsets.data_ptr()), N, K, _np_ptr(idx),
+    _launch("k2b_shape_pass_lbfgs", dev, model.handle, prior.handle, C.byref(cfg), S, _ptr(seq_offsets), N, K, _np_ptr(idx),
             _dev(j3d, "j3d", dev, (N, K, 3)), _dev(conf, "conf", dev, (N, K)), _dev(global_orient, "global_orient", dev, (N, 3)),
             _dev(body_pose, "body_pose", dev, (N, D)), _dev(root_targets, "root_targets", dev, (N, 3)), int(root_joint), nb,
-            _dev(betas, "betas", dev, (S, nb)), C.c_void_p(out.data_ptr()), int(max_iter), int(history_size), float(lr),
-            float(tolerance_grad), float(tolerance_change), stream), "k2b_shape_pass_lbfgs")
+            _dev(betas, "betas", dev, (S, nb)), _ptr(out), int(max_iter),
+            *_lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change))
     return out
 
 
@@ -612,34 +510,29 @@ def angular_error_deg(pred_rotvec: torch.Tensor, gt_rotvec: torch.Tensor) -> tor
         raise ValueError(f"expected two (...,3) tensors of equal shape, got {tuple(pred_rotvec.shape)} and {tuple(gt_rotvec.shape)}")
     n = pred_rotvec.numel() // 3
     out = torch.empty(pred_rotvec.shape[:-1], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_angular_error_deg(n, _dev(pred_rotvec, "pred_rotvec", dev), _dev(gt_rotvec, "gt_rotvec", dev),
-                                                    C.c_void_p(out.data_ptr()) if n else None, stream), "k2b_angular_error_deg")
+    _launch("k2b_angular_error_deg", dev, n, _dev(pred_rotvec, "pred_rotvec", dev), _dev(gt_rotvec, "gt_rotvec", dev),
+            _ptr(out) if n else None)
     return out
+
+
+def _term_call(name, model: NativeModel, idx: np.ndarray, targets, conf, conf_shape, flags, sigma, joint_loss_weight, *params):
+    """Shared body of the two stand-alone joint-loss terms: loss (B,) and gradient (B, P) in the packed layout."""
+    dev, B, T = model.device, targets.shape[0], idx.shape[0]
+    ins = [_dev(targets, "targets", dev, (B, T, 3)), _dev(conf, "conf", dev, conf_shape), *flags, float(sigma),
+           float(joint_loss_weight), *_param_ptrs(model, B, *params)]
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, sum(_param_widths(model))), dtype=torch.float32, device=dev)
+    _launch(name, dev, model.handle, B, T, _np_ptr(idx), *ins, _ptr(loss), _ptr(grad))
+    return loss, grad
 
 
 def vertex_term(model: NativeModel, extra_index: Sequence[int], targets: torch.Tensor, conf: Optional[torch.Tensor],
                 sigma: float, joint_loss_weight: float, global_orient: torch.Tensor, body_pose: torch.Tensor,
                 betas: torch.Tensor, transl: torch.Tensor):
     """Loss (B,) and gradient (B, P) of the joint-loss term of vertex-selected joints (``k2b_vertex_term``)."""
-    dev = model.device
-    B, E = targets.shape[0], targets.shape[1]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(extra_index)))
-    if idx.shape != (E,):
-        raise ValueError(f"extra_index has {idx.shape[0]} entries for {E} targets")
-    loss = torch.empty((B,), dtype=torch.float32, device=dev)
-    grad = torch.empty((B, 3 + D + model.num_betas + 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_vertex_term(
-            model.handle, B, E, _np_ptr(idx), _dev(targets, "targets", dev, (B, E, 3)), _dev(conf, "conf", dev, (E,)),
-            float(sigma), float(joint_loss_weight), _dev(global_orient, "global_orient", dev, (B, 3)),
-            _dev(body_pose, "body_pose", dev, (B, D)), _dev(betas, "betas", dev, (B, model.num_betas)),
-            _dev(transl, "transl", dev, (B, 3)), C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()), stream),
-            "k2b_vertex_term")
-    return loss, grad
+    E = targets.shape[1]
+    return _term_call("k2b_vertex_term", model, _joint_index(extra_index, E, "extra_index"), targets, conf, (E,), (),
+                      sigma, joint_loss_weight, global_orient, body_pose, betas, transl)
 
 
 def surface_term(model: NativeModel, model_joint_index: Sequence[int], targets: torch.Tensor, conf: Optional[torch.Tensor],
@@ -647,25 +540,11 @@ def surface_term(model: NativeModel, model_joint_index: Sequence[int], targets: 
                  betas: torch.Tensor, transl: torch.Tensor):
     """Loss (B,) and gradient (B, P) of the joint-loss term of surface targets - extra joints and landmarks, given as model
     joint indices in [J, J+E+L) - (``k2b_surface_term``).  `conf`: (T,), (B, T) per frame, or None."""
-    dev = model.device
     B, T = targets.shape[0], targets.shape[1]
-    D = 3 * (model.num_joints - 1)
-    idx = _host_i32(np.asarray(list(model_joint_index)))
-    if idx.shape != (T,):
-        raise ValueError(f"model_joint_index has {idx.shape[0]} entries for {T} targets")
     per_frame = conf is not None and conf.dim() == 2
-    loss = torch.empty((B,), dtype=torch.float32, device=dev)
-    grad = torch.empty((B, 3 + D + model.num_betas + 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_surface_term(
-            model.handle, B, T, _np_ptr(idx), _dev(targets, "targets", dev, (B, T, 3)),
-            _dev(conf, "conf", dev, (B, T) if per_frame else (T,)), 1 if per_frame else 0,
-            float(sigma), float(joint_loss_weight), _dev(global_orient, "global_orient", dev, (B, 3)),
-            _dev(body_pose, "body_pose", dev, (B, D)), _dev(betas, "betas", dev, (B, model.num_betas)),
-            _dev(transl, "transl", dev, (B, 3)), C.c_void_p(loss.data_ptr()), C.c_void_p(grad.data_ptr()), stream),
-            "k2b_surface_term")
-    return loss, grad
+    return _term_call("k2b_surface_term", model, _joint_index(model_joint_index, T), targets, conf,
+                      (B, T) if per_frame else (T,), (1 if per_frame else 0,), sigma, joint_loss_weight,
+                      global_orient, body_pose, betas, transl)
 
 
 def adam_step(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, step_size: float,
@@ -676,16 +555,15 @@ def adam_step(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torc
     for name, t in (("grad", grad), ("m", m), ("v", v)):
         if t.numel() != n:
             raise ValueError(f"{name} has {t.numel()} elements, params {n}")
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _check(load_library().k2b_adam_step(n, _dev(params, "params", dev), _dev(grad, "grad", dev), _dev(m, "m", dev),
-                                            _dev(v, "v", dev), int(step), float(step_size), float(beta1), float(beta2),
-                                            float(eps), stream), "k2b_adam_step")
+    _launch("k2b_adam_step", dev, n, _dev(params, "params", dev), _dev(grad, "grad", dev), _dev(m, "m", dev), _dev(v, "v", dev),
+            int(step), float(step_size), float(beta1), float(beta2), float(eps))
 
 
-class NativeIkgat:
+class NativeIkgat(_Handle):
     """Owner of a ``k2b_ikgat`` handle: the IK-GAT regressor's packed weights and graph in HBM
     (layout: ``include/k2b.h``, ``k2b_ikgat_create``)."""
+
+    _destroy = "k2b_ikgat_destroy"
 
     def __init__(self, parents, weights, input_dim: int, hidden_dim: int, num_layers: int, num_heads: int, device=None):
         self.device = require_device(device)
@@ -716,16 +594,5 @@ class NativeIkgat:
                 raise ValueError(f"quat_in has shape {tuple(quat_in.shape)}, expected ({T}, {J}, 4)"
                                  + (" or (1, J, 4) in chain mode" if chain else ""))
         out = torch.empty((T, J, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _check(load_library().k2b_ikgat_predict(self._h, T, pos, q, 1 if chain else 0, C.c_void_p(out.data_ptr()), stream),
-                   "k2b_ikgat_predict")
+        _launch("k2b_ikgat_predict", dev, self._h, T, pos, q, 1 if chain else 0, _ptr(out))
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value and _lib is not None:
-                _lib.k2b_ikgat_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass

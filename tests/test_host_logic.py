@@ -77,6 +77,42 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.k2b_version() >> 16 == 1
 
 
+def test_ctypes_prototypes_match_header_argument_by_argument():
+    """Every ``k2b_*(...)`` declaration of include/k2b.h against the ctypes prototype of the same symbol: the number of
+    arguments and each argument's kind (pointer = the declaration has a ``*``, else its scalar type), and the kind of the
+    result.  A prototype that drifts from the header would pass garbage through the ABI without any error."""
+    header = re.sub(r"/\*.*?\*/", " ", (REPO / "include" / "k2b.h").read_text(), flags=re.S)
+    decls = re.findall(r"([\w \*]+?)\b(k2b_[a-z_]+)\s*\(([^()]*)\)\s*;", header)
+    assert len(decls) == 30 and len({name for _, name, _ in decls}) == 30
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+    results = {"void": None, "int": ctypes.c_int, "uint32_t": ctypes.c_uint32, "const char *": ctypes.c_char_p}
+
+    def header_kind(text):
+        if "*" in text:
+            return "pointer"
+        (kind,) = [k for k in scalars if re.search(rf"\b{k}\b", text)]
+        return kind
+
+    def ctypes_kind(t):
+        if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+            return "pointer"
+        (kind,) = [k for k, c in scalars.items() if c is t]
+        return kind
+
+    lib = native.load_library()
+    for result, name, args in decls:
+        fn = getattr(lib, name)
+        want = [] if args.strip() == "void" else [header_kind(a) for a in args.split(",")]
+        got = [ctypes_kind(t) for t in (fn.argtypes or ())]
+        assert got == want, f"{name}: header {want}, ctypes {got}"
+        assert fn.restype is results[result.strip()], name
+    for name in ("k2b_version", "k2b_last_error", "k2b_fit_config_size"):
+        assert not getattr(lib, name).argtypes, name
+    assert {n: len(getattr(lib, n).argtypes) for n in ("k2b_fit_world", "k2b_fit_sequence", "k2b_fit_world_lbfgs",
+                                                        "k2b_shape_pass_lbfgs")} == {
+        "k2b_fit_world": 21, "k2b_fit_sequence": 20, "k2b_fit_world_lbfgs": 26, "k2b_shape_pass_lbfgs": 23}
+
+
 def test_header_is_plain_c_and_struct_size_matches(tmp_path):
     """include/k2b.h is the drop-in boundary: it must compile as C99 and as C++ with nothing but the
     standard headers, and sizeof(k2b_fit_config) seen by a C compiler must equal what the library and the
