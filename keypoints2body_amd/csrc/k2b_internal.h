@@ -206,9 +206,18 @@ struct TileArgs {
     int num_wgs;                 // grid size (a multiple of 8), set by the launcher
 };
 hipError_t launch_skin_tiles(const TileArgs& a, int num_cus, hipStream_t stream);
+// grid of the persistent vertex kernels: one workgroup per CU, a multiple of the 8 XCD labels, no more than the tiles need
+inline int persistent_grid(int num_cus, long long tiles) {
+    const int wgs = num_cus < 8 ? 8 : num_cus / 8 * 8;
+    return tiles < wgs ? (int)((tiles + 7) / 8 * 8) : wgs;
+}
 
-// ---- stream kernel (k2b_lbs_stream.hip): the same tile for 17-24 joints and 7 pose k-steps, Pd global -> registers ------------
-// Operands (1 KiB pieces = 64 lanes x 8 halfs in v_mfma_f32_16x16x32_f16 operand order: lane = row + 16 k-group):
+// ---- stream kernels (k2b_lbs_stream.hip): the same tile, Pd global -> registers -------------------------------------------------
+// One kernel body (stream_body<S>) behind two entry points, one description S each; the descriptions hold what differs (pose
+// k-steps, X resident or in a ring, fragment counts and products, the counted-wait tables) and live in k2b_lbs_stream.hip.
+//   k2b_lbs_stream_kernel    17-24 joints, 7 pose k-steps (SMPL)               launch_skin_stream
+//   k2b_lbs_stream_x_kernel  49-56 joints, 16 pose k-steps (SMPL-H / SMPL-X)   launch_skin_stream_x
+// Operands (1 KiB pieces = 64 lanes x 8 halfs in v_mfma_f32_16x16x32_f16 operand order: lane = row + 16 k-group), SMPL:
 //   X   as for the tile kernel
 //   A   [16-frame tile][entry 12][fragment 2]: fragment 0 = k-groups hi_0 hi_1 hi_2 PAD, fragment 1 = lo_0 lo_1 lo_2 ZERO
 //       (the pose set-up writes this group order with PoseArgs::a2_stream_order)
@@ -228,7 +237,7 @@ struct StreamArgs {
     int num_wgs;
 };
 hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stream);
-// 49-56 joints and 16 pose k-steps (SMPL-X), k2b_lbs_stream_x_kernel: the same operands with
+// SMPL-X: the same operands with
 //   A   [16-frame tile][entry 12][fragment 4]: hi_0-3 | hi_4-6 PAD | lo_0-3 | lo_4-6 ZERO   (a2_stream_order with GA = 7)
 //   Pd  [k-step 16][16-vertex tile][coordinate 3][hi | lo]
 //   W   [16-vertex tile][5]: hi_0-3, [hi_4-6 | ONES], lo_0-3, [lo_4-6 | 0], [hi_4-6 | tag]

@@ -27,11 +27,9 @@
 #include <hip/hip_fp16.h>
 
 #include "k2b_internal.h"
+#include "k2b_lbs_device.h"
 
 namespace k2b {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-struct __attribute__((packed, aligned(4))) float3v { float x, y, z; };
 
 __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
     hi = (_Float16)x;
@@ -246,44 +244,22 @@ constexpr int kFragHalfs = 512;      // one piece = 64 lanes x 8 halfs = 1 KiB
 // v_posed (which die tile by tile), so the three coordinates of a (frame, vertex) pair meet in registers and leave as ONE
 // 12-byte store - no LDS parking, no spills.  Bytes into LDS per 32 x 32 sub-tile: 41 KiB (128 x 64 kernel: 60 KiB).
 // ---------------------------------------------------------------------------------------------
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int kTileSlotBytes = 64 * 1024;
 #ifndef K2B_TILE_AHEAD
 #define K2B_TILE_AHEAD(NKT) ((NKT) <= 3)
 #endif
 #ifndef K2B_TILE_CHUNK
-#define K2B_TILE_CHUNK 8      // frame groups per L2 chunk of the tile walk
+#define K2B_TILE_CHUNK 8      // frame groups per L2 chunk of the tile walk (Walk, k2b_lbs_device.h)
 #endif
 
-
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_barrier" ::: "memory"); }
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// the tiles of one workgroup: XCD label x = block % 8 owns a contiguous range of (frame chunk, vertex group) items,
-// a chunk = 8 frame groups (1024 frames: their per-frame operands, 2.3 MB, stay in the XCD's L2 while the vertex
-// groups stream past); inside the range the frame group runs fastest, the XCD's workgroups take every nx-th tile.
-struct TileWalk {
-    int vgroups, fgroups, item_lo, item_hi, nx;
-    int t;                      // index into the XCD's tile sequence (item-major, 8 frame slots per item)
-    int fg, vg;
+// the tile walk with its cursor inside: the kernel keeps two, the loader's one slice ahead of the consumer's (each set up on
+// its own, as before; an exhausted cursor is only marked: fg, vg mean nothing then)
+struct TileCursor : Walk<K2B_TILE_CHUNK> {
+    int t, fg, vg;
     bool valid;
-    __device__ void init(const TileArgs& a, int block, int nblocks) {
-        vgroups = (a.v_tiles + 3) >> 2; fgroups = (a.f_tiles + 3) >> 2;
-        const int items = ((fgroups + K2B_TILE_CHUNK - 1) / K2B_TILE_CHUNK) * vgroups, x = block & 7;
-        item_lo = (int)((long long)items * x / 8); item_hi = (int)((long long)items * (x + 1) / 8);
-        nx = nblocks >> 3;
-        t = (block >> 3) - nx;
-        next();
-    }
     __device__ void next() {
-        for (;;) {
-            t += nx;
-            const int item = item_lo + t / K2B_TILE_CHUNK;
-            if (item >= item_hi) { valid = false; return; }
-            const int c = item / vgroups;
-            fg = c * K2B_TILE_CHUNK + t % K2B_TILE_CHUNK; vg = item - c * vgroups;
-            if (fg < fgroups) { valid = true; return; }
-        }
+        valid = true;
+        Walk::next(t, fg, vg, [&] { valid = false; });
     }
 };
 
@@ -329,8 +305,9 @@ __global__ __launch_bounds__(512) void k2b_lbs_tile_kernel(const TileArgs a) {
     // The source of every piece is  base pointer + 32-bit element offset + lane x 16 B.  What depends on the wave only is
     // worked out once, what depends on the tile once per tile; per slice a piece costs an add or two (the first version
     // redid the whole index arithmetic, divisions included, per piece: 900 cycles of scalar work per slice and wave).
-    TileWalk lw;
-    lw.init(a, blockIdx.x, a.num_wgs);
+    TileCursor lw;
+    lw.t = lw.init((a.v_tiles + 3) >> 2, (a.f_tiles + 3) >> 2, blockIdx.x, a.num_wgs);
+    lw.next();
     int ls = 0;                   // slice of the loader's tile to issue next
     int lq = 0;                   // global slice counter of the loader (slot = lq & 1)
     const int spt = KX + 4 * NTS; // slices per tile
@@ -386,8 +363,9 @@ __global__ __launch_bounds__(512) void k2b_lbs_tile_kernel(const TileArgs a) {
     };
 
     // ---- consumer ------------------------------------------------------------------------------------------------
-    TileWalk cw;
-    cw.init(a, blockIdx.x, a.num_wgs);
+    TileCursor cw;
+    cw.t = cw.init((a.v_tiles + 3) >> 2, (a.f_tiles + 3) >> 2, blockIdx.x, a.num_wgs);
+    cw.next();
     if (!cw.valid) return;        // whole workgroup: no tile
     int q = 0;                    // global slice counter of the consumer
     if (loader) issue();
@@ -660,10 +638,7 @@ hipError_t launch_skin_tiles(const TileArgs& a_in, int num_cus, hipStream_t stre
     if (a_in.num_frames <= 0 || a_in.num_out <= 0) return hipSuccess;
     TileArgs a = a_in;
     const int vgroups = (a.v_tiles + 3) / 4, fgroups = (a.f_tiles + 3) / 4;
-    const long long tiles = (long long)vgroups * fgroups;
-    int wgs = num_cus < 8 ? 8 : num_cus / 8 * 8;           // one persistent workgroup per CU, a multiple of the 8 XCD labels
-    if (tiles < wgs) wgs = (int)((tiles + 7) / 8 * 8);
-    a.num_wgs = wgs;
+    const int wgs = a.num_wgs = persistent_grid(num_cus, (long long)vgroups * fgroups);
     const int GA = a.groups_a;
     const size_t lds = (size_t)2 * kTileSlotBytes + (size_t)8 * tile_ngp(GA) * 256;
     if (a.k_steps_x & 1) return hipErrorInvalidValue;

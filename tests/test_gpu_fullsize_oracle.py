@@ -2,13 +2,14 @@
 
 * LBS (reference seam: the final forward of ``core/fitters/world_space.py:258-278``): 4096 and 10 000 SMPL frames through the
   stream kernel (its full-tile fast path, the counted ``vmcnt`` waits and the XCD walk over 32 / 79 frame groups x 54 vertex
-  groups) and 1024 SMPL-X frames through the tile kernel ``<7, 6>``, random LARGE rotations; vertices and all output joints of
+  groups) and 1024 SMPL-X frames through the SMPL-X stream kernel, random LARGE rotations; vertices and all output joints of
   >= 128 sampled frames spread over the first / middle / last frame groups against ``TorchSMPL`` / ``TorchSMPLX`` at
   5e-6 x scale.
 * Fit (``world_space.py:248-256``): 64 sampled frames of the 4096-frame bench problem (paired shape) and of the 1024-frame one
   (split shape) against ``oracle.fit_torch.fit_world_adam`` on exactly those frames, 100 iterations, at the north star's 1e-4.
-* Partial tiles of the stream kernel: batches with B % 128 in 1..15 and joints-only calls, where whole waves
+* Partial tiles of the stream kernels: batches with B % 128 in 1..15 and joints-only calls, where whole waves
   have no store to issue, under HBM pressure from a concurrent copy - results must equal the quiet run bit for bit and the oracle.
+  SMPL and SMPL-X: both kernels take their partial-tile wait counts from the same generic body.
 """
 import numpy as np
 import pytest
@@ -134,4 +135,39 @@ def test_stream_kernel_partial_tiles_under_memory_pressure(B):
         j, v = m.lbs(*args)
         jo, _ = m.lbs(*args, want_vertices=False)
         assert torch.equal(v, v_quiet) and torch.equal(j, j_quiet) and torch.equal(jo, j_quiet)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("B", [1, 15, 128 + 9])
+def test_stream_x_kernel_partial_tiles_under_memory_pressure(B):
+    """The same for the SMPL-X kernel, whose partial-tile wait counts come out of the same body: a tile whose waves mostly have
+    nothing to store (B = 1), the last frame of a 16-frame unit (15), a second tile with a partial frame group (137).  Full and
+    joints-only calls against the oracle when quiet, then bit-equal to their quiet results beside the saturating copy.  (That
+    the joints-only call equals the full call bit for bit has not been established for SMPL-X and is not asserted.)"""
+    from tests.test_gpu_smplx import POSE_FIELDS
+    p = synthetic.make_poses_x(B, seed=60 + B)
+    fields = ("global_orient",) + tuple(k for k, _ in POSE_FIELDS) + ("betas", "expression", "transl")
+    with torch.no_grad():
+        want = H.oracle_model_x()(**{k: torch.tensor(np.asarray(getattr(p, k))) for k in fields})
+    pose = np.concatenate([getattr(p, k) for k, _ in POSE_FIELDS], axis=1)
+    shape = np.concatenate([p.betas, p.expression], axis=1)
+    m = H.native_model_x()
+    args = (H.cuda(p.global_orient), H.cuda(pose), H.cuda(shape), H.cuda(p.transl))
+    scale = max(1.0, float(want.vertices.abs().max()))
+    j_quiet, v_quiet = m.lbs(*args)
+    jo_quiet, _ = m.lbs(*args, want_vertices=False)
+    assert (v_quiet.cpu() - want.vertices).abs().max().item() < LBS_TOL * scale
+    assert (j_quiet.cpu() - want.joints).abs().max().item() < LBS_TOL * scale
+    assert (jo_quiet.cpu() - want.joints).abs().max().item() < LBS_TOL * scale
+    side = torch.cuda.Stream()
+    src = torch.empty(256 << 20, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for _ in range(12):
+            dst.copy_(src, non_blocking=True)
+    for _ in range(6):
+        j, v = m.lbs(*args)
+        jo, _ = m.lbs(*args, want_vertices=False)
+        assert torch.equal(v, v_quiet) and torch.equal(j, j_quiet) and torch.equal(jo, jo_quiet)
     torch.cuda.synchronize()
