@@ -112,6 +112,22 @@ __device__ __forceinline__ float group8_wave_min(float v) {
     return r;
 }
 
+// group8_wave_min for TWO values at once (the two frames of a row wave of the 16-wave shape): after the step inside the rows the
+// two registers trade rows with ONE v_permlane16_swap - even rows then carry the first value's row pair, odd rows the second's -
+// so that both minima ride through the remaining steps in one register (9 vector instructions against 14, one no-op per swap
+// instead of one per swap and frame).  A minimum does not depend on the order of its operands: the same values as group8_wave_min.
+__device__ __forceinline__ void group8_wave_min2(float v0, float v1, float& r0, float& r1) {
+    float a, b;
+    asm("s_nop 1\n\tv_min_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_min_f32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xf" : "=&v"(a), "=&v"(b) : "v"(v0), "v"(v1));
+    swap16(a, b);                     // a: rows 0, 2 of the first | rows 0, 2 of the second; b: rows 1, 3 of both
+    float m = vmin(a, b), t = m;      // even rows: the first value over its row pair; odd rows: the second
+    swap32(m, t);                     // m: rows 0, 1 twice; t: rows 2, 3 twice
+    m = vmin(m, t);                   // every even row: wave-wide minimum of the first value; every odd row: of the second
+    r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 0));
+    r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 16));
+}
+
 // sum over the 32-lane half of the lane
 __device__ __forceinline__ float half_sum_fast(float v) {
     v = pair_sum16(v);
@@ -141,32 +157,6 @@ __device__ __forceinline__ float butterfly8(const float (&v)[8], int lane) {
     }
     const float s0 = u[0] + lane_xor8(u[0]), s1 = u[1] + lane_xor8(u[1]);
     return (lane & 8) ? s1 : s0;
-}
-
-// 16 per-lane values -> lane l ends with the sum over ITS 32-lane half of v[k],
-// k = 8 bit4(l) + 4 bit3(l) + 2 bit2(l) + bit1(l).
-__device__ __forceinline__ float butterfly16_half_sum(const float (&v)[16], int lane) {
-    float w8[8], w4[4], w2[2];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float a = v[i], b = v[8 + i];
-        swap16(a, b);
-        w8[i] = a + b;             // even 16-lane rows: v[i] over the row pair; odd rows: v[8 + i]
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float s0 = w8[i] + lane_xor8(w8[i]), s1 = w8[4 + i] + lane_xor8(w8[4 + i]);
-        w4[i] = (lane & 8) ? s1 : s0;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float t0 = w4[i] + lane_xor4(w4[i]), t1 = w4[2 + i] + lane_xor4(w4[2 + i]);
-        w2[i] = (lane & 4) ? t1 : t0;
-    }
-    const float u0 = w2[0] + lane_xor2(w2[0]), u1 = w2[1] + lane_xor2(w2[1]);
-    float r = (lane & 2) ? u1 : u0;
-    r += lane_xor1(r);
-    return r;
 }
 
 }  // namespace
@@ -402,7 +392,13 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         }
     };
     const int jj = isJ ? joint : 0;
-    const int thoff = jj == 0 ? 0 : XS_BODY + 3 * (jj - 1);
+    // d/d beta: the value this lane ends with in the tree pass's reduction, and whether it is the lane that stores it
+    const int gk = PAIR ? butterfly_half_index<NBT>(lane) : lane >> 2;
+    const bool gk_store = (lane & (PAIR ? 1 : 3)) == 0 && gk >= 0 && gk < NB;
+    // (a lane beyond the tree reads the three floats behind body_pose, which nobody writes after the strips are cleared: its
+    //  rotation vector is an exact zero without a select per pass)
+    static_assert(XS_BODY + D + 3 <= XS_BETA, "three unused floats behind body_pose");
+    const int thoff = !isJ ? XS_BODY + D : (jj == 0 ? 0 : XS_BODY + 3 * (jj - 1));
 
     // targets: the lane of joint j holds the target of that joint (or none)
     const int tk = isJ ? a.lane_target[jj] : -1;
@@ -663,7 +659,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             }
             dj = {e[0], e[1], e[2]};
         }
-        const Rodrigues rod = rodrigues_fwd(isJ ? th : Vec3{0.f, 0.f, 0.f});
+        const Rodrigues rod = rodrigues_fwd(th);           // (beyond the tree th is zero: thoff)
         // ---- pointer-doubling down-sweep: after round r a lane is composed with 2^(r+1) ancestors ----
         Mat3 Rg = rod.R;                   // becomes the global rotation
         Vec3 pj = dj;                      // becomes the posed joint (without transl)
@@ -708,14 +704,19 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             const float lo[3] = {gj.x, gj.y, gj.z};
             const float hi[3] = {pxg.x, pxg.y, pxg.z};
             if (PAIR) {
-                // both halves carry a tree: six scans
+                // both halves carry a tree: six scans, three at a time side by side
+                int zlo = 0, zhi = 0;
 #pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const float v = i < 3 ? lo[i] : hi[i - 3];
-                    const double scan = half_wave_inclusive_scan(v);
-                    const double hi_end = bperm64(sub_end_addr, scan);  // prefix at the last lane of the subtree
-                    const double lo_end = scan - (double)v;             // prefix just before its first lane (this lane)
-                    sums[i] = (float)(hi_end - lo_end);                 // (lanes beyond the tree: window = the lane itself, an exact zero)
+                for (int g = 0; g < 2; ++g) {
+                    const float v3[3] = {g ? hi[0] : lo[0], g ? hi[1] : lo[1], g ? hi[2] : lo[2]};
+                    double scan[3];
+                    half_wave_inclusive_scans(v3, scan, zlo, zhi);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double hi_end = bperm64(sub_end_addr, scan[i]);  // prefix at the last lane of the subtree
+                        const double lo_end = scan[i] - (double)v3[i];         // prefix just before its first lane (this lane)
+                        sums[3 * g + i] = (float)(hi_end - lo_end);            // (lanes beyond the tree: window = the lane itself, an exact zero)
+                    }
                 }
             } else {
                 // the two triples ride in the two 32-lane halves (g in lanes t, p x g in lanes 32 + t): three scans
@@ -762,26 +763,31 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             const Vec3 uxw = cross(rod.u, w);
             gth = {a1 * w.x + a2uw * rod.u.x - a3 * uxw.x, a1 * w.y + a2uw * rod.u.y - a3 * uxw.y, a1 * w.z + a2uw * rod.u.z - a3 * uxw.z};
         }
-        float gb[16];
+        float gb[NBT];
         {
             float dd[4 * DDQ];
             read_dd(dd);
             const Vec3 gz = {isJ ? gd.x : 0.f, isJ ? gd.y : 0.f, isJ ? gd.z : 0.f};     // one select per component instead of one per beta
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int kk = k < NBT ? k : 0;
-                gb[k] = k < NBT ? gz.x * dd[kk] + gz.y * dd[NBT + kk] + gz.z * dd[2 * NBT + kk] : 0.f;
-            }
+            for (int k = 0; k < NBT; ++k) gb[k] = gz.x * dd[k] + gz.y * dd[NBT + k] + gz.z * dd[2 * NBT + k];
         }
-        // d joint-loss / d beta_k summed over the tree; which lane ends up with which k: see the helpers
-        const float gbeta = PAIR ? butterfly16_half_sum(gb, lane) : butterfly16_sum(gb, lane);
-        const int gk = PAIR ? (((lane >> 4) & 1) << 3 | ((lane >> 3) & 1) << 2 | ((lane >> 2) & 1) << 1 | ((lane >> 1) & 1)) : (lane >> 2);
-        const bool gk_writer = PAIR ? (lane & 1) == 0 : (lane & 3) == 0;
+        // d joint-loss / d beta_k summed over the tree; which lane ends up with which k: gk above.  Two trees per wave: the reduction
+        // sized by NBT.  One tree per wave (<= 4 frames per CU, bound by this wave's latency, not by issue): the 16-value form - the
+        // sized one with its grouped swaps measured 1.5 % SLOWER there ("Rejected"; profiles/wide_diet_ab.txt run 1)
+        float gbeta;
+        if constexpr (PAIR) {
+            gbeta = butterfly_half_sum<NBT>(gb, lane);
+        } else {
+            float g16[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) g16[k] = k < NBT ? gb[k < NBT ? k : 0] : 0.f;
+            gbeta = butterfly16_sum(g16, lane);
+        }
 
         // ---- f. tree layout -> gradient strip ---------------------------------------------------------
         const float jloss = last ? (PAIR ? half_sum_fast(part) : wave_sum_fast(part)) : 0.f;
         if (isJ) { gs_t[thoff] = gth.x; gs_t[thoff + 1] = gth.y; gs_t[thoff + 2] = gth.z; }
-        if (gk_writer && gk < NB) gs_t[XS_BETA + gk] = gbeta;
+        if (gk_store) gs_t[XS_BETA + gk] = gbeta;
         // the root's subtree is the whole tree: its force sum is d/d transl
         if (tl == 0) { gs_t[XS_TRANSL] = aj.x; gs_t[XS_TRANSL + 1] = aj.y; gs_t[XS_TRANSL + 2] = aj.z; gs_t[XS - 1] = jloss; }
     };
@@ -1139,46 +1145,47 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             // per-lane rim constants (P_BB row, c_B, P_BA mu_A, mu_B): two 16-byte LDS reads per iteration, for both frames
             const float4 rc0 = *reinterpret_cast<const float4*>(rcl + lane * 8), rc1 = *reinterpret_cast<const float4*>(rcl + lane * 8 + 4);
             // (both frames unconditionally - a wave's second slot beyond the workgroup's frames reads strips nobody wrote and its
-            //  results are dropped below: without the branch the two frames' chains of LDS round trips interleave, 4096 frames
-            //  0.3610 against 0.3680 ms; hoisting the reads and terms that do not hang on the meeting above it, or dropping the same
-            //  branch from the Adam and publish loops, adds nothing)
+            //  results are dropped below: the two frames' chains of LDS round trips interleave and share one arg-min reduction)
+            float yA[2] = {0.f, 0.f};
+            if (use_gmm) {
+                // (the two frames side by side in one block: their values, ONE arg-min reduction for both, their rows of y)
+                float4 t64[2];
+                float t68[2], yBv[2], val[2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#ifdef K2B_WIDE_PRIORS_BRANCH
-                if (slot0 + h >= F) continue;      // (A/B build: the form before this change)
-#endif
-                const int slot = slot0 + h;
-                const float* xs = slots + slot * SLOT;
-                float yA = 0.f, best = 0.f;
-                if (use_gmm) {
-                    const float4 t64 = *reinterpret_cast<const float4*>(xs + XS_BODY + NC);
-                    const float t68 = xs[XS_BODY + NC + 4];
-                    float yBv, qrim;
-                    {
-                        const float wm = wx[slot * 64 + lane], tB = xs[tBoff];
-                        const float vB = rc0.x * t64.x + rc0.y * t64.y + rc0.z * t64.z + rc0.w * t64.w + rc1.x * t68;
-                        const float y = wm + vB - rc1.y;
-                        const float term = tB * (wm - rc1.z) + (tB - rc1.w) * y;
-                        yBv = gs < NR ? y : 0.f;
-                        qrim = group8_sum(gs < NR ? term : 0.f);
-                    }
+                for (int h = 0; h < 2; ++h) {
+                    const int slot = slot0 + h;
+                    const float* xs = slots + slot * SLOT;
+                    t64[h] = *reinterpret_cast<const float4*>(xs + XS_BODY + NC);
+                    t68[h] = xs[XS_BODY + NC + 4];
+                    const float wm = wx[slot * 64 + lane], tB = xs[tBoff];
+                    const float vB = rc0.x * t64[h].x + rc0.y * t64[h].y + rc0.z * t64[h].z + rc0.w * t64[h].w + rc1.x * t68[h];
+                    const float y = wm + vB - rc1.y;
+                    const float term = tB * (wm - rc1.z) + (tB - rc1.w) * y;
+                    yBv[h] = gs < NR ? y : 0.f;
+                    const float qrim = group8_sum(gs < NR ? term : 0.f);
                     const float q = qrim + qx[slot * MG + gm];
-                    float val = 0.5f * q + a.neg_log_nllw[gm < M ? gm : 0];
-                    val = gm < M ? val : __builtin_inff();
-                    best = group8_wave_min(val);
-                    const unsigned long long hit = __builtin_amdgcn_ballot_w64(val == best);
+                    const float v = 0.5f * q + a.neg_log_nllw[gm < M ? gm : 0];
+                    val[h] = gm < M ? v : __builtin_inff();
+                }
+                group8_wave_min2(val[0], val[1], bestv[0], bestv[1]);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int slot = slot0 + h;
+                    const unsigned long long hit = __builtin_amdgcn_ballot_w64(val[h] == bestv[h]);
                     const int mstar = hit ? (int)(__builtin_ctzll(hit) >> 3) : 0;
-                    yA = yx[slot * YX_STRIDE + mstar * NC + lane];
+                    yA[h] = yx[slot * YX_STRIDE + mstar * NC + lane];
                     const float* rimf = lds + mstar * (NR * NC) + lane;
-                    yA += rimf[0 * NC] * t64.x + rimf[1 * NC] * t64.y + rimf[2 * NC] * t64.z + rimf[3 * NC] * t64.w + rimf[4 * NC] * t68;
-                    const float yb = bperm((8 * mstar + (kq < NR ? kq : 0)) * 4, yBv);      // rows 64 + kq, for both halves
+                    yA[h] += rimf[0 * NC] * t64[h].x + rimf[1 * NC] * t64[h].y + rimf[2 * NC] * t64[h].z + rimf[3 * NC] * t64[h].w + rimf[4 * NC] * t68[h];
+                    const float yb = bperm((8 * mstar + (kq < NR ? kq : 0)) * 4, yBv[h]);      // rows 64 + kq, for both halves
                     yQ = hq == h ? yb : yQ;
                 }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
                 const float dA = xa[h] - pra[h];
                 const float eA = __expf(xa[h] * angA);
-                gpa[h] = wpp2 * yA + 2.f * wpr2 * dA + (wa2 * 2.f * angA) * (eA * eA);
+                gpa[h] = wpp2 * yA[h] + 2.f * wpr2 * dA + (wa2 * 2.f * angA) * (eA * eA);
                 if (last) lossp[h] = wpr2 * dA * dA + (angA != 0.f ? wa2 * eA * eA : 0.f);
-                bestv[h] = best;
             }
             const float dQ = xq - refQ;
             const float gpq = cyQ * yQ + 2.f * cqQ * dQ;
