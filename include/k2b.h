@@ -230,7 +230,10 @@ int k2b_fit_sequence(const k2b_model *model, const k2b_prior *prior, const k2b_f
  * of the closure's launch), two launches per round beyond that and for the larger models; the result does not depend on which.  Arguments as k2b_fit_world; preserve_pose / transl_prior_target NULL = the initial body pose /
  * translation; *_out may alias *_in; loss_out dev [B] and grad_out dev [B][3 + 3(J-1) + NB + 3] (either may be NULL) receive
  * loss and gradient AT the result.  Frames never interact (torch couples the frames of a batch in one line search; the
- * reference only ever passes one frame).  At most 192 parameters per frame.
+ * reference only ever passes one frame).  At most 256 parameters per frame (3 + 3(J-1) + NB + 3): every model the fit
+ * kernels take (63 joints and 32 shape coefficients are 224); beyond 192 the optimiser's step kernel runs in its wide form.
+ * NOTE: k2b_lbs does not skin such a model - it stages at most 512 features (9(J-1) + NB + 2), i.e. a 55-joint model with at
+ * most 24 shape coefficients - so a caller gets fitted parameters for it from this entry, but no vertices / joints from k2b_lbs.
  * Line searches branch on rounding, so results agree with torch's statistically (and iterate by iterate with the float64
  * twin core/lbfgs_batched.py while rounding has not yet been amplified): see DESIGN.md.
  * ------------------------------------------------------------------------------- */

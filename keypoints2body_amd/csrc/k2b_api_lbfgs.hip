@@ -16,6 +16,17 @@ int lbfgs_scheme() {
     return scheme;
 }
 
+// development switch K2B_LBFGS_STAGE_PAIRS: at most that many history pairs of a frame are staged in LDS by the step kernel (0:
+// none; every pair of the two-loop recursion then comes from global memory), and the fit takes the step kernel - two launches per
+// round, no persistent chain.  Read on EVERY call (a test changes it in-process).  Staging only changes where the same floats
+// are read from: the results do not change by a bit (tests/test_gpu_lbfgs_wide.py).  Unset or empty: no cap (-1).
+int lbfgs_stage_cap() {
+    const char* e = getenv("K2B_LBFGS_STAGE_PAIRS");
+    if (!e || !*e) return -1;
+    const int v = atoi(e);
+    return v < 0 ? -1 : v;
+}
+
 // Workspace of the optimiser: its state, then two closure-result buffers (the fused rounds alternate).
 struct LbfgsWs { unsigned char* base; size_t off_si, off_sv, n_state, n_res; float *gbuf, *lbuf, *gbuf2, *lbuf2; bool state_cleared; };   // (state_cleared: the caller did)
 size_t lbfgs_ws_layout(int B, int P, int H, LbfgsWs* w) {
@@ -77,7 +88,8 @@ int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_conf
     // [finalise | closure] with the caller's outputs.  Two result buffers alternate (a launch reads the one its predecessor
     // wrote while writing the other).  Otherwise two launches per round.
     const int frames_per_cu = (B + device_cus() - 1) / device_cus();
-    const bool fused = lbfgs_scheme() != 1 && frames_per_cu <= 4 && fused_eligibility(model, prior, cfg).fused &&
+    const int stage_cap = lbfgs_stage_cap();
+    const bool fused = stage_cap < 0 && lbfgs_scheme() != 1 && frames_per_cu <= 4 && fused_eligibility(model, prior, cfg).fused &&
                        kinematic_only(model, at.K, at.model_joint_index);
     if (fused) {
         // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
@@ -101,10 +113,10 @@ int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_conf
     }
     for (int r = 0; r < rounds; ++r) {
         if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
-        HIP_TRY(k2b::launch_lbfgs_step(la, stream));
+        HIP_TRY(k2b::launch_lbfgs_step(la, stream, stage_cap));
     }
     la.finalize = 1;
-    HIP_TRY(k2b::launch_lbfgs_step(la, stream));
+    HIP_TRY(k2b::launch_lbfgs_step(la, stream, stage_cap));
     // loss (and gradient) at the result (world_space.py:245-246 evaluates the loss once more behind the optimiser)
     return closure(at.loss_out ? at.loss_out : w.lbuf, at.grad_out);
 }
@@ -117,8 +129,8 @@ int lbfgs_check(const k2b_model* model, const k2b_prior* prior, const k2b_fit_co
     if (*history_size > k2b::kLbfgsMaxHistory)
         return fail(K2B_ERR_UNSUPPORTED, "%s: history_size=%d (at most %d)", who, *history_size, k2b::kLbfgsMaxHistory);
     if (!(lr > 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lr must be positive", who);
-    if (3 + 3 * (model->J - 1) + model->NB + 3 > 192)
-        return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 192)", who, 3 + 3 * (model->J - 1) + model->NB + 3);
+    if (3 + 3 * (model->J - 1) + model->NB + 3 > 256)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 256)", who, 3 + 3 * (model->J - 1) + model->NB + 3);
     return K2B_OK;
 }
 
@@ -207,7 +219,7 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
 #define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_sequence_lbfgs: HIP call failed")
     float* pres = lbfgs_ws_assign(&w, ws.get(), 1, P);
     // the whole sequence in ONE launch where the fused kernel takes it (24-joint model, the prior over the whole pose, kinematic targets)
-    if (lbfgs_scheme() == 0 && T > 1 && fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)) {
+    if (lbfgs_scheme() == 0 && lbfgs_stage_cap() < 0 && T > 1 && fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)) {
         FitCall c = fit_call(1, K, model_joint_index, j3d, conf, stream_v);
         c.in = {go_in, bp_in, be_in, tr_in};
         c.out = {go_out, bp_out, be_out, tr_out};                             // rows t of the outputs: frame t's point
@@ -337,16 +349,16 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
     ev.out = {go_o, bp_o, be_o, tr_o};
     ev.loss_out = loss_f; ev.grad_out = grad_f;
     k2b::LbfgsArgs la = make_lbfgs_args(S, model_c, {max_iter, H, lr, tolerance_grad, tolerance_change}, {go_s, bp_s, be_s, tr_s}, w);
-    const int rounds = la.max_eval + 2;
+    const int rounds = la.max_eval + 2, stage_cap = lbfgs_stage_cap();
     for (int r = 0; r < rounds; ++r) {
         TRY_Q(k2b::launch_shape_prep(sa, stream));
         if (N > 0)
             if (const int rc = fit_world_impl(model_c, prior, &ec, ev); rc != K2B_OK) return rc;
         TRY_Q(k2b::launch_shape_reduce(sa, stream));
-        TRY_Q(k2b::launch_lbfgs_step(la, stream));
+        TRY_Q(k2b::launch_lbfgs_step(la, stream, stage_cap));
     }
     la.finalize = 1;
-    TRY_Q(k2b::launch_lbfgs_step(la, stream));                                            // the accepted points
+    TRY_Q(k2b::launch_lbfgs_step(la, stream, stage_cap));                                           // the accepted points
     TRY_Q(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), be_s, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
                            hipMemcpyDeviceToDevice, stream));
 #undef TRY_Q

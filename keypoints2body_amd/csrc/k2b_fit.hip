@@ -430,7 +430,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 int pairs = (per_wave - head) / (2 * PL * (int)sizeof(float));
                 pairs = pairs < 0 ? 0 : pairs;
                 unsigned char* stage = reinterpret_cast<unsigned char*>(yx) + wave * per_wave;
-                lbfgs_dev::lbfgs_step_frame(la, f[0], lane, stage, pairs);
+                lbfgs_dev::lbfgs_step_frame<lbfgs_dev::kEpl>(la, f[0], lane, stage, pairs);
             }
             // the parameters written above are read back below by other lanes of the same wave (and by nobody else in this launch)
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             if (lb_loop) la = a.lbv;
         }
         la.finalize = 0;
-        lbfgs_dev::Frame fr(la);                                        // (unbound: touches no memory; bound below where an optimiser runs)
+        lbfgs_dev::Frame<lbfgs_dev::kEpl> fr(la);                      // (unbound: touches no memory; bound below where an optimiser runs)
         if constexpr (MODE == MODE_SPLIT_LBFGS) {
             if (lb_loop) {
                 double* lds_al = reinterpret_cast<double*>(lb_stage);
@@ -944,7 +944,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
 #pragma unroll
                 for (int w = 0; w < lbfgs_dev::SV_HIST; ++w)
 #pragma unroll
-                    for (int k = 0; k < lbfgs_dev::EPL; ++k) fr.V[w][k] = 0.f;
+                    for (int k = 0; k < lbfgs_dev::kEpl; ++k) fr.V[w][k] = 0.f;
             }
         }
         for (int step = 0; step < steps; ++step) {
@@ -986,7 +986,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                             if (fr.s.phase != lbfgs_dev::PH_DONE) {
                                 const float* gsrc = la.grad_in + (size_t)lb_frame * la.P;
 #pragma unroll
-                                for (int k = 0; k < lbfgs_dev::EPL; ++k) fr.GN[k] = fr.has(k) ? gsrc[lane + 64 * k] : 0.f;
+                                for (int k = 0; k < lbfgs_dev::kEpl; ++k) fr.GN[k] = fr.has(k) ? gsrc[lane + 64 * k] : 0.f;
                                 const float* lp = la.loss_in + lb_frame;
                                 asm volatile("" : "+v"(lp));      // (a per-lane address: a VECTOR load, through the L1 the row wave's store went through)
                                 lbfgs_dev::lbfgs_consume(fr, (double)*lp);

@@ -10,8 +10,9 @@
 //   * torch's algorithm (LBFGS.step, _strong_wolfe, _cubic_interpolate: two-loop recursion, bracket phase, zoom phase with its
 //     insufficient-progress rule, the tolerance / max_iter / max_eval exits) restated as a per-frame state machine
 //     INIT -> (BRACKET | ZOOM)* -> DONE that consumes ONE closure result per call and names the next point to evaluate;
-//   * one wavefront per frame (k2b_lbfgs_device.h): vectors (<= 192 parameters) three elements per lane, in registers for the
-//     whole step; state and history (2 H P floats) in global memory between steps, the history staged in LDS for the two-loop
+//   * one wavefront per frame (k2b_lbfgs_device.h): vectors three elements per lane (<= 192 parameters; four, <= 256, in the
+//     step kernel's wide form for the 55- and 63-joint models beyond that), in registers for the whole step; state and history
+//     (2 H P floats) in global memory between steps, the history staged in LDS for the two-loop
 //     recursion; inner products reduced over the wave in double (DPP scan), scalars in double where torch holds Python floats;
 //     no FMA contraction (the code is inlined into three kernels and must round alike in each);
 //   * the host only ENQUEUES a fixed number of [closure, step] rounds - max_eval + 2, the most any frame can need - without
@@ -32,9 +33,11 @@ namespace k2b {
 
 using namespace lbfgs_dev;
 
+// EPL = vector elements per lane: kEpl for P <= 192, kEplWide for P <= 256
+template <int EPL>
 __global__ __launch_bounds__(64) void k2b_lbfgs_step_kernel(const LbfgsArgs a, int lds_pairs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lbfgs_lds[];
-    lbfgs_step_frame(a, blockIdx.x, threadIdx.x, lbfgs_lds, lds_pairs);
+    lbfgs_step_frame<EPL>(a, blockIdx.x, threadIdx.x, lbfgs_lds, lds_pairs);
 }
 
 // start of one frame of a warm-start sequence: parameters and preserve pose from their sources (the previous frame's result),
@@ -66,18 +69,22 @@ size_t lbfgs_state_bytes(int B, int P, int H, size_t* off_si, size_t* off_sv) {
     return n;
 }
 
-hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream) {
+hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_staged_pairs) {
     if (a.B <= 0) return hipSuccess;
-    if (a.P > 192 || a.H < 1 || a.H > kLbfgsMaxHistory) return hipErrorInvalidValue;
+    if (a.P > 64 * kEplWide || a.H < 1 || a.H > kLbfgsMaxHistory) return hipErrorInvalidValue;
     // LDS: the alphas, then as many staged history pairs as a fit can collect (one per outer iteration) - within 48 KiB, so that
-    // several frames share a CU; pairs beyond that are read from global memory
+    // several frames share a CU; pairs beyond that are read from global memory.  (P > 192: a pair is 2 KiB and H = 30 leaves room
+    // for 23 of the 30, so the reference's default max_iter = 30 reads pairs 23.. from global memory - tests/test_gpu_lbfgs_wide.py.)
+    // max_staged_pairs >= 0 caps the number further (development switch: the results do not depend on it).
     const int PL = (a.P + 63) / 64 * 64;
     int pairs = a.H < a.max_iter ? a.H : a.max_iter;
     const size_t per_pair = (size_t)2 * PL * sizeof(float), head = (size_t)2 * a.H * sizeof(double);
     const size_t room = 48 * 1024 - head;
     if ((size_t)pairs * per_pair > room) pairs = (int)(room / per_pair);
+    if (max_staged_pairs >= 0 && pairs > max_staged_pairs) pairs = max_staged_pairs;
     const size_t lds = head + (size_t)pairs * per_pair;
-    hipLaunchKernelGGL(k2b_lbfgs_step_kernel, dim3(a.B), dim3(64), lds, stream, a, pairs);
+    if (a.P <= 64 * kEpl) hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEpl>, dim3(a.B), dim3(64), lds, stream, a, pairs);
+    else hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEplWide>, dim3(a.B), dim3(64), lds, stream, a, pairs);
     return hipGetLastError();
 }
 

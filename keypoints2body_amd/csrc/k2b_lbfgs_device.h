@@ -75,15 +75,20 @@ struct Scal {
     int phase, nold, niter, evals, ls_iter, max_ls, ls_evals, first, low, insuf, head;
 };
 
-constexpr int EPL = 3;                           // vector elements per lane (P <= 192): element e = lane + 64 k
-typedef float Vec[EPL];
+// Vector elements per lane, a compile-time parameter of the state machine: element e = lane + 64 k, k < EPL, so P <= 64 EPL.
+// Three cover the 24- and 52-joint models and the 55-joint one up to 24 shape coefficients (P <= 192): the fit kernel's three
+// inlined copies and the step kernel's narrow form.  Four (P <= 256) cover every model the library fits (the tree kernel:
+// 63 joints, 32 shape coefficients, P = 224): the step kernel's wide form only.
+constexpr int kEpl = 3, kEplWide = 4;
 
 // A step used to walk through global memory: every vector operation a loop of loads and stores, every decision behind the
 // round trip of the one before (9.6 us median, 12.8 us mean per step for one frame: more than the closure's launch).  Now the
-// frame's eight state vectors and the closure's gradient are loaded ONCE, all loads in flight together, live in registers (three
+// frame's eight state vectors and the closure's gradient are loaded ONCE, all loads in flight together, live in registers (EPL
 // elements per lane) for the whole step and are written back once at its end; the history pairs the two-loop recursion needs are
 // staged in LDS by one burst of loads.
+template <int EPL>
 struct Frame {
+    typedef float Vec[EPL];
     const LbfgsArgs& a;
     int f, lane, P, H;
     int fp;                                      // row of the parameter arrays the closure evaluates (= f except in a sequence chain)
@@ -128,7 +133,7 @@ struct Frame {
             for (int k = 0; k < EPL; ++k) V[w][k] = 0.f;
     }
     __device__ __forceinline__ bool has(int k) const { return lane + 64 * k < P; }
-    // every state vector and the new gradient: 27 independent loads (a frame in phase INIT has no vectors yet: zeros)
+    // every state vector and the new gradient: 9 EPL independent loads (a frame in phase INIT has no vectors yet: zeros)
     // (requested whatever the phase turns out to be - the scalars above are still in flight -; a frame in phase INIT has no vectors
     //  yet: what was read is dropped)
     __device__ __forceinline__ void load_vectors(const float* g_new) {
@@ -464,7 +469,8 @@ struct Frame {
 // parameter arrays (frames still in a line search when the rounds run out fall back to it), for the final loss evaluation.
 // lds = 2 H doubles (alphas, rho) followed by lds_pairs staged history pairs of 2 x 64 ceil(P / 64) floats, private to the wave.
 // one closure result (loss f_new, gradient in fr.GN) through the state machine
-__device__ __forceinline__ void lbfgs_consume(Frame& fr, double f_new) {
+template <int EPL>
+__device__ __forceinline__ void lbfgs_consume(Frame<EPL>& fr, double f_new) {
     const LbfgsArgs& a = fr.a;
     const int lane = fr.lane;
     if (fr.s.phase == PH_INIT) {
@@ -487,10 +493,11 @@ __device__ __forceinline__ void lbfgs_consume(Frame& fr, double f_new) {
     }
 }
 
+template <int EPL>
 __device__ __forceinline__ void lbfgs_step_frame(const LbfgsArgs& a, int f, int lane, unsigned char* lds, int lds_pairs) {
     double* lds_al = reinterpret_cast<double*>(lds);
     float* lds_hist = reinterpret_cast<float*>(lds + (size_t)2 * a.H * sizeof(double));
-    Frame fr(a, f, lane, lds_hist, lds_al, lds_pairs);
+    Frame<EPL> fr(a, f, lane, lds_hist, lds_al, lds_pairs);
     fr.load_vectors(a.grad_in + (size_t)f * a.P);
     if (a.finalize) { if (fr.s.phase != PH_INIT) fr.park(); return; }
     if (fr.s.phase == PH_DONE) return;
