@@ -65,7 +65,10 @@ const char *k2b_last_error(void);
  *   j_regressor [J][V]        lbs_weights [V][J]        parents [J] (parents[0] = -1,
  *   extra_vertex_ids [E]      (output joints J..J+E-1 are these vertices)   parents[i] < i)
  * Limits: 2 <= J <= 64, 1 <= NB <= 32, E >= 0.  (24 joints with NB <= 16 run the 24-lane fused fit kernel,
- * everything else the tree kernel; the vertex kernel is built for 17-24 and 49-56 joints.)
+ * everything else the tree kernel; the vertex kernels are built for 17-24 and 49-56 joints, with every NB up to 32: a frame's
+ * 9(J-1) + NB + 2 features are staged in at most 34 k-steps of 16, 544 features, and 56 joints with 32 coefficients are 529.)
+ * Development switch: with K2B_LBS_TILE set to a non-zero number in the environment WHEN THIS FUNCTION RUNS, k2b_lbs skins the
+ * model with the tile kernel instead of a stream kernel (the same results within the forward's tolerance; a test twin).
  * ------------------------------------------------------------------------------- */
 int k2b_model_create(k2b_model **out, int32_t num_vertices, int32_t num_joints, int32_t num_betas,
                      int32_t num_extra_joints, const float *v_template, const float *shapedirs,
@@ -232,8 +235,8 @@ int k2b_fit_sequence(const k2b_model *model, const k2b_prior *prior, const k2b_f
  * loss and gradient AT the result.  Frames never interact (torch couples the frames of a batch in one line search; the
  * reference only ever passes one frame).  At most 256 parameters per frame (3 + 3(J-1) + NB + 3): every model the fit
  * kernels take (63 joints and 32 shape coefficients are 224); beyond 192 the optimiser's step kernel runs in its wide form.
- * NOTE: k2b_lbs does not skin such a model - it stages at most 512 features (9(J-1) + NB + 2), i.e. a 55-joint model with at
- * most 24 shape coefficients - so a caller gets fitted parameters for it from this entry, but no vertices / joints from k2b_lbs.
+ * (k2b_lbs skins 17-24 and 49-56 joints with up to 32 shape coefficients: a model with another joint count gets fitted
+ * parameters from this entry, but no vertices / joints from k2b_lbs.)
  * Line searches branch on rounding, so results agree with torch's statistically (and iterate by iterate with the float64
  * twin core/lbfgs_batched.py while rounding has not yet been amplified): see DESIGN.md.
  * ------------------------------------------------------------------------------- */
@@ -336,6 +339,8 @@ int k2b_fit_sequences_lbfgs(const k2b_model *model, const k2b_prior *prior, cons
  *   joints_out dev [B][J+E+L][3], vertices_out dev [B][V][3] (NULL: joints only; the E
  *   vertex-selected joints and the 3L landmark vertices are then skinned alone).  transl may be NULL
  *   (no translation).  Landmarks are combined from the translated vertices.
+ * Models: 17-24 joints (SMPL) and 49-56 joints (SMPL-H / SMPL-X) with 1 <= NB <= 32 shape coefficients (betas | expression);
+ * any other joint count: K2B_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------------- */
 int k2b_lbs(const k2b_model *model, int32_t num_frames, const float *global_orient,
             const float *body_pose, const float *betas, const float *transl,

@@ -107,17 +107,18 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
     if (m->groups_a != 3 && m->groups_a != 7)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs: %d joints; the vertex kernel is built for 17-24 (SMPL) and 49-56 (SMPL-H / SMPL-X) joints", m->J);
     pa.xh = m->wsXh.get(); pa.xl = m->wsXl.get(); pa.a2 = m->wsA2.get(); pa.joints_out = joints_out;
-    pa.a2_stream_order = (m->stream || m->stream_x) ? 1 : 0;
+    pa.a2_stream_order = m->streams() ? 1 : 0;
     HIP_TRY(k2b::launch_pose_setup(pa, stream));
     auto skin = [&](const VertexSet& vs, float* out, int stride, int row0, float* joint_copies) -> hipError_t {
-        if (m->stream || m->stream_x) {
+        if (m->streams()) {
             k2b::StreamArgs sa{};
             sa.xh = pa.xh; sa.xl = pa.xl; sa.a2 = pa.a2; sa.pd = vs.spd.get(); sa.w = vs.sw.get();
             sa.f32_tiles = bpad / 32; sa.nv16 = vs.nv16;
             sa.num_frames = B; sa.num_out = vs.num; sa.out = out; sa.out_stride = stride; sa.out_row0 = row0;
             sa.dump = m->dump.get();
             sa.joints_out = joint_copies; sa.joints_stride = ostride; sa.joints_row0 = m->J;
-            return m->stream ? k2b::launch_skin_stream(sa, device_cus(), stream) : k2b::launch_skin_stream_x(sa, device_cus(), stream);
+            return m->stream ? k2b::launch_skin_stream(sa, device_cus(), stream)
+                 : m->stream_x ? k2b::launch_skin_stream_x(sa, device_cus(), stream) : k2b::launch_skin_stream_xw(sa, device_cus(), stream);
         }
         k2b::TileArgs ta{};
         ta.xh = pa.xh; ta.xl = pa.xl; ta.a2 = pa.a2; ta.pdh = vs.pdh.get(); ta.pdl = vs.pdl.get(); ta.w2 = vs.w2.get();

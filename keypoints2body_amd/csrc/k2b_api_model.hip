@@ -2,6 +2,7 @@
 // tables of the two fit kernels, landmarks, and the per-model tables and workspaces that calls build on first use.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -66,7 +67,7 @@ int build_vertex_set(k2b_model* m, VertexSet& vs, const std::vector<int>& ids, c
             if (i < n && !tag.empty() && tag[i]) rowp[(size_t)(2 * GA + 1) * 128] = (k2b::k2b_half)(float)tag[i];   // ZERO group: joint tag
         }
     hipError_t e;
-    if (m->stream || m->stream_x) {
+    if (m->streams()) {
         // stream kernels: Pd [k-step][16-vertex tile][coord][hi | lo] and W [16-vertex tile][3 or 5 fragments], 1 KiB pieces in
         // MFMA operand order (lane = row + 16 k-group, 8 halfs); vertex tiles padded to whole 128-vertex groups
         const int nv16 = (n + 127) / 128 * 8, SK = KX / 2, NWF = m->stream ? 3 : 5;
@@ -98,7 +99,7 @@ int build_vertex_set(k2b_model* m, VertexSet& vs, const std::vector<int>& ids, c
         if ((e = vs.spd.upload(spd.data(), spd.size())) != hipSuccess) return (int)e;
         if ((e = vs.sw.upload(sw.data(), sw.size())) != hipSuccess) return (int)e;
     }
-    if (m->stream || m->stream_x) return 0;          // the tile kernel's images stay on the host (SMPL-X: 64 MB less per GPU)
+    if (m->streams()) return 0;                      // the tile kernel's images stay on the host (SMPL-X: 64 MB less per GPU)
     if ((e = vs.w2.upload(w2.data(), w2.size())) != hipSuccess) return (int)e;
     if ((e = vs.pdh.upload(pdh.data(), pdh.size())) != hipSuccess) return (int)e;
     if ((e = vs.pdl.upload(pdl.data(), pdl.size())) != hipSuccess) return (int)e;
@@ -336,8 +337,13 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
         // 49-56 joints with fewer features than SMPL-X (SMPL-H: 477 -> 15 k-steps): one all-zero k-step more buys the stream kernel
         if (K2B_LBS_STREAM && m->groups_a == 7 && KX < 2 * k2b::kStreamXKSteps) KX = 2 * k2b::kStreamXKSteps;
         m->k_steps_x = KX;
-        m->stream = K2B_LBS_STREAM && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
-        m->stream_x = K2B_LBS_STREAM && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
+        // development switch K2B_LBS_TILE (non-zero): this model is skinned by the tile kernel whatever the stream kernels would
+        // take - their run-time twin.  Per model, fixed here; nothing else reads it.
+        const char* tile_env = getenv("K2B_LBS_TILE");
+        const bool streams = K2B_LBS_STREAM && !(tile_env && atoi(tile_env) != 0);
+        m->stream = streams && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
+        m->stream_x = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
+        m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 25-32 shape coefficients
         HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
         std::vector<int> all(V), ex(extra_vertex_ids, extra_vertex_ids + E), tag(V, 0);
         for (int v = 0; v < V; ++v) all[v] = v;

@@ -58,7 +58,8 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
 // ---------------------------------------------------------------------------------------------
 // Pose set-up: one 64-lane workgroup per frame, lane j = joint j.
 // ---------------------------------------------------------------------------------------------
-constexpr int kMaxXSteps = 32;       // 16-deep k-steps of the feature vector this kernel can stage (SMPL: 14, SMPL-X: 32)
+constexpr int kMaxXSteps = 34;       // 16-deep k-steps of the feature vector this kernel can stage (SMPL: 14, SMPL-X: 32, or 34 with 25-32
+                                     // shape coefficients: 9 x 54 + 32 + 2 = 520 features)
 
 // NBC = capacity of the shape loop (10 / 16 / 20 / 32: the unrolled J(beta) loads and products are a third of this
 // kernel's instructions at 32), GA = ceil(J / 8) (compile-time divisors in the A2 store loop)

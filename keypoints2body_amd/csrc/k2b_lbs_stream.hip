@@ -1,6 +1,7 @@
 // k2b_lbs_stream.hip — vertex skinning for SMPL (k2b_lbs_stream_kernel: 17-24 joints, 7 pose k-steps) and SMPL-H / SMPL-X
-// (k2b_lbs_stream_x_kernel: 49-56 joints, 16 pose k-steps) on gfx950: ONE kernel body, stream_body<S>, and two descriptions S
-// (Smpl, SmplX) that hold what the two kernels do not share - the counted-wait tables among it.
+// (k2b_lbs_stream_x_kernel: 49-56 joints, 16 pose k-steps; k2b_lbs_stream_xw_kernel: the same with 25-32 shape coefficients,
+// 17 pose k-steps) on gfx950: ONE kernel body, stream_body<S>, and three descriptions S (Smpl, SmplX, SmplXWide) that hold what
+// the kernels do not share - the counted-wait tables among it.
 //
 // Same arithmetic as the tile kernel of k2b_lbs.hip (two GEMMs over frames x vertices on v_mfma_f32_16x16x32_f16, operands
 // as f16 hi/lo pairs, v = T [v_posed; 1] + t; reference seam: the final forward of world_space.py:258-278, smplx's
@@ -9,7 +10,8 @@
 //   * a wave owns 16 vertices x 128 frames (eight 16 x 16 accumulator tiles per coordinate).  Its share of the big
 //     B operand Pd (posedirs | shapedirs | template, 48 of the 64 KiB a 32-deep k-step needs) is private to it, so it goes
 //     global -> REGISTERS with plain 16-byte loads, two k-steps ahead, and never touches LDS or a barrier: k-step ks lives in
-//     Pd buffer ks % 3, and since 7 % 3 == 16 % 3 == 1 the next tile's k-steps 0 and 1 end the tile in buffers 1 and 2;
+//     Pd buffer ks % 3, so the next tile's k-steps 0 and 1 end the tile in the buffers KS % 3 and (KS + 1) % 3 (1 and 2 for 7
+//     and 16 k-steps, 2 and 0 for 17) and are handed down to the buffers 0 and 1;
 //   * the frame-side operand X (16 KiB per k-step) is fetched by LDS-DMA.  SMPL: X of the WHOLE tile is resident in 7 slots, the
 //     pose phase has NO barrier at all, waves drift apart and the stores of one wave overlap the matrix work of another; X of
 //     the next tile arrives during the transform phase, one k-step per 16-frame unit.  SMPL-X: 16 k-steps do not fit, so X
@@ -28,7 +30,8 @@
 // its description, under the table that justifies them, and nowhere else.
 //
 // LDS: X slots x 16 KiB + 2 A units = 7 x 16 + 2 x 24 = 4 x 16 + 2 x 48 = 160 KiB.  SMPL: 9 (J - 1) + NB + 2 <= 224 (up to 15
-// shape coefficients); SMPL-X: 9 x 54 + 20 + 2 = 508 features; everything else runs the tile kernel.
+// shape coefficients); SMPL-X: 9 x 54 + NB + 2 <= 512 features (up to 24 shape coefficients) in 16 k-steps, <= 544 (25-32) in
+// 17; everything else runs the tile kernel.
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
@@ -117,7 +120,7 @@ __device__ __forceinline__ void gstore12(unsigned lane_off, float3r d, const voi
     asm volatile("global_store_dwordx3 %0, %1, %2" ::"v"(lane_off), "v"(d), "s"(sbase) : "memory");
 }
 
-// ---- the two descriptions ---------------------------------------------------------------------------------------------------------
+// ---- the three descriptions -------------------------------------------------------------------------------------------------------
 // Vector-memory operations of a wave in issue order (they retire in order; N of a wait = operations younger than the awaited one):
 //   pose phase, top of k-step ks:  [wait] [barrier]  X(ks + 3) (ring only)   W (last k-step)   Pd(ks + 2)
 //   transform, top of unit u:      [wait] [barrier]  A(u + 1)   X(next tile, u) (the first units)   ...   stores (full tile)
@@ -193,6 +196,33 @@ struct SmplX {
     static constexpr int kStampPoseEnd = -1, kStampUnits = 16, kStampTileEnd = 40;
     [[maybe_unused]] static constexpr int kStampsPerWave = 64, kStampTile = 1;
     [[maybe_unused]] static constexpr int kDiagLevel = K2B_STREAMX_DIAG;
+};
+
+// SMPL-X with 25-32 shape coefficients: 9 x 54 + NB + 2 = 513..520 features, one 32-deep k-step more.  Ring, fragments, products
+// and unit waits are SmplX's; the ring runs one k-step longer, and 17 % 3 == 2 hands the Pd buffers over from 2 and 0 (the body).
+struct SmplXWide {
+    static constexpr int kPoseSteps = kStreamXWKSteps;
+    static constexpr int kXSlots = 4;                       // X(16) takes slot 0; the next tile's X(0) follows it behind the barrier of unit 0
+    static constexpr bool pose_barrier(int ks) { return ks >= 1 && ks <= 15; }   // publishes X(ks + 1), frees the slot of X(ks - 1)
+    static constexpr bool pose_x_fill(int ks) { return ks >= 1 && ks <= 13; }    // X(ks + 3) into that slot; X(16) is the last
+    static constexpr int kXUnits = SmplX::kXUnits;
+    static constexpr int kAFrags = SmplX::kAFrags, kWFrags = SmplX::kWFrags, kTagFrag = SmplX::kTagFrag;
+    static constexpr int kProducts = SmplX::kProducts;
+    static constexpr int prod_a(int p) { return SmplX::prod_a(p); }
+    static constexpr int prod_w(int p) { return SmplX::prod_w(p); }
+    static constexpr int kChunk = SmplX::kChunk;
+    // | point          | awaited                                          | younger in issue order                                  |
+    // | k-steps 0, 1   | Pd(0), Pd(1)                                     | covered by the waits of the previous tile's units       |
+    // | k-step 2..14   | Pd(ks) (and X(ks + 1), filled in front of it)    | X(ks + 2), Pd(ks + 1)   (issued at k-step ks - 1 <= 13) |
+    // | k-steps 15, 16 | Pd(ks) (15: and X(16), filled at k-step 13)      | Pd(ks + 1)              (no fill at k-steps 14, 15)     |
+    // | unit 0         | W (loaded at k-step 16) and A(unit 0)            | the next tile's Pd(1)                                   |
+    // | unit 1..7      | as SmplX (the same fills and stores in the same order): its unit_wait, partial-tile counts included      |
+    static constexpr int pose_wait(int ks) { return ks < 2 ? kNoWait : ks <= 14 ? kXFills + kPdLoads : kPdLoads; }
+    static __device__ __forceinline__ void unit_wait(int u, bool full, half8 (&wf)[kWFrags]) { SmplX::unit_wait(u, full, wf); }
+    // pose stamps 0..16
+    static constexpr int kStampPoseEnd = -1, kStampUnits = 17, kStampTileEnd = 41;
+    [[maybe_unused]] static constexpr int kStampsPerWave = 64, kStampTile = 1;
+    [[maybe_unused]] static constexpr int kDiagLevel = 0;   // (no diagnostics build of this kernel)
 };
 
 template <class S> constexpr int stream_x_bytes() { return S::kXSlots * 16 * 1024; }
@@ -324,7 +354,10 @@ __device__ __forceinline__ void stream_body(const StreamArgs a) {
             if constexpr (!(K2B_SX_SKIP & 4)) { if constexpr (ks + 2 < KS) load_pd(ahead, cvg, ks + 2); else load_pd(ahead, nvg, ks + 2 - KS); }
             kstep(ksc, cur);
         };
-        static_assert(KS % 3 == 1, "the next tile's k-steps 0 and 1 must end the tile in buffers 1 and 2");
+        // the next tile's k-steps 0 and 1 are loaded at the k-steps KS - 2 and KS - 1 into the buffers KS % 3 and (KS + 1) % 3; a
+        // remainder 0 would put k-step 0 into buffer 0 itself and k-step 1 into 1: no hand-over, and nothing here is built for it
+        static_assert(KS % 3 == 1 || KS % 3 == 2, "the next tile's k-steps 0 and 1 must end the tile in buffers 1, 2 or 2, 0");
+        constexpr int kHand0 = KS % 3, kHand1 = (KS + 1) % 3;
         xread(xq[0], ic<0>{}, ic<0>{});
         static_for<KS>(step);
         K2B_SDIAG_STAMP(S::kStampPoseEnd);
@@ -427,14 +460,22 @@ __device__ __forceinline__ void stream_body(const StreamArgs a) {
                 }
             }
         }
-        // buffers 1 and 2 hold the next tile's k-steps 0 and 1 (landed long ago: the waits of the units covered them); the empty
-        // statement pins the copies behind this point - the compiler takes an asm load's result for ready at once
-        asm volatile("" : "+v"(pb[1][0][0]), "+v"(pb[1][0][1]), "+v"(pb[1][1][0]), "+v"(pb[1][1][1]), "+v"(pb[1][2][0]), "+v"(pb[1][2][1]),
-                          "+v"(pb[2][0][0]), "+v"(pb[2][0][1]), "+v"(pb[2][1][0]), "+v"(pb[2][1][1]), "+v"(pb[2][2][0]), "+v"(pb[2][2][1]));
+        // buffers kHand0 and kHand1 hold the next tile's k-steps 0 and 1 (landed long ago: the waits of the units covered them); the
+        // empty statement pins the copies behind this point - the compiler takes an asm load's result for ready at once
+        {
+            half8 (&h0)[3][2] = pb[kHand0], (&h1)[3][2] = pb[kHand1];
+            asm volatile("" : "+v"(h0[0][0]), "+v"(h0[0][1]), "+v"(h0[1][0]), "+v"(h0[1][1]), "+v"(h0[2][0]), "+v"(h0[2][1]),
+                              "+v"(h1[0][0]), "+v"(h1[0][1]), "+v"(h1[1][0]), "+v"(h1[1][1]), "+v"(h1[2][0]), "+v"(h1[2][1]));
+        }
+        // down to the buffers 0 and 1, a source never overwritten before it is read: 1, 2 -> 0, 1 in that order; 2, 0 -> 0, 1 moves
+        // buffer 0 up first
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) { pb[0][c][h] = pb[1][c][h]; pb[1][c][h] = pb[2][c][h]; }
+            for (int h = 0; h < 2; ++h) {
+                if constexpr (kHand0 == 1) { pb[0][c][h] = pb[1][c][h]; pb[1][c][h] = pb[2][c][h]; }
+                else { pb[1][c][h] = pb[0][c][h]; pb[0][c][h] = pb[2][c][h]; }
+            }
         K2B_SDIAG_STAMP(S::kStampTileEnd);
         wt = nt; cfg = nxf; cvg = nxv;
         K2B_SDIAG_TILE;
@@ -461,12 +502,16 @@ hipError_t launch_stream(void (*kernel)(const StreamArgs), const StreamArgs& a_i
 
 __global__ __launch_bounds__(512) void k2b_lbs_stream_kernel(const StreamArgs a) { stream_body<Smpl>(a); }
 __global__ __launch_bounds__(512) void k2b_lbs_stream_x_kernel(const StreamArgs a) { stream_body<SmplX>(a); }
+__global__ __launch_bounds__(512) void k2b_lbs_stream_xw_kernel(const StreamArgs a) { stream_body<SmplXWide>(a); }
 
 hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stream) {
     return launch_stream<Smpl>(k2b_lbs_stream_kernel, a, num_cus, stream);
 }
 hipError_t launch_skin_stream_x(const StreamArgs& a, int num_cus, hipStream_t stream) {
     return launch_stream<SmplX>(k2b_lbs_stream_x_kernel, a, num_cus, stream);
+}
+hipError_t launch_skin_stream_xw(const StreamArgs& a, int num_cus, hipStream_t stream) {
+    return launch_stream<SmplXWide>(k2b_lbs_stream_xw_kernel, a, num_cus, stream);
 }
 
 }  // namespace k2b

@@ -83,11 +83,13 @@ class BodyModel:
                    c.extra_vertex_ids, device=device, model_type="smplh")
 
     @classmethod
-    def synthetic_x(cls, seed: int = 0, device=None) -> "BodyModel":
-        """SMPL-X-shaped synthetic model (55 joints, V = 10475, 10 betas + 10 expression coefficients)."""
-        c = synthetic.make_body_model_x(seed)
+    def synthetic_x(cls, seed: int = 0, device=None, num_shape: int = 20, num_betas: Optional[int] = None) -> "BodyModel":
+        """SMPL-X-shaped synthetic model (55 joints, V = 10475).  ``num_shape`` coefficients (up to 32) of which the first
+        ``num_betas`` are betas and the rest expression; the defaults give 10 betas + 10 expression coefficients, and
+        ``num_shape=26, num_betas=16`` the layout of the AMASS SMPL-X files."""
+        c = synthetic.make_body_model_x(seed, num_shape=num_shape)
         return cls(c.v_template, c.shapedirs, c.posedirs, c.J_regressor, c.lbs_weights, c.parents,
-                   c.extra_vertex_ids, device=device, model_type="smplx")
+                   c.extra_vertex_ids, device=device, model_type="smplx", num_betas=num_betas)
 
     # -- SMPL-X packing ---------------------------------------------------------------------
     def pack_pose(self, B: int, **kw) -> torch.Tensor:

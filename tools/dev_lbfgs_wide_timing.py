@@ -84,8 +84,8 @@ def main():
                                                                     max_iter=30, lr=1e-2))
         return
 
-    # the wide model: its targets come from the oracle's CPU forward, as in tests/test_gpu_lbfgs_wide.py (k2b_lbs stages at most
-    # 512 features, so it does not skin a 55-joint model with more than 24 shape coefficients)
+    # the wide model: its targets come from the oracle's CPU forward, as in tests/test_gpu_lbfgs_wide.py (written when k2b_lbs
+    # did not skin a 55-joint model with more than 24 shape coefficients; kept so that the figures stay comparable)
     from keypoints2body_amd.core.fitters.world_space import WorldSpaceFitter
     from keypoints2body_amd.models.smpl_data import SMPLXData
     from tests import test_gpu_lbfgs_wide as W
