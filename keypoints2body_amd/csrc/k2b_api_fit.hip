@@ -281,6 +281,7 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
     if (const int rc = chain_adam_table(model, cfg, c, &coef); rc != K2B_OK) return rc;
 
     a.dt = model->dt.get(); a.dd = model->dd.get(); a.lane_tab = model->tree.get();
+    a.scan64 = model->fit_scan64 ? 1 : 0;
     a.num_rounds = rounds_for_depth(t.max_depth);
     a.num_betas = model->NB;
     a.pa_image = prior->pa_image.get(); a.row_const = prior->row_const.get(); a.neg_log_nllw = prior->nlw.get();

@@ -7,6 +7,7 @@
 #include <memory>
 
 #include "k2b_host.h"
+#include "k2b_scan_plan.h"
 
 #ifndef K2B_LBS_STREAM
 #define K2B_LBS_STREAM 1      // 0: development builds that keep the tile kernel for 17-24 joint models (A/B timing)
@@ -387,8 +388,7 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
         HIP_TRY(m->j_basis_lane.upload(lane.data(), lane.size()));
     }
 
-    // tables of the fused fit kernel: lanes follow the DFS pre-order of the tree, so that every
-    // subtree is a contiguous lane range
+    // tables of the fused fit kernel, by lane (the placement is chosen below)
     bool ok = (J == k2b::kFitJoints) && NB <= k2b::kMaxBetas;
     if (!ok) m->fit_why = "the 24-lane fused fit kernel is built for the 24-joint SMPL tree with <= 16 betas";
     std::vector<std::vector<int>> children(J);
@@ -415,25 +415,45 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
     while ((1 << rounds) < maxd + 1) ++rounds;
     if (ok && (rounds > k2b::kMaxRounds || J > 32)) { ok = false; m->fit_why = "tree too deep / large for the fused fit kernel"; }
     m->depth = depth;
+    // Lane placement of the fused kernel.  With a scan plan (k2b_scan_plan.h): reversed DFS order with holes, the subtree sums are
+    // fp32 chain / end scans.  Without one (a junction inside a limb, a chain of more than 8 joints, ...): DFS order, where every
+    // subtree is the lane range that starts at its joint, and the fp64 prefix differences.
+    // Development switch K2B_FIT_SCAN64 (non-zero): this model gets the DFS placement and the fp64 scans whatever its tree allows -
+    // the run-time twin of the fp32 form.  Per model, fixed here; nothing else reads it.
+    const char* scan_env = getenv("K2B_FIT_SCAN64");
+    k2b::ScanPlan plan;
+    if (ok && !(scan_env && atoi(scan_env) != 0)) plan = k2b::fit_scan_plan(J, parents);
+    m->fit_scan64 = !plan.valid;
+    std::vector<int> f_lane_of = lane_of, f_joint_at(k2b::kScanLanes, -1);
+    if (plan.valid) {
+        f_lane_of = plan.lane_of;
+        f_joint_at.assign(plan.joint_at, plan.joint_at + k2b::kScanLanes);
+    } else if (ok) {
+        for (int l = 0; l < J; ++l) f_joint_at[l] = order[l];
+    }
     std::vector<int> tab((size_t)64 * k2b::kLaneTabStride, -1);
+    for (int l = 0; l < 64; ++l) tab[(size_t)l * k2b::kLaneTabStride + k2b::kLaneTabScan] = 0;
     std::vector<float> dt((size_t)64 * 3, 0.f), dd((size_t)64 * 3 * k2b::kMaxBetas, 0.f);
     if (ok) {
-        for (int l = 0; l < J; ++l) {
-            const int j = order[l], p = parents[j];
+        for (int l = 0; l < k2b::kScanLanes; ++l) {
+            const int j = f_joint_at[l];
+            if (j < 0) continue;                     // a hole or a lane beyond the tree: no joint, zero offset, identity transform
+            const int p = parents[j];
             int* t = tab.data() + (size_t)l * k2b::kLaneTabStride;
             t[0] = j;
-            t[1] = p >= 0 ? lane_of[p] : -1;
+            t[1] = p >= 0 ? f_lane_of[p] : -1;
             // ancestor lane 2^r levels up (pointer doubling), -1 once past the root
             int anc = t[1];
             for (int r = 0; r < k2b::kMaxRounds; ++r) {
                 t[2 + r] = anc;
                 for (int s = 0; s < (1 << r) && anc >= 0; ++s) {   // advance 2^r more levels
-                    const int aj = order[anc];
-                    anc = parents[aj] >= 0 ? lane_of[parents[aj]] : -1;
+                    const int aj = f_joint_at[anc];
+                    anc = parents[aj] >= 0 ? f_lane_of[parents[aj]] : -1;
                 }
             }
-            t[2 + k2b::kMaxRounds] = size[j];        // subtree = lanes [l, l + size)
+            t[2 + k2b::kMaxRounds] = size[j];        // DFS placement: subtree = lanes [l, l + size)
             t[3 + k2b::kMaxRounds] = depth[j];
+            t[k2b::kLaneTabScan] = plan.valid ? plan.flags[l] : 0;
             for (int c = 0; c < 3; ++c) {
                 dt[l * 3 + c] = m->h_j_template[j * 3 + c] - (p >= 0 ? m->h_j_template[p * 3 + c] : 0.f);
                 for (int k = 0; k < NB; ++k)
@@ -478,6 +498,20 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
     }
     *out = owner.release();
     return K2B_OK;
+}
+
+// Development entry, outside include/k2b.h: the scan plan of a parent table (k2b_scan_plan.h) without a device, for the host
+// tests.  lane_of[J], lane_flags[32] (kScan* bits; 0: hole).  Returns 1 for a valid plan, 0 where the tree gets the DFS
+// placement and the fp64 scans (nothing is written), -1 for bad arguments.
+int k2b_dev_fit_scan_plan(int32_t J, const int32_t* parents, int32_t* lane_of, int32_t* lane_flags) {
+    if (J < 1 || J > k2b::kMaxJoints || !parents || !lane_of || !lane_flags || parents[0] >= 0) return -1;
+    for (int j = 1; j < J; ++j)
+        if (parents[j] < 0 || parents[j] >= j) return -1;
+    const k2b::ScanPlan plan = k2b::fit_scan_plan(J, parents);
+    if (!plan.valid) return 0;
+    for (int j = 0; j < J; ++j) lane_of[j] = plan.lane_of[j];
+    for (int l = 0; l < k2b::kScanLanes; ++l) lane_flags[l] = plan.flags[l];
+    return 1;
 }
 
 void k2b_model_destroy(k2b_model* m) {

@@ -21,11 +21,14 @@
 //   "row layout"   optimiser state: register set A, lane l <-> body_pose[l] (l = 0..63, the MFMA core
 //                  rows); set B, lane l <-> body_pose[64 + l] (l < 5), global_orient (5..7), betas
 //                  (8..8+NB-1), transl (next 3).
-//   "tree layout"  lane t < 24 owns the t-th joint of the kinematic tree in DFS pre-order, so
-//                  every subtree is a contiguous lane range.  Global transforms come from a
-//                  pointer-doubling down-sweep (log2(depth) rounds of cross-lane moves instead
-//                  of one round per level); subtree force / torque sums are differences of one
-//                  prefix scan.  All tree traffic is ds_bpermute / DPP cross-lane moves.
+//   "tree layout"  one joint of the kinematic tree per lane of a 32-lane half, placed by the host (k2b_scan_plan.h): in
+//                  REVERSED DFS pre-order, so that every subtree is the contiguous lane range that ends at its
+//                  joint, with holes where a limb's chain would straddle a 16-lane DPP row.  Global transforms
+//                  come from a pointer-doubling down-sweep (log2(depth) rounds of cross-lane moves instead of
+//                  one round per level); subtree force / torque sums are fp32 prefix scans taken as they stand
+//                  (along the joint's own chain, or over everything up to its lane) - never a difference of two.
+//                  A tree that has no such plan keeps plain DFS order and differences of one fp64 prefix scan
+//                  (template parameter SCAN64).  All tree traffic is ds_bpermute / DPP cross-lane moves.
 // The layouts exchange values through per-frame LDS strips.
 //
 // Three execution shapes (template parameter MODE), chosen by frames per CU:
@@ -50,6 +53,7 @@
 #include "k2b_internal.h"
 #include "k2b_lanes.h"
 #include "k2b_lbfgs_device.h"
+#include "k2b_scan_plan.h"
 
 // Per-phase s_memtime stamps of the split shape's two roles live outside this file: tools/build_fit_stamps.sh compiles it with
 // -DK2B_FIT_DIAG_HEADER=<tools/fit_diag.h>, which fills the hooks below (iteration 50 of one workgroup, device printf behind the loop).
@@ -193,7 +197,10 @@ __device__ __forceinline__ void adam_update(float& x, float& m, float& v, float 
     x = __builtin_fmaf(-co.x, m * fast_rcp(denom), x);
 }
 
-template <int NBT, int MODE>
+// SCAN64: how the tree pass forms its subtree sums (k2b_lanes.h) - false: fp32 chain / end scans on the lanes of the model's scan
+// plan; true: fp64 prefix differences on lanes in DFS order (models without a plan).  A template parameter, not a branch in the
+// tree pass: a run-time-false block there costs the 16-wave shape spilled registers (profiles/HISTORY.md).
+template <int NBT, int MODE, bool SCAN64>
 __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel(const FitArgs a) {
     constexpr bool SPLIT = Shape<MODE>::SPLIT, PAIR = Shape<MODE>::PAIR;
     constexpr int NROW = Shape<MODE>::NROW, CPW = Shape<MODE>::CPW;
@@ -341,7 +348,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     for (int i = 0; i < 4; ++i)
         if (lane == a.angle_index[i]) angA = a.angle_sign[i];
 
-    // tree layout constants (host tables, DFS pre-order; paired: one tree per 32-lane half)
+    // tree layout constants (host tables, in the model's lane order; paired: one tree per 32-lane half)
     const int hb = PAIR ? lane >> 5 : 0;         // which of the wave's frames this lane's tree belongs to
     const int tl = PAIR ? (lane & 31) : lane;    // lane inside that tree
     float* xs_t = slots + (slot0 + hb) * SLOT;   // strips of this lane's tree
@@ -355,8 +362,12 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     int anc_addr[kMaxRounds];
 #pragma unroll
     for (int r = 0; r < kMaxRounds; ++r) anc_addr[r] = ((lt[2 + r] >= 0 ? lt[2 + r] : 31) + 32 * hb) * 4;
-    // subtree lane range of this lane's joint inside its 32-lane half (unpaired: the upper half mirrors
-    // the lower one and carries the p x g sums)
+    // fp32 scans: the chain scan's step masks of this lane and which of the two prefixes its joint takes (unpaired: the upper half
+    // mirrors the lower one and carries the p x g sums)
+    const int scan_flags = a.lane_tab[(lane & 31) * kLaneTabStride + kLaneTabScan];
+    const float sm1 = (scan_flags & kScanStep1) ? 1.f : 0.f, sm2 = (scan_flags & kScanStep2) ? 1.f : 0.f, sm4 = (scan_flags & kScanStep4) ? 1.f : 0.f;
+    const bool take_u = (scan_flags & kScanEnd) != 0;
+    // fp64 scans: subtree lane range of this lane's joint inside its 32-lane half (unpaired: as above)
     bool sub_ok;
     int sub_end_addr;
     {
@@ -693,9 +704,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             const float k2 = 2.f * wconf * (s2 * s2);
             gj = {k2 * ex * fast_rcp(dx * dx), k2 * ey * fast_rcp(dy * dy), k2 * ez * fast_rcp(dz * dz)};
         }
-        // subtree sums of g and p x g.  A subtree is the lane range [t, t + size_t) (DFS order), so its
-        // sum is a difference of two inclusive prefix sums: five DPP steps per half-wave in double (no LDS
-        // round trip), then ONE round of cross-lane fetches for the range ends.
+        // subtree sums of g and p x g (k2b_lanes.h).  fp32 form: the lanes are in reversed DFS order and a joint's sum is one of two
+        // prefixes as it stands.  fp64 form: a subtree is the lane range [t, t + size_t) (DFS order), so its sum is a difference of
+        // two inclusive prefix sums: five DPP steps per half-wave in double (no LDS round trip), then ONE round of cross-lane
+        // fetches for the range ends.
         float sums[6];
         {
             // (lanes beyond the tree carry no target: wconf = 0 there, so g and p x g are exact zeros without a select - their
@@ -703,7 +715,33 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             const Vec3 pxg = cross(pj, gj);
             const float lo[3] = {gj.x, gj.y, gj.z};
             const float hi[3] = {pxg.x, pxg.y, pxg.z};
-            if (PAIR) {
+            if constexpr (!SCAN64) {
+                // fp32: per value an unmasked prefix and a chain prefix, one of them IS the subtree sum.  The values enter through an
+                // empty asm (paired) or the swap's (unpaired): the first add must not be contracted with the product that made them
+                if (PAIR) {
+                    float v6[6] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) asm("" : "+v"(v6[i]));
+                    chain_end_scans(v6, sums, sm1, sm2, sm4, take_u);
+                } else {
+                    // the two triples ride in the two 32-lane halves (g in lanes t, p x g in lanes 32 + t): three values
+                    float w3[3], s3[3];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        float x = lo[i], y = hi[i];
+                        swap32(x, y);                                   // x: lanes t keep g, lanes 32 + t receive p x g of joint t
+                        w3[i] = x;
+                    }
+                    chain_end_scans(w3, s3, sm1, sm2, sm4, take_u);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        float x = s3[i], y = s3[i];
+                        swap32(x, y);                                   // y: lanes t receive the value of lane 32 + t
+                        sums[i] = s3[i];
+                        sums[3 + i] = y;
+                    }
+                }
+            } else if (PAIR) {
                 // both halves carry a tree: six scans, three at a time side by side
                 int zlo = 0, zhi = 0;
 #pragma unroll
@@ -789,7 +827,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         if (isJ) { gs_t[thoff] = gth.x; gs_t[thoff + 1] = gth.y; gs_t[thoff + 2] = gth.z; }
         if (gk_store) gs_t[XS_BETA + gk] = gbeta;
         // the root's subtree is the whole tree: its force sum is d/d transl
-        if (tl == 0) { gs_t[XS_TRANSL] = aj.x; gs_t[XS_TRANSL + 1] = aj.y; gs_t[XS_TRANSL + 2] = aj.z; gs_t[XS - 1] = jloss; }
+        if (joint == 0) { gs_t[XS_TRANSL] = aj.x; gs_t[XS_TRANSL + 1] = aj.y; gs_t[XS_TRANSL + 2] = aj.z; gs_t[XS - 1] = jloss; }
     };
 
     // ---- component role: y = D / scale - c, core part of the quadratic form per frame, publish both ----
@@ -1435,14 +1473,21 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
         if (a.lb_mode == 3 && fpw > 2) fpw = 2;                  // (the optimisers sit on the idle tree waves: two sequences per workgroup)
         a.frames_per_wg = fpw;
         const dim3 grid((a.num_frames + fpw - 1) / fpw), block(MAXW * 64);
+        // (the scan form is the model's: FitArgs::scan64)
+#define K2B_LAUNCH_CHAIN(NBT_, MODE_)                                                                                   \
+    do {                                                                                                                \
+        if (a.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, true>), grid, block, 0, stream, a);         \
+        else hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, false>), grid, block, 0, stream, a);                 \
+    } while (0)
         if (a.lb_mode == 3) {
-            if (a.num_betas <= 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE_SPLIT_LBFGS>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((k2b_fit_world_kernel<16, MODE_SPLIT_LBFGS>), grid, block, 0, stream, a);
+            if (a.num_betas <= 10) K2B_LAUNCH_CHAIN(10, MODE_SPLIT_LBFGS);
+            else K2B_LAUNCH_CHAIN(16, MODE_SPLIT_LBFGS);
             return hipGetLastError();
         }
         if (a.lb_mode != 0) return hipErrorInvalidValue;
-        if (a.num_betas <= 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE_SPLIT>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k2b_fit_world_kernel<16, MODE_SPLIT>), grid, block, 0, stream, a);
+        if (a.num_betas <= 10) K2B_LAUNCH_CHAIN(10, MODE_SPLIT);
+        else K2B_LAUNCH_CHAIN(16, MODE_SPLIT);
+#undef K2B_LAUNCH_CHAIN
         return hipGetLastError();
     }
     // More frames than one full-width launch of the densest shape holds (16 per CU): such a launch runs in rounds of
@@ -1479,7 +1524,11 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
     fpw = fpw < 1 ? 1 : (fpw > cap ? cap : fpw);
     a.frames_per_wg = fpw;
     const dim3 grid((a.num_frames + fpw - 1) / fpw);
-#define K2B_LAUNCH(NBT_, MODE_) hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_>), grid, dim3(Shape<MODE_>::NWAVES * 64), 0, stream, a)
+#define K2B_LAUNCH(NBT_, MODE_)                                                                                                      \
+    do {                                                                                                                            \
+        if (a.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, true>), grid, dim3(Shape<MODE_>::NWAVES * 64), 0, stream, a); \
+        else hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, false>), grid, dim3(Shape<MODE_>::NWAVES * 64), 0, stream, a);   \
+    } while (0)
 #define K2B_LAUNCH_NB(MODE_) do { if (a.num_betas <= 10) K2B_LAUNCH(10, MODE_); else K2B_LAUNCH(16, MODE_); } while (0)
     switch (mode) {
         case MODE_SPLIT: K2B_LAUNCH_NB(MODE_SPLIT); break;

@@ -112,6 +112,7 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     std::vector<float> h_j_template, h_j_dirs;               // host copies
     // fused-fit tables (J == 24 only)
     bool fit_ok = false;
+    bool fit_scan64 = false;                                 // lanes in DFS order and fp64 subtree scans (no scan plan, or K2B_FIT_SCAN64)
     std::string fit_why;
     DevBuf<float> dt, dd;
     DevBuf<int> tree;

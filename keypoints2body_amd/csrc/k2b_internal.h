@@ -17,7 +17,8 @@ constexpr int kMaxShape = 32;       // shape coefficients (betas | expression) o
 constexpr int kFitMaxWaves = 8;     // frames (waves) per workgroup
 constexpr int kMaxJoints = 64;
 constexpr int kMaxRounds = 4;       // pointer-doubling rounds: tree depth < 2^4
-constexpr int kLaneTabStride = 8;   // ints per lane: joint, parent lane, anc[kMaxRounds], subtree size, depth
+constexpr int kLaneTabStride = 9;   // ints per lane: joint, parent lane, anc[kMaxRounds], subtree size, depth, scan flags
+constexpr int kLaneTabScan = 8;     // scan flags of the lane (k2b_scan_plan.h: kScan*), 0 where the model has no scan plan
 // LDS image of the prior: rim rows 64..68 over columns 0..63 as [m][5][64], then mu | c = P mu of rows 0..63 as [m][2][64]
 constexpr int kPriorRimFragEntries = 4 * 21;   // per component: 4 fragments [k-step 2][hi | lo] of 20 live lanes + one zero entry, 16 B each
 constexpr int kPriorImageFloats = 2 * 5 * 64 * 4 + kPriorMaxGauss * 2 * 64 + kPriorMaxGauss * kPriorRimFragEntries * 4;
@@ -41,12 +42,14 @@ struct LbfgsArgs {
 
 struct FitArgs {
     // model (device)
-    // tree tables are indexed by LANE: lanes follow the DFS pre-order of the kinematic tree
+    // tree tables are indexed by LANE: lanes follow the model's scan plan (reversed DFS order with holes, k2b_scan_plan.h) or,
+    // without one, the DFS pre-order of the kinematic tree
     const float* dt;            // [64][3]     J_template[j] - J_template[parent]  (root: J_template[0])
     const float* dd;            // [64][3][16] same for J_dirs, zero padded
     const int* lane_tab;        // [64][kLaneTabStride]
     int num_rounds;             // pointer-doubling rounds needed by the targeted joints of this call
     int num_betas;
+    int scan64;                 // 0: the lane tables carry a scan plan (fp32 chain / end scans); 1: DFS order, fp64 prefix differences
     // prior (device)
     const float* pa_image;      // LDS image, kPriorImageFloats floats (see k2b_api_prior.hip)
     const void* pa_frag32;      // kPriorFrag32Halfs f16

@@ -5,11 +5,71 @@
 
 namespace k2b {
 
-// Inclusive prefix sum inside each 32-lane half with DPP (no LDS traffic): Hillis-Steele inside each
-// row of 16 (row_shr 1, 2, 4, 8; out-of-row sources read 0), then row_bcast:15 into rows 1 and 3.
-// Accumulated in DOUBLE: the subtree sums are differences of two prefixes, and in fp32 their
-// absolute error (eps x the largest prefix) was visible after Adam's per-parameter normalisation
-// (parity 3e-6 -> up to 9e-5); in double the differences are exact to fp32.
+// ---- subtree sums of the fit kernel's tree pass: two forms ----------------------------------------
+// Both are inclusive prefix sums inside each 32-lane half with DPP (no LDS traffic): Hillis-Steele inside each row of 16
+// (row_shr 1, 2, 4, 8; out-of-row sources read 0), then row_bcast:15 into rows 1 and 3.
+//
+// fp32, no difference (chain_end_scans; models with a scan plan, k2b_scan_plan.h).  The tree lanes are in REVERSED DFS order,
+// so a subtree is the lane range that ends at its joint, and every joint takes one of two prefixes as it stands: the unmasked
+// prefix U over the half-wave (its subtree is everything up to its lane) or the prefix C along its own chain, whose steps
+// (shifts 1, 2, 4) are masked per lane so that it stops at the chain's leaf.  Nothing from outside a subtree enters its sum: the
+// error is <= (n - 1) 2^-24 sum |terms of that subtree|, the class of an fp32 autograd sum.
+//
+// fp64, a difference of two prefixes (half_wave_inclusive_scan(s) + a ds_bpermute per sum; every other tree, lanes in DFS order,
+// a subtree = the lane range that STARTS at its joint).  Accumulated in DOUBLE: in fp32 the absolute error of the difference
+// (eps x the largest prefix) was visible after Adam's per-parameter normalisation (parity 3e-6 -> up to 9e-5); in double the
+// differences are exact to fp32.  An fp64 add issues at half the fp32 rate and moves as two DPP copies: four issue slots per
+// scan step against one.
+
+// NS values side by side (3 or 6).  m1, m2, m4: 1.0f where the chain scan's step with that shift adds the lower lane's value, else
+// 0.0f (x 1 and x 0 in a fused multiply-add: the sum is that of a plain add, and a masked step adds an exact zero); take_u: the
+// lane's sum is U, else C.  One instruction per value and step, in place: v_add_f32_dpp for U, v_fmac_f32_dpp for C (a lane whose
+// DPP source lies outside its row, or whose row the row mask leaves out, keeps its value).  Per value the adds are the same in the
+// same order wherever this is inlined.
+// (Inline asm: the compiler forms neither the fused multiply-add with a DPP operand nor the row-masked add - 84 instructions for
+//  six values against 54.  Inside the string nobody inserts the two wait states between a VALU write of a register and a DPP read
+//  of it: the leading s_nop covers the values' producers, and the instructions are ordered step by step over all values, U and C
+//  alternating, so that at least two others lie between a write and the DPP read of the same register - also from the row_shr:8
+//  step to the row_bcast:15 step of three values.)
+#define K2B_SCAN_U(u, ctl) "v_add_f32_dpp " u ", " u ", " u " " ctl " bank_mask:0xf bound_ctrl:1\n\t"
+#define K2B_SCAN_C(c, m, shr) "v_fmac_f32_dpp " c ", " c ", " m " row_shr:" shr " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define K2B_SCAN_STEP3(shr, m) \
+    K2B_SCAN_U("%0", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%3", m, shr) K2B_SCAN_U("%1", "row_shr:" shr " row_mask:0xf") \
+    K2B_SCAN_C("%4", m, shr) K2B_SCAN_U("%2", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%5", m, shr)
+#define K2B_SCAN_STEP6(shr, m) \
+    K2B_SCAN_U("%0", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%6", m, shr) K2B_SCAN_U("%1", "row_shr:" shr " row_mask:0xf") \
+    K2B_SCAN_C("%7", m, shr) K2B_SCAN_U("%2", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%8", m, shr) \
+    K2B_SCAN_U("%3", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%9", m, shr) K2B_SCAN_U("%4", "row_shr:" shr " row_mask:0xf") \
+    K2B_SCAN_C("%10", m, shr) K2B_SCAN_U("%5", "row_shr:" shr " row_mask:0xf") K2B_SCAN_C("%11", m, shr)
+template <int NS>
+__device__ __forceinline__ void chain_end_scans(const float (&v)[NS], float (&s)[NS], float m1, float m2, float m4, bool take_u) {
+    float u[NS], c[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) u[i] = c[i] = v[i];
+    if constexpr (NS == 3)
+        asm("s_nop 1\n\t" K2B_SCAN_STEP3("1", "%6") K2B_SCAN_STEP3("2", "%7") K2B_SCAN_STEP3("4", "%8")
+            K2B_SCAN_U("%0", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%1", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%2", "row_shr:8 row_mask:0xf")
+            K2B_SCAN_U("%0", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%1", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%2", "row_bcast:15 row_mask:0xa")
+            : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(c[0]), "+v"(c[1]), "+v"(c[2])
+            : "v"(m1), "v"(m2), "v"(m4));
+    else if constexpr (NS == 6)
+        asm("s_nop 1\n\t" K2B_SCAN_STEP6("1", "%12") K2B_SCAN_STEP6("2", "%13") K2B_SCAN_STEP6("4", "%14")
+            K2B_SCAN_U("%0", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%1", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%2", "row_shr:8 row_mask:0xf")
+            K2B_SCAN_U("%3", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%4", "row_shr:8 row_mask:0xf") K2B_SCAN_U("%5", "row_shr:8 row_mask:0xf")
+            K2B_SCAN_U("%0", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%1", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%2", "row_bcast:15 row_mask:0xa")
+            K2B_SCAN_U("%3", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%4", "row_bcast:15 row_mask:0xa") K2B_SCAN_U("%5", "row_bcast:15 row_mask:0xa")
+            : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]),
+              "+v"(c[4]), "+v"(c[5])
+            : "v"(m1), "v"(m2), "v"(m4));
+    else static_assert(NS < 0, "no scan group of this size");
+#pragma unroll
+    for (int i = 0; i < NS; ++i) s[i] = take_u ? u[i] : c[i];
+}
+#undef K2B_SCAN_U
+#undef K2B_SCAN_C
+#undef K2B_SCAN_STEP3
+#undef K2B_SCAN_STEP6
+
 __device__ __forceinline__ double half_wave_inclusive_scan(float v) {
     double s = (double)v;
 #define K2B_DPP_ADD64(ctrl, row_mask)                                                                   \

@@ -1,17 +1,18 @@
 """Static instruction counts of the fit kernel's loops from the compiler's assembly.
 usage: hipcc <CXXFLAGS of csrc/Makefile> --cuda-device-only -S k2b_fit.hip -o k2b_fit.s
-       python3 tools/count_fit_valu.py k2b_fit.s [NBT,MODE ...]     (default: 10,3 10,0)
-For every outermost loop of k2b_fit_world_kernel<NBT, MODE> (`loop@<first block>`: all its blocks) and for every basic block
+       python3 tools/count_fit_valu.py k2b_fit.s [NBT,MODE[,SCAN64] ...]     (default: 10,3 10,0; SCAN64 0 = the fp32 scans)
+For every outermost loop of k2b_fit_world_kernel<NBT, MODE, SCAN64> (`loop@<first block>`: all its blocks) and for every basic block
 inside one that holds at least 20 instructions: vector-ALU instructions (mnemonics v_*, without v_mfma*), MFMAs, no-ops, DPP and permlane-swap forms,
-LDS and barrier instructions.  A block's role shows in its marks: `f64` = the tree pass (fp64 scans), `mfma` = the row waves'
+LDS and barrier instructions.  A block's role shows in its marks: `f64` = the tree pass of the fp64 instantiation, `mfma` = the row waves'
 component block, `bar` = it ends an iteration half."""
 import re
 import sys
 from collections import Counter
 
 
-def kernel_body(lines, nbt, mode):
-    sym = re.compile(rf'^_ZN3k2b20k2b_fit_world_kernelILi{nbt}ELi{mode}EEEvNS_7FitArgsE:')
+def kernel_body(lines, nbt, mode, scan64=0):
+    # (assembly from before the SCAN64 parameter has two template arguments: matched for scan64 = 1, which is what it ran)
+    sym = re.compile(rf'^_ZN3k2b20k2b_fit_world_kernelILi{nbt}ELi{mode}E(Lb{scan64}E)' + ('?' if scan64 else '') + r'EEvNS_7FitArgsE:')
     start = next(i for i, l in enumerate(lines) if sym.match(l))
     end = next(i for i in range(start, len(lines)) if lines[i].lstrip().startswith('s_endpgm'))
     return lines[start + 1:end + 1]
@@ -32,8 +33,8 @@ def blocks_of(body):
     return blocks
 
 
-def count(nbt, mode, lines):
-    blocks = blocks_of(kernel_body(lines, nbt, mode))
+def count(nbt, mode, lines, scan64=0):
+    blocks = blocks_of(kernel_body(lines, nbt, mode, scan64))
     index = {name: i for i, (name, _) in enumerate(blocks)}
     in_loop = [False] * len(blocks)
     for i, (_, ins) in enumerate(blocks):
@@ -76,12 +77,12 @@ def count(nbt, mode, lines):
 
 def main():
     lines = open(sys.argv[1]).read().split('\n')
-    insts = [tuple(map(int, a.split(','))) for a in sys.argv[2:]] or [(10, 3), (10, 0)]
+    insts = [(tuple(map(int, a.split(','))) + (0,))[:3] for a in sys.argv[2:]] or [(10, 3, 0), (10, 0, 0)]
     cols = ['all', 'valu', 'mfma', 'nop', 'dpp', 'swap', 'f64', 'mov0', 'cndmask', 'lds', 'bar']
-    for nbt, mode in insts:
-        print(f'k2b_fit_world_kernel<{nbt}, {mode}>')
+    for nbt, mode, scan64 in insts:
+        print(f'k2b_fit_world_kernel<{nbt}, {mode}, {"true" if scan64 else "false"}>')
         print(f'  {"block":<12}' + ''.join(f'{c:>8}' for c in cols))
-        for name, c in count(nbt, mode, lines):
+        for name, c in count(nbt, mode, lines, scan64):
             print(f'  {name:<12}' + ''.join(f'{c[k]:>8}' for k in cols))
 
 
