@@ -50,6 +50,8 @@ typedef struct k2b_ikgat k2b_ikgat; /* IK-GAT rotation regressor (weights + grap
 
 /* Library / ABI version: (major << 16) | minor. */
 uint32_t k2b_version(void);
+/* Marks a declaration with the ABI version that introduced it (documentation only: expands to nothing). */
+#define K2B_SINCE(major, minor)
 /* Message of the last failing call on this thread ("" if none). */
 const char *k2b_last_error(void);
 
@@ -345,6 +347,30 @@ int k2b_fit_sequences_lbfgs(const k2b_model *model, const k2b_prior *prior, cons
 int k2b_lbs(const k2b_model *model, int32_t num_frames, const float *global_orient,
             const float *body_pose, const float *betas, const float *transl,
             float *joints_out, float *vertices_out, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * k2b_lbs_backward (ABI 1.4) — the vector-Jacobian product of k2b_lbs: what `loss.backward()` through `self.smpl(**kwargs)`
+ * computes for a loss over the model's joints and / or vertices.  Parameters as k2b_lbs (transl may be NULL; it is not read:
+ * the forward is affine in it).
+ *   grad_joints   dev [B][J+E+L][3] or NULL: cotangent of joints_out.  The J kinematic rows feed the chain, an extra-vertex row
+ *                 adds to its vertex, a landmark row adds b_k x itself to its three vertices; every row adds to grad_transl
+ *                 (a landmark's with the sum of its weights, as the forward combines translated vertices)
+ *   grad_vertices dev [B][V][3] or NULL: cotangent of vertices_out.  NULL: only the vertices that extra joints and landmarks name
+ *                 are visited (none: no vertex pass at all)
+ *   grad_global_orient [B][3], grad_body_pose [B][3(J-1)], grad_betas [B][NB], grad_transl [B][3]: dev, each may be NULL (not
+ *                 wanted; the others are unchanged by that).  grad_transl is defined whether or not the forward had a transl.
+ * Everything is recomputed from the parameters: the forward saves nothing.  Stream-ordered, launches only; scratch (feature rows,
+ * transforms and B x G x (12 (J + 1) + padded features) floats of partial sums, G <= 16 a function of V) is stream-ordered too.
+ * The FIRST call on a model uploads a small table of its surface rows (blocking).  Sums have one fixed order: a frame's
+ * gradient is bit-identical from run to run, in any batch, at any position.  Models as k2b_lbs; other joint counts:
+ * K2B_ERR_UNSUPPORTED.  NULL model / parameter buffer, or both cotangents NULL: K2B_ERR_INVALID_ARGUMENT before any launch.
+ * num_frames == 0 is a no-op.
+ * ------------------------------------------------------------------------------- */
+int k2b_lbs_backward(const k2b_model *model, int32_t num_frames, const float *global_orient,
+                     const float *body_pose, const float *betas, const float *transl,
+                     const float *grad_joints, const float *grad_vertices,
+                     float *grad_global_orient, float *grad_body_pose, float *grad_betas, float *grad_transl,
+                     void *stream) K2B_SINCE(1, 4);
 
 /* Development: copies the first nbytes (<= 64 KiB) of the model's scratch row (where diagnostic builds leave their
  * in-kernel time stamps) to HOST memory; synchronises the device. */

@@ -69,7 +69,8 @@ def default_init_params(mean_pose, mean_shape, joints_frame, model, joints_categ
     if coordinate_mode == "world":
         if joints_category == "GENERIC":
             m = as_body_model(model)
-            out = m(global_orient=pose[:, :3], body_pose=pose[:, 3:], betas=betas, return_verts=False)
+            with torch.no_grad():                  # the engine's own model calls build no graph
+                out = m(global_orient=pose[:, :3], body_pose=pose[:, 3:], betas=betas, return_verts=False)
             target = torch.as_tensor(joints_frame, dtype=torch.float32).to(m.device)
             transl = (target[:, 0, :] - out.joints[:, 0, :]).detach()
         else:

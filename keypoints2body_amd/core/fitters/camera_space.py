@@ -151,7 +151,8 @@ class CameraSpaceFitter(FitterBase):
         # initial camera translation (camera_space.py:110-134)
         if init_cam_t is None:
             if self.smpl.packed:
-                joints0 = self.smpl(global_orient=go, body_pose=bp, betas=be, return_verts=False).joints
+                with torch.no_grad():              # the engine's own model calls build no graph
+                    joints0 = self.smpl(global_orient=go, body_pose=bp, betas=be, return_verts=False).joints
             else:
                 joints0 = self.smpl.native.lbs(go, bp, be, None, want_vertices=False)[0]
             if not tg["custom"]:

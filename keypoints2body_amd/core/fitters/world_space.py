@@ -58,7 +58,8 @@ def guess_init_transl_from_root(smpl_model, pose_aa, betas, j3d_world_frame, joi
     model = as_body_model(smpl_model)
     root_model, root_target = root_indices(joints_category)
     pose_aa = torch.as_tensor(pose_aa, dtype=torch.float32)
-    out = model(global_orient=pose_aa[:, :3], body_pose=pose_aa[:, 3:], betas=betas, return_verts=False)
+    with torch.no_grad():                          # the engine's own model calls build no graph
+        out = model(global_orient=pose_aa[:, :3], body_pose=pose_aa[:, 3:], betas=betas, return_verts=False)
     target = torch.as_tensor(j3d_world_frame, dtype=torch.float32).to(model.device)
     return (target[:, root_target, :] - out.joints[:, root_model, :]).detach()
 

@@ -161,6 +161,16 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     };
     std::map<std::vector<int>, SurfaceTable> surface_tables;
     uint64_t surface_clock = 0;
+    // k2b_lbs_backward (k2b_lbs_backward.hip): the rows of grad_joints that are vertices, sorted by vertex, built on first use.
+    // One int image (offsets o_*): vertex list [U] | rows [n] | positions in the mesh [n] | positions in the list [n] | item
+    // offsets per chunk of the mesh | per chunk of the list
+    struct LbsBackward {
+        bool built = false;
+        int U = 0, n = 0, L = 0;                             // distinct vertices, items, landmarks the table was built with
+        int o_rows = 0, o_pos_dense = 0, o_pos_compact = 0, o_off_dense = 0, o_off_compact = 0;
+        DevBuf<int> ints;
+        DevBuf<float> w;                                     // [n] weight of every item
+    } bwd;
     std::mutex mu;
 };
 
@@ -194,6 +204,7 @@ int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, 
 int folded_prior(k2b_prior* p, int Dv, const k2b_prior::Folded** out);
 int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<int>& col, hipStream_t stream, SurfaceTermArgs* out);
 int reserve_lbs_workspace(k2b_model* m, int bpad);           // caller holds m->mu
+int lbs_backward_tables(k2b_model* m);                       // caller holds m->mu (k2b_lbs_backward.hip)
 
 // ---- k2b_api_fit.hip: one description of a fit call --------------------------------------------------------------------------
 struct ConstParams { const float *go = nullptr, *bp = nullptr, *be = nullptr, *tr = nullptr; };

@@ -15,6 +15,7 @@ from typing import Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import native, synthetic
 
@@ -23,6 +24,30 @@ from .. import native, synthetic
 SMPLX_POSE_FIELDS = (("body_pose", 63), ("jaw_pose", 3), ("leye_pose", 3), ("reye_pose", 3), ("left_hand_pose", 45),
                      ("right_hand_pose", 45))
 SMPLH_POSE_FIELDS = (("body_pose", 63), ("left_hand_pose", 45), ("right_hand_pose", 45))
+
+
+class _LbsFunction(torch.autograd.Function):
+    """``native.lbs`` with ``native.lbs_backward`` as its (first-order) backward: the four packed parameter tensors are all it
+    saves, the backward kernel recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, model, want_vertices, go, bp, be, tr):
+        ctx.model = model
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None: the joints-only route stays cheap
+        ctx.save_for_backward(go, bp, be, tr)
+        joints, verts = model.lbs(go, bp, be, tr, want_vertices=want_vertices)
+        return joints, verts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_joints, grad_verts):
+        go, bp, be, tr = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[2:6])
+        if (grad_joints is None and grad_verts is None) or not any(want):
+            return (None,) * 6
+        gj = grad_joints.to(torch.float32).contiguous() if grad_joints is not None else None
+        gv = grad_verts.to(torch.float32).contiguous() if grad_verts is not None else None
+        return (None, None) + ctx.model.lbs_backward(go, bp, be, tr, gj, gv, want=want)
 
 
 class BodyModel:
@@ -94,22 +119,29 @@ class BodyModel:
     # -- SMPL-X packing ---------------------------------------------------------------------
     def pack_pose(self, B: int, **kw) -> torch.Tensor:
         """(B, 3 (J - 1)) pose of all non-root joints from smplx keyword arguments (missing ones are zero)."""
+        return self._pack_pose(B, kw, self._as_dev)
+
+    def _pack_pose(self, B: int, kw: dict, conv) -> torch.Tensor:
+        # conv: _as_dev (detached) or _as_dev_graph (differentiable: every keyword receives the gradient of its own slice)
         if not self.packed:
-            return self._as_dev(kw.get("body_pose"), 3 * (self.num_joints - 1)) if kw.get("body_pose") is not None \
+            return conv(kw.get("body_pose"), 3 * (self.num_joints - 1)) if kw.get("body_pose") is not None \
                 else torch.zeros((B, 3 * (self.num_joints - 1)), dtype=torch.float32, device=self.device)
         parts = []
         for name, cols in self.pose_fields:
             x = kw.get(name)
-            t = self._as_dev(x, cols) if x is not None else torch.zeros((B, cols), dtype=torch.float32, device=self.device)
+            t = conv(x, cols) if x is not None else torch.zeros((B, cols), dtype=torch.float32, device=self.device)
             parts.append(t.expand(B, -1) if t.shape[0] != B else t)
         return torch.cat(parts, dim=1).contiguous()
 
     def pack_shape(self, B: int, betas=None, expression=None) -> torch.Tensor:
+        return self._pack_shape(B, betas, expression, self._as_dev)
+
+    def _pack_shape(self, B: int, betas, expression, conv) -> torch.Tensor:
         z = lambda c: torch.zeros((B, c), dtype=torch.float32, device=self.device)
         if not self.packed:
-            return self._as_dev(betas, self.num_shape) if betas is not None else z(self.num_shape)
-        be = self._as_dev(betas, self.num_betas) if betas is not None else z(self.num_betas)
-        ex = self._as_dev(expression, self.num_expression_coeffs) if expression is not None else z(self.num_expression_coeffs)
+            return conv(betas, self.num_shape) if betas is not None else z(self.num_shape)
+        be = conv(betas, self.num_betas) if betas is not None else z(self.num_betas)
+        ex = conv(expression, self.num_expression_coeffs) if expression is not None else z(self.num_expression_coeffs)
         be, ex = (t.expand(B, -1) if t.shape[0] != B else t for t in (be, ex))
         return torch.cat((be, ex), dim=1).contiguous()
 
@@ -150,25 +182,40 @@ class BodyModel:
             raise ValueError(f"expected a (B,{cols}) tensor, got {tuple(t.shape)}")
         return t.to(self.device).contiguous()
 
+    def _as_dev_graph(self, x, cols) -> torch.Tensor:
+        """``_as_dev`` in differentiable torch operations: the result stays attached to `x`."""
+        t = torch.as_tensor(x).to(torch.float32)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.shape[-1] != cols:
+            raise ValueError(f"expected a (B,{cols}) tensor, got {tuple(t.shape)}")
+        return t.to(self.device).contiguous()
+
     def __call__(self, global_orient=None, body_pose=None, betas=None, transl=None,
                  return_full_pose: bool = False, return_verts: bool = True, **unused):
         extra = {k: unused.get(k) for k in ("jaw_pose", "leye_pose", "reye_pose", "left_hand_pose", "right_hand_pose", "expression")}
         given = [x for x in (global_orient, body_pose, betas, transl, *extra.values()) if x is not None]
         B = max((int(torch.as_tensor(x).reshape(-1, torch.as_tensor(x).shape[-1]).shape[0]) for x in given), default=1)
         zeros = lambda c: torch.zeros((B, c), dtype=torch.float32, device=self.device)
-        go = self._as_dev(global_orient, 3) if global_orient is not None else zeros(3)
+        # differentiable route (the backward is k2b_lbs_backward) exactly when a gradient could be asked for; else today's path
+        graph = torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in given)
+        conv = self._as_dev_graph if graph else self._as_dev
+        go = conv(global_orient, 3) if global_orient is not None else zeros(3)
         if self.packed:
-            bp = self.pack_pose(B, body_pose=body_pose, **{k: v for k, v in extra.items() if k != "expression"})
-            be = self.pack_shape(B, betas, extra["expression"])
+            bp = self._pack_pose(B, dict(body_pose=body_pose, **{k: v for k, v in extra.items() if k != "expression"}), conv)
+            be = self._pack_shape(B, betas, extra["expression"], conv)
         else:
             D = 3 * (self.num_joints - 1)
-            bp = self._as_dev(body_pose, D) if body_pose is not None else zeros(D)
-            be = self._as_dev(betas, self.num_betas) if betas is not None else zeros(self.num_betas)
-        tr = self._as_dev(transl, 3) if transl is not None else None
+            bp = conv(body_pose, D) if body_pose is not None else zeros(D)
+            be = conv(betas, self.num_betas) if betas is not None else zeros(self.num_betas)
+        tr = conv(transl, 3) if transl is not None else None
         go, bp, be = (t.expand(B, -1).contiguous() if t.shape[0] != B else t for t in (go, bp, be))
         if tr is not None and tr.shape[0] != B:
             tr = tr.expand(B, -1).contiguous()
-        joints, verts = self.native.lbs(go, bp, be, tr, want_vertices=return_verts)
+        if graph:
+            joints, verts = _LbsFunction.apply(self.native, return_verts, go, bp, be, tr)
+        else:
+            joints, verts = self.native.lbs(go, bp, be, tr, want_vertices=return_verts)
         return SimpleNamespace(vertices=verts, joints=joints, betas=be[:, :self.num_betas], global_orient=go,
                                body_pose=bp[:, :3 * self.NUM_BODY_JOINTS],
                                full_pose=torch.cat((go, bp), dim=1) if return_full_pose else None)

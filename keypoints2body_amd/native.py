@@ -96,6 +96,7 @@ _PROTOTYPES = (
     ("k2b_sequence_order", C.c_int, (_i32, _vp, _vp, _vp, C.POINTER(_i32))),
     ("k2b_shape_pass_lbfgs", C.c_int,
      _FIT_HEAD + (_i32, _vp, _i32, _i32, _vp) + (_vp,) * 5 + (_i32, _i32, _vp, _vp, _i32) + _LBFGS_TAIL + _STREAM),
+    ("k2b_lbs_backward", C.c_int, (_vp, _i32) + (_vp,) * 10 + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -272,6 +273,20 @@ class NativeModel(_Handle):
         verts = torch.empty((B, self.num_vertices, 3), dtype=torch.float32, device=dev) if want_vertices else None
         _launch("k2b_lbs", dev, self._h, B, *params, _ptr(joints), _ptr(verts))
         return joints, verts
+
+    def lbs_backward(self, global_orient, body_pose, betas, transl, grad_joints, grad_vertices, want=(True, True, True, True)):
+        """Vector-Jacobian product of ``lbs``: the gradients of (global_orient, body_pose, betas, transl) for the cotangents
+        `grad_joints` (B,J+E+L,3) and / or `grad_vertices` (B,V,3) (either may be None, not both); an entry of `want` that is
+        false leaves its gradient out (None in the result).  ``transl`` may be None; its gradient is defined all the same."""
+        dev = self.device
+        B = global_orient.shape[0]
+        params = _param_ptrs(self, B, global_orient, body_pose, betas, transl)
+        gj = _dev(grad_joints, "grad_joints", dev, (B, self.num_output_joints, 3))
+        gv = _dev(grad_vertices, "grad_vertices", dev, (B, self.num_vertices, 3))
+        grads = [torch.empty((B, w), dtype=torch.float32, device=dev) if wanted else None
+                 for w, wanted in zip(_param_widths(self), want)]
+        _launch("k2b_lbs_backward", dev, self._h, B, *params, gj, gv, *(_ptr(g) for g in grads))
+        return tuple(grads)
 
 
 class NativePrior(_Handle):
