@@ -197,6 +197,22 @@ __device__ __forceinline__ void adam_update(float& x, float& m, float& v, float 
     x = __builtin_fmaf(-co.x, m * fast_rcp(denom), x);
 }
 
+// Gradient of the priors on one parameter: c_y y (mixture) + c_q d (preserve, shape or translation prior; c_q = 2 w^2) +
+// c_a e2 (bending prior).  Pinned like adam_update: written as a plain sum, the instantiations contracted it in different orders
+// once two of the terms were non-zero (mixture and preserve term on one pose entry), and the launch shapes' gradients
+// differed in the last bit.  Without a preserve term (a first frame) the results are bit for bit what the plain sum gave.
+__device__ __forceinline__ float prior_grad(float c_y, float y, float c_q, float d, float c_a, float e2) {
+    return __builtin_fmaf(c_a, e2, __builtin_fmaf(c_q, d, c_y * y));
+}
+
+// The priors' share of the loss, pinned for the same reason.  A lane's partial: the preserve term fused onto the bending term,
+// then the set-B term c_q d^2 (preserve, shape or translation prior), rounded on its own before it is added - in the 16-wave
+// shape that product crosses lanes first, so no shape may fuse it.  A frame's loss: the mixture's value fused onto the lanes' sum,
+// then the joint term.
+__device__ __forceinline__ float prior_loss_part(float c_p, float d, float bend) { return __builtin_fmaf(c_p * d, d, bend); }
+__device__ __forceinline__ float add_rounded(float sum, float product) { return __builtin_fmaf(1.f, product, sum); }
+__device__ __forceinline__ float frame_loss(float lanes, float c_y, float best, float joint) { return __builtin_fmaf(c_y, best, lanes) + joint; }
+
 // SCAN64: how the tree pass forms its subtree sums (k2b_lanes.h) - false: fp32 chain / end scans on the lanes of the model's scan
 // plan; true: fp64 prefix differences on lanes in DFS order (models without a plan).  A template parameter, not a branch in the
 // tree pass: a run-time-false block there costs the 16-wave shape spilled registers (profiles/HISTORY.md).
@@ -912,10 +928,12 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         // zeros elsewhere), and the angle prior's exp() runs with sign 0 (-> 1, times 0) outside its four lanes.
         const float dA = x0[h] - pr0[h], dB = x1[h] - refB[h];
         const float eA = __expf(x0[h] * angA);
-        const float ga = wpp2 * yA + 2.f * wpr2 * dA + (wa2 * 2.f * angA) * (eA * eA);
-        const float gb = cyB * yBs + 2.f * cqB * dB;
+        // (explicit fused multiply-adds: left to the compiler, the contraction of these sums differed between the instantiations
+        //  once mixture and preserve term were both on, and the shapes' gradients by an ulp)
+        const float ga = prior_grad(wpp2, yA, 2.f * wpr2, dA, (wa2 * 2.f * angA), eA * eA);
+        const float gb = prior_grad(cyB, yBs, 2.f * cqB, dB, 0.f, 0.f);
         float part = 0.f;                  // per-lane partial of the prior losses
-        if (last) part = wpr2 * dA * dA + (angA != 0.f ? wa2 * eA * eA : 0.f) + cqB * dB * dB;
+        if (last) part = add_rounded(prior_loss_part(wpr2, dA, angA != 0.f ? wa2 * eA * eA : 0.f), cqB * dB * dB);
         gp0[h] = ga; gp1[h] = gb; lossp[h] = part; bestv[h] = best;
         }  // frames of this wave
     };
@@ -928,7 +946,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         //  update below needs no branch)
         g0[h] = optA ? gs_r[offA] + gp0[h] : 0.f;
         g1[h] = optB ? gs_r[offB] + gp1[h] : 0.f;
-        if (last) loss_total[h] = wave_sum_fast(lossp[h]) + wpp2 * bestv[h] + gs_r[XS - 1];
+        if (last) loss_total[h] = frame_loss(wave_sum_fast(lossp[h]), wpp2, bestv[h], gs_r[XS - 1]);
 
         // torch.optim.Adam, single-tensor path
         const float2 co = a.adam_coef[it];     // {lr / (1 - b1^t), sqrt(1 - b2^t)}
@@ -1222,17 +1240,17 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             for (int h = 0; h < 2; ++h) {
                 const float dA = xa[h] - pra[h];
                 const float eA = __expf(xa[h] * angA);
-                gpa[h] = wpp2 * yA[h] + 2.f * wpr2 * dA + (wa2 * 2.f * angA) * (eA * eA);
-                if (last) lossp[h] = wpr2 * dA * dA + (angA != 0.f ? wa2 * eA * eA : 0.f);
+                gpa[h] = prior_grad(wpp2, yA[h], 2.f * wpr2, dA, (wa2 * 2.f * angA), eA * eA);
+                if (last) lossp[h] = prior_loss_part(wpr2, dA, angA != 0.f ? wa2 * eA * eA : 0.f);
             }
             const float dQ = xq - refQ;
-            const float gpq = cyQ * yQ + 2.f * cqQ * dQ;
+            const float gpq = prior_grad(cyQ, yQ, 2.f * cqQ, dQ, 0.f, 0.f);
             if (last) {
                 // the set-B share of a frame's prior loss joins the partial of the lane it sits on in the other shapes (lane kq)
                 float pq0 = cqQ * dQ * dQ, pq1 = pq0;
                 swap32(pq0, pq1);                      // pq1: lanes kq < 32 receive the value of lane 32 + kq (frame 1)
-                lossp[0] += hq == 0 ? cqQ * dQ * dQ : 0.f;
-                lossp[1] += hq == 0 ? pq1 : 0.f;
+                lossp[0] = add_rounded(lossp[0], hq == 0 ? cqQ * dQ * dQ : 0.f);
+                lossp[1] = add_rounded(lossp[1], hq == 0 ? pq1 : 0.f);
             }
             K2B_FSTAMP(6);
             __syncthreads();
@@ -1244,7 +1262,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 if (slot0 + h >= F) continue;
                 const float* gs_r = slots + (slot0 + h) * SLOT + XS;
                 const float g = optA ? gs_r[offA] + gpa[h] : 0.f;
-                if (last) { g0o[h] = g; losso[h] = wave_sum_fast(lossp[h]) + wpp2 * bestv[h] + gs_r[XS - 1]; }
+                if (last) { g0o[h] = g; losso[h] = frame_loss(wave_sum_fast(lossp[h]), wpp2, bestv[h], gs_r[XS - 1]); }
                 adam_update(xa[h], ma[h], va[h], g, co, inv_bc2, om_b1, a.beta2, om_b2, a.eps);
             }
             {
