@@ -376,6 +376,35 @@ int k2b_lbs_backward(const k2b_model *model, int32_t num_frames, const float *gl
  * in-kernel time stamps) to HOST memory; synchronises the device. */
 int k2b_debug_read_dump(const k2b_model *model, void *host, int64_t nbytes);
 
+/* Development (ABI 1.5): the device L-BFGS state machine alone, fed a CALLER'S closure results - what k2b_fit_world_lbfgs runs
+ * behind its own closure, one round per call, so that tests can drive every branch of the optimiser with chosen (loss, gradient)
+ * sequences.  No model is involved; the sizes are arguments.
+ * k2b_debug_lbfgs_state_layout: for num_frames optimisers of num_params = 3 + pose_dim + num_betas + 3 parameters and `history`
+ *   pairs, the bytes of the state buffer, the byte offsets of its integer and vector blocks, and the row lengths of the two scalar
+ *   blocks: doubles [num_frames][doubles_per_frame] at offset 0, int32 [num_frames][ints_per_frame] at offset_ints (column order:
+ *   csrc/k2b_lbfgs_device.h).  Host only.
+ * k2b_debug_lbfgs_step: advances the num_frames optimisers by ONE closure result.
+ *   global_orient [B][3], body_pose [B][pose_dim], betas [B][num_betas], transl [B][3] (dev, in / out): the parameter arrays the
+ *     closure would read.  Before the first call they hold the start; after a call, the point whose loss and gradient the next
+ *     call expects (a finished frame: its final point).
+ *   loss dev [B], grad dev [B][num_params] (layout of grad_out above): the closure's result at the arrays' current point.
+ *   state: dev, 16-byte aligned, state_bytes >= the layout's bytes, caller-owned, ZEROED before the first call (all frames in
+ *     phase INIT) and otherwise only ever written by this entry.
+ *   history: ring slots, used as given (k2b_fit_world_lbfgs passes min(history_size, max_iter)); max_eval = max_iter * 5 / 4.
+ *   finalize != 0: no result is consumed (loss / grad may be NULL); every frame's ACCEPTED point goes into the parameter arrays
+ *     (what the fit does behind its last round); the state is not written.
+ *   max_staged_pairs: cap on the history pairs staged in LDS (< 0: none; results do not depend on it).
+ * Everything is checked on the host before any launch: num_params outside [8, 256] or history outside [1, 100]:
+ * K2B_ERR_UNSUPPORTED; pose_dim / num_betas < 1, max_iter outside [1, 10000] (as the fit entries), lr <= 0, a negative
+ * tolerance, a NULL buffer, a state buffer too small or misaligned: K2B_ERR_INVALID_ARGUMENT.  num_frames == 0 is a no-op.  Stream-ordered, one launch. */
+int k2b_debug_lbfgs_state_layout(int32_t num_frames, int32_t num_params, int32_t history, int64_t *state_bytes,
+                                 int64_t *offset_ints, int64_t *offset_vectors, int32_t *doubles_per_frame,
+                                 int32_t *ints_per_frame) K2B_SINCE(1, 5);
+int k2b_debug_lbfgs_step(int32_t num_frames, int32_t pose_dim, int32_t num_betas, float *global_orient, float *body_pose,
+                         float *betas, float *transl, const float *loss, const float *grad, int32_t max_iter,
+                         int32_t history, double lr, double tolerance_grad, double tolerance_change, void *state,
+                         int64_t state_bytes, int32_t finalize, int32_t max_staged_pairs, void *stream) K2B_SINCE(1, 5);
+
 /* ---------------------------------------------------------------------------------
  * Vertex-selected joints in the loss, stand-alone pieces.  `target_model_indices` of the reference
  * (world_space.py:198-201) may name smplx's "extra" joints, which are single mesh vertices

@@ -24,6 +24,26 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 
 _INIT, _BRACKET, _ZOOM, _DONE = 0, 1, 2, 3
+# The line search's "bracket is so small" stop: ``LBFGS.step`` calls ``_strong_wolfe`` WITHOUT its tolerance_change, so inside
+# the line search torch always uses that function's default, whatever the optimiser was given (tests/test_lbfgs_branches.py)
+_LS_TOLERANCE_CHANGE = 1e-9
+
+# Branch record (``BatchedLBFGS(..., record=True)``): every decision a frame takes, in order, as one of these names.  The
+# record is filled from the very masks the code branches on and changes no arithmetic; tests use it to show WHICH parts of the
+# state machine an input exercises (tests/test_lbfgs_branches.py) before the device is compared with this twin on that input.
+EVENTS = (
+    "init_done",                                                     # first gradient already within tolerance_grad
+    "first_step_lr", "first_step_scaled",                            # t = lr min(1, 1 / |g|_1): which side of the min
+    "pair_accepted", "pair_rejected", "pair_rejected_full", "ring_drop",
+    "gtd_exit",                                                      # directional derivative > -tolerance_change
+    "br_armijo", "br_not_below_prev", "br_wolfe_first", "br_wolfe_later", "br_uphill", "br_exhausted_keep0", "br_exhausted_take_t",
+    "ex_clamp_low", "ex_clamp_high", "ex_interior", "ex_bisect",     # the bracket phase's extrapolation
+    "zoom_enter_low0", "zoom_enter_low1",
+    "zr_armijo", "zr_not_below_low", "zr_wolfe", "zr_flip", "zr_low_no_flip", "zr_worse_low1", "zr_better_low1",
+    "zn_insuf_set", "zn_moved_insuf", "zn_moved_edge", "zn_to_high", "zn_to_low", "zn_descending", "zn_bisect", "zn_width_stop",
+    "zn_budget_low0", "zn_budget_low1",
+    "fin_max_iter", "fin_max_eval", "fin_tol_grad", "fin_small_step", "fin_flat", "fin_non_finite", "fin_t0",
+)
 
 
 def _rowdot(a: np.ndarray, b: np.ndarray) -> np.ndarray:
@@ -33,6 +53,11 @@ def _rowdot(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 
 def _cubic(x1, f1, g1, x2, f2, g2, lo=None, hi=None):
     """torch's ``_cubic_interpolate`` on arrays; bounds default to the interval [min(x1, x2), max(x1, x2)]."""
+    return _cubic_masks(x1, f1, g1, x2, f2, g2, lo, hi)[0]
+
+
+def _cubic_masks(x1, f1, g1, x2, f2, g2, lo=None, hi=None):
+    """``_cubic`` and the masks it selects by: (position, clamped to lo, clamped to hi, bisected)."""
     if lo is None:
         lo, hi = np.minimum(x1, x2), np.maximum(x1, x2)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -44,9 +69,12 @@ def _cubic(x1, f1, g1, x2, f2, g2, lo=None, hi=None):
     pos = np.where(x1 <= x2, fwd, bwd)
     # torch: min(max(pos, lo), hi) on Python floats, where max(a, b) is "b if b > a else a": a NaN position STAYS NaN (every
     # comparison with it is false), the step becomes NaN, the next loss is not finite and the frame stops - same here
-    pos = np.where(lo > pos, lo, pos)
-    pos = np.where(hi < pos, hi, pos)
-    return np.where(sq >= 0, pos, 0.5 * (lo + hi))
+    at_lo = lo > pos
+    pos = np.where(at_lo, lo, pos)
+    at_hi = hi < pos
+    pos = np.where(at_hi, hi, pos)
+    real = sq >= 0
+    return np.where(real, pos, 0.5 * (lo + hi)), real & at_lo & ~at_hi, real & at_hi, ~real
 
 
 class BatchedLBFGS:
@@ -55,7 +83,7 @@ class BatchedLBFGS:
 
     def __init__(self, evaluate: Callable[[np.ndarray], Tuple[np.ndarray, np.ndarray]], x0: np.ndarray, *, lr: float,
                  max_iter: int, max_eval: Optional[int] = None, tolerance_grad: float = 1e-7,
-                 tolerance_change: float = 1e-9, history_size: int = 100):
+                 tolerance_change: float = 1e-9, history_size: int = 100, record: bool = False):
         self.evaluate = evaluate
         self.vt = np.float64 if np.asarray(x0).dtype == np.float64 else np.float32     # vectors: float32 like torch's (float64: tests)
         self.x = np.array(x0, dtype=self.vt, copy=True)
@@ -87,6 +115,14 @@ class BatchedLBFGS:
         self.insuf = np.zeros(B, dtype=bool)
         self.x_eval = self.x.copy()
         self.rounds = 0
+        self.events = [[] for _ in range(B)] if record else None      # per frame: the names of EVENTS it took, in order
+
+    def _ev(self, frames, name, mask=None):
+        """Record event `name` for `frames` (those of them where `mask` holds).  No-op unless recording."""
+        if self.events is None:
+            return
+        for i in (frames if mask is None else frames[mask]):
+            self.events[int(i)].append(name)
 
     # ------------------------------------------------------------------------------------------------------------
     def run(self) -> np.ndarray:
@@ -96,12 +132,19 @@ class BatchedLBFGS:
             self._advance(np.asarray(f_new, dtype=np.float64), np.asarray(g_new, dtype=self.vt))
         return self.x
 
+    def advance(self, f_new, g_new) -> None:
+        """One round driven from outside: consume the closure result (losses (B,), gradients (B, P)) at ``x_eval``; the next
+        point to evaluate is ``x_eval`` again.  What ``run`` does per round, and what one call of the device's step kernel does."""
+        self.rounds += 1
+        self._advance(np.asarray(f_new, dtype=np.float64), np.asarray(g_new, dtype=self.vt))
+
     def _advance(self, f_new, g_new):
         ph = self.phase.copy()
         I = np.nonzero(ph == _INIT)[0]
         if I.size:
             self.loss[I], self.g[I], self.evals[I] = f_new[I], g_new[I], 1
             opt = np.abs(self.g[I]).max(axis=1) <= self.tol_g
+            self._ev(I, "init_done", opt)
             self.phase[I[opt]] = _DONE
             self._start_iteration(I[~opt])
         Bk = np.nonzero(ph == _BRACKET)[0]
@@ -123,15 +166,26 @@ class BatchedLBFGS:
             self.d[F] = -self.g[F]
             self.nold[F] = 0
             self.Hdiag[F] = 1.0
-            self.t[F] = np.minimum(1.0, 1.0 / np.abs(self.g[F]).sum(axis=1, dtype=self.vt).astype(np.float64)) * self.lr
+            inv = 1.0 / np.abs(self.g[F]).sum(axis=1, dtype=self.vt).astype(np.float64)
+            self.t[F] = np.minimum(1.0, inv) * self.lr
+            if self.events is not None:
+                scaled = np.minimum(1.0, inv) != 1.0               # (the value the step was made of, not a second comparison)
+                self._ev(F, "first_step_scaled", scaled)
+                self._ev(F, "first_step_lr", ~scaled)
         if N.size:
             y = self.g[N] - self.prev_g[N]
             s = self.d[N] * self.t[N, None].astype(self.vt)
             ys = _rowdot(y, s)
             upd = ys > 1e-10
             U = N[upd]
+            if self.events is not None:
+                was_full = self.nold[N] == self.H
+                self._ev(N, "pair_accepted", upd)
+                self._ev(N, "pair_rejected", ~upd & ~was_full)
+                self._ev(N, "pair_rejected_full", ~upd & was_full)
             if U.size:
                 full = self.nold[U] == self.H
+                self._ev(U, "ring_drop", full)
                 if np.any(full):                                   # shift the history by one (limited memory)
                     W = U[full]
                     self.Y[W, :-1], self.S[W, :-1], self.RO[W, :-1] = self.Y[W, 1:], self.S[W, 1:], self.RO[W, 1:]
@@ -160,6 +214,7 @@ class BatchedLBFGS:
         self.prev_loss[I] = self.loss[I]
         gtd = _rowdot(self.g[I], self.d[I])
         stop = ~(gtd <= -self.tol_c)                               # "gtd > -tolerance_change" (NaN stops too)
+        self._ev(I, "gtd_exit", stop)
         self.phase[I[stop]] = _DONE
         self.x_eval[I[stop]] = self.x[I[stop]]
         L = I[~stop]
@@ -189,8 +244,14 @@ class BatchedLBFGS:
         opt = np.abs(g).max(axis=1) <= self.tol_g
         small_step = np.abs(self.d[L] * t[:, None].astype(self.vt)).max(axis=1) <= self.tol_c
         flat = np.abs(f - self.prev_loss[L]) < self.tol_c
-        stop = (self.n_iter[L] >= self.max_iter) | (self.evals[L] >= self.max_eval) | opt | small_step | flat
-        stop |= ~np.isfinite(f)
+        at_iter, at_eval, bad = self.n_iter[L] >= self.max_iter, self.evals[L] >= self.max_eval, ~np.isfinite(f)
+        stop = at_iter | at_eval | opt | small_step | flat
+        stop |= bad
+        if self.events is not None:
+            self._ev(L, "fin_t0", t == 0.0)
+            for name, m in (("fin_max_iter", at_iter), ("fin_max_eval", at_eval), ("fin_tol_grad", opt), ("fin_small_step", small_step),
+                            ("fin_flat", flat), ("fin_non_finite", bad)):
+                self._ev(L, name, m)                                # (every rule that holds: several may at once)
         self.phase[L[stop]] = _DONE
         self.x_eval[L[stop]] = self.x[L[stop]]
         self._start_iteration(L[~stop])
@@ -203,15 +264,24 @@ class BatchedLBFGS:
         t, f0, gtd0 = self.t[Bk], self.f0[Bk], self.gtd0[Bk]
         gtd_new = _rowdot(g_new, self.d[Bk])
         exhausted = self.ls_iter[Bk] >= self.max_ls[Bk]            # "ls_iter == max_ls": bracket = [0, t], no zoom
-        armijo = (f_new > f0 + c1 * t * gtd0) | ((self.ls_iter[Bk] > 1) & (f_new >= self.f_prev[Bk]))
+        suff, not_below = f_new > f0 + c1 * t * gtd0, (self.ls_iter[Bk] > 1) & (f_new >= self.f_prev[Bk])
+        armijo = suff | not_below
         wolfe = ~armijo & (np.abs(gtd_new) <= -c2 * gtd0)
         uphill = ~armijo & ~wolfe & (gtd_new >= 0)
         to_zoom = ~exhausted & (armijo | uphill)
         done = ~exhausted & wolfe
         cont = ~exhausted & ~armijo & ~wolfe & ~uphill
+        if self.events is not None:
+            self._ev(Bk, "br_armijo", ~exhausted & suff)
+            self._ev(Bk, "br_not_below_prev", ~exhausted & ~suff & not_below)
+            self._ev(Bk, "br_wolfe_first", done & (self.ls_iter[Bk] == 0))
+            self._ev(Bk, "br_wolfe_later", done & (self.ls_iter[Bk] > 0))
+            self._ev(Bk, "br_uphill", ~exhausted & uphill)
         if np.any(exhausted):
             E = Bk[exhausted]
             lower0 = f0[exhausted] <= f_new[exhausted]
+            self._ev(E, "br_exhausted_keep0", lower0)
+            self._ev(E, "br_exhausted_take_t", ~lower0)
             self._finish_line_search(E, np.where(lower0, 0.0, t[exhausted]), np.where(lower0, f0[exhausted], f_new[exhausted]),
                                      np.where(lower0[:, None], self.g0[E], g_new[exhausted]))
         if np.any(done):
@@ -223,14 +293,20 @@ class BatchedLBFGS:
             self.br_gtd[Zn] = np.stack([self.gtd_prev[Zn], gtd_new[to_zoom]], axis=1)
             self.br_g[Zn, 0], self.br_g[Zn, 1] = self.g_prev[Zn], g_new[to_zoom]
             self.low[Zn] = np.where(self.br_f[Zn, 0] <= self.br_f[Zn, 1], 0, 1)
+            self._ev(Zn, "zoom_enter_low0", self.low[Zn] == 0)
+            self._ev(Zn, "zoom_enter_low1", self.low[Zn] == 1)
             self.insuf[Zn] = False
             self.phase[Zn] = _ZOOM
             self._zoom_next(Zn)
         if np.any(cont):
             C = Bk[cont]
             tc, tp = t[cont], self.t_prev[C]
-            t_next = _cubic(tp, self.f_prev[C], self.gtd_prev[C], tc, f_new[cont], gtd_new[cont],
-                            lo=tc + 0.01 * (tc - tp), hi=tc * 10.0)
+            t_next, at_lo, at_hi, bis = _cubic_masks(tp, self.f_prev[C], self.gtd_prev[C], tc, f_new[cont], gtd_new[cont],
+                                                     lo=tc + 0.01 * (tc - tp), hi=tc * 10.0)
+            self._ev(C, "ex_clamp_low", at_lo)
+            self._ev(C, "ex_clamp_high", at_hi)
+            self._ev(C, "ex_interior", ~at_lo & ~at_hi & ~bis)
+            self._ev(C, "ex_bisect", bis)
             self.t_prev[C], self.f_prev[C], self.gtd_prev[C], self.g_prev[C] = tc, f_new[cont], gtd_new[cont], g_new[cont]
             self.t[C] = t_next
             self._issue(C)
@@ -242,22 +318,37 @@ class BatchedLBFGS:
             return
         bt = self.br_t[Z]
         width = np.abs(bt[:, 1] - bt[:, 0])
-        stop = (self.ls_iter[Z] >= self.max_ls[Z]) | (width * self.d_norm[Z] < self.tol_c)
+        budget, narrow = self.ls_iter[Z] >= self.max_ls[Z], width * self.d_norm[Z] < _LS_TOLERANCE_CHANGE
+        stop = budget | narrow
         if np.any(stop):
             S = Z[stop]
             lo = self.low[S]
+            if self.events is not None:
+                self._ev(Z, "zn_budget_low0", budget & (self.low[Z] == 0))
+                self._ev(Z, "zn_budget_low1", budget & (self.low[Z] == 1))
+                self._ev(Z, "zn_width_stop", ~budget & narrow)
             ar = np.arange(S.size)
             self._finish_line_search(S, self.br_t[S][ar, lo], self.br_f[S][ar, lo], self.br_g[S][ar, lo])
         G = Z[~stop]
         if not G.size:
             return
         bt, bf, bg = self.br_t[G], self.br_f[G], self.br_gtd[G]
-        t = _cubic(bt[:, 0], bf[:, 0], bg[:, 0], bt[:, 1], bf[:, 1], bg[:, 1])
+        t, _, _, bis = _cubic_masks(bt[:, 0], bf[:, 0], bg[:, 0], bt[:, 1], bf[:, 1], bg[:, 1])
         hi, lo = bt.max(axis=1), bt.min(axis=1)
         eps = 0.1 * (hi - lo)
         near = np.minimum(hi - t, t - lo) < eps
-        move = near & (self.insuf[G] | (t >= hi) | (t <= lo))
-        t = np.where(move, np.where(np.abs(t - hi) < np.abs(t - lo), hi - eps, lo + eps), t)
+        edge = (t >= hi) | (t <= lo)
+        move = near & (self.insuf[G] | edge)
+        to_high = np.abs(t - hi) < np.abs(t - lo)
+        if self.events is not None:
+            self._ev(G, "zn_descending", bt[:, 0] > bt[:, 1])
+            self._ev(G, "zn_bisect", bis)
+            self._ev(G, "zn_moved_insuf", move & self.insuf[G])
+            self._ev(G, "zn_moved_edge", move & ~self.insuf[G])
+            self._ev(G, "zn_to_high", move & to_high)
+            self._ev(G, "zn_to_low", move & ~to_high)
+            self._ev(G, "zn_insuf_set", near & ~move)
+        t = np.where(move, np.where(to_high, hi - eps, lo + eps), t)
         self.insuf[G] = near & ~move
         self.t[G] = t
         self._issue(G)
@@ -271,7 +362,13 @@ class BatchedLBFGS:
         low = self.low[Z]
         high = 1 - low
         bt, bf, bgtd, bg = self.br_t[Z], self.br_f[Z], self.br_gtd[Z], self.br_g[Z]
-        worse = (f_new > f0 + c1 * t * gtd0) | (f_new >= bf[ar, low])
+        suff, not_below = f_new > f0 + c1 * t * gtd0, f_new >= bf[ar, low]
+        worse = suff | not_below
+        if self.events is not None:
+            self._ev(Z, "zr_armijo", suff)
+            self._ev(Z, "zr_not_below_low", ~suff & not_below)
+            self._ev(Z, "zr_worse_low1", worse & (low == 1))
+            self._ev(Z, "zr_better_low1", ~worse & (low == 1))
         # Armijo violated or not below the lowest point: the trial replaces the HIGH end
         w = np.nonzero(worse)[0]
         bt[w, high[w]], bf[w, high[w]], bgtd[w, high[w]], bg[w, high[w]] = t[w], f_new[w], gtd_new[w], g_new[w]
@@ -280,7 +377,12 @@ class BatchedLBFGS:
         wolfe = np.zeros(Z.size, dtype=bool)
         if b.size:
             wolfe[b] = np.abs(gtd_new[b]) <= -c2 * gtd0[b]
-            flip = b[~wolfe[b] & (gtd_new[b] * (bt[b, high[b]] - bt[b, low[b]]) >= 0)]
+            turn = ~wolfe[b] & (gtd_new[b] * (bt[b, high[b]] - bt[b, low[b]]) >= 0)
+            flip = b[turn]
+            if self.events is not None:
+                self._ev(Z[b], "zr_wolfe", wolfe[b])
+                self._ev(Z[b], "zr_flip", turn)
+                self._ev(Z[b], "zr_low_no_flip", ~wolfe[b] & ~turn)
             bt[flip, high[flip]], bf[flip, high[flip]] = bt[flip, low[flip]], bf[flip, low[flip]]
             bgtd[flip, high[flip]], bg[flip, high[flip]] = bgtd[flip, low[flip]], bg[flip, low[flip]]
             bt[b, low[b]], bf[b, low[b]], bgtd[b, low[b]], bg[b, low[b]] = t[b], f_new[b], gtd_new[b], g_new[b]

@@ -49,8 +49,7 @@ struct LbfgsOpts {
     double lr, tol_g, tol_c;
 };
 // B optimiser instances over the points `p`, reading closure result buffer A of `w`
-k2b::LbfgsArgs make_lbfgs_args(int B, const k2b_model* model, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
-    const int NB = model->NB, D = 3 * (model->J - 1);
+k2b::LbfgsArgs make_lbfgs_args(int B, int D, int NB, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
     k2b::LbfgsArgs la{};
     la.B = B; la.P = 3 + D + NB + 3; la.D = D; la.NB = NB; la.H = o.history;
     la.max_iter = o.max_iter; la.max_eval = o.max_iter * 5 / 4;          // torch's default
@@ -59,6 +58,9 @@ k2b::LbfgsArgs make_lbfgs_args(int B, const k2b_model* model, const LbfgsOpts& o
     la.loss_in = w.lbuf; la.grad_in = w.gbuf;
     la.sd = reinterpret_cast<double*>(w.base); la.si = reinterpret_cast<int*>(w.base + w.off_si); la.sv = reinterpret_cast<float*>(w.base + w.off_sv);
     return la;
+}
+k2b::LbfgsArgs make_lbfgs_args(int B, const k2b_model* model, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
+    return make_lbfgs_args(B, 3 * (model->J - 1), model->NB, o, p, w);
 }
 
 // One device-driven L-BFGS fit of the frames of `at`, whose start is ALREADY in the parameter arrays at.out (in place): state
@@ -362,6 +364,60 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
     TRY_Q(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), be_s, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
                            hipMemcpyDeviceToDevice, stream));
 #undef TRY_Q
+    return K2B_OK;
+}
+
+// Development: the optimiser alone, fed a caller's closure results (include/k2b.h).  The state buffer's layout ...
+int k2b_debug_lbfgs_state_layout(int32_t B, int32_t P, int32_t H, int64_t* state_bytes, int64_t* offset_ints, int64_t* offset_vectors,
+                                 int32_t* doubles_per_frame, int32_t* ints_per_frame) {
+    const char* who = "k2b_debug_lbfgs_state_layout";
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_frames=%d", who, B);
+    if (P < 8 || P > 256) return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (8 to 256)", who, P);
+    if (H < 1 || H > k2b::kLbfgsMaxHistory)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: history=%d (1 to %d)", who, H, k2b::kLbfgsMaxHistory);
+    if (!state_bytes || !offset_ints || !offset_vectors || !doubles_per_frame || !ints_per_frame)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL output", who);
+    size_t off_si = 0, off_sv = 0;
+    *state_bytes = (int64_t)k2b::lbfgs_state_bytes(B, P, H, &off_si, &off_sv);
+    *offset_ints = (int64_t)off_si;
+    *offset_vectors = (int64_t)off_sv;
+    int nd = 0, ni = 0;
+    k2b::lbfgs_state_rows(H, &nd, &ni);
+    *doubles_per_frame = nd;
+    *ints_per_frame = ni;
+    return K2B_OK;
+}
+
+// ... and one step: make_lbfgs_args + launch_lbfgs_step on the caller's buffers, everything checked before the launch.
+int k2b_debug_lbfgs_step(int32_t B, int32_t D, int32_t NB, float* go, float* bp, float* be, float* tr, const float* loss,
+                         const float* grad, int32_t max_iter, int32_t H, double lr, double tolerance_grad, double tolerance_change,
+                         void* state, int64_t state_bytes, int32_t finalize, int32_t max_staged_pairs, void* stream_v) {
+    const char* who = "k2b_debug_lbfgs_step";
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_frames=%d", who, B);
+    if (D < 1 || NB < 1) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: pose_dim=%d, num_betas=%d (at least 1 each)", who, D, NB);
+    const long long P64 = 3ll + D + NB + 3;
+    if (P64 < 8 || P64 > 256) return fail(K2B_ERR_UNSUPPORTED, "%s: %lld parameters per frame (8 to 256)", who, P64);
+    const int P = (int)P64;
+    if (H < 1 || H > k2b::kLbfgsMaxHistory)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: history=%d (1 to %d)", who, H, k2b::kLbfgsMaxHistory);
+    if (max_iter < 1 || max_iter > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: max_iter=%d", who, max_iter);
+    if (!(lr > 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lr must be positive", who);
+    if (!(tolerance_grad >= 0.0) || !(tolerance_change >= 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: negative tolerance", who);
+    if (B == 0) return K2B_OK;
+    if (!go || !bp || !be || !tr || !state) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / state buffer", who);
+    if (!finalize && (!loss || !grad)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL closure result", who);
+    LbfgsWs w{};
+    const size_t need = k2b::lbfgs_state_bytes(B, P, H, &w.off_si, &w.off_sv);
+    if (state_bytes < 0 || (size_t)state_bytes < need)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: state buffer of %lld bytes, %zu needed", who, (long long)state_bytes, need);
+    if (reinterpret_cast<uintptr_t>(state) % 16) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: state buffer not 16-byte aligned", who);
+    w.base = static_cast<unsigned char*>(state);
+    // (a finalize call consumes no result, but the kernel requests the gradient row with the state vectors: any readable rows do)
+    w.lbuf = const_cast<float*>(loss);
+    w.gbuf = const_cast<float*>(grad ? grad : reinterpret_cast<const float*>(w.base + w.off_sv));
+    k2b::LbfgsArgs la = make_lbfgs_args(B, D, NB, {max_iter, H, lr, tolerance_grad, tolerance_change}, {go, bp, be, tr}, w);
+    la.finalize = finalize ? 1 : 0;
+    HIP_TRY_MSG(k2b::launch_lbfgs_step(la, (hipStream_t)stream_v, max_staged_pairs < 0 ? -1 : max_staged_pairs), "%s: launch failed", who);
     return K2B_OK;
 }
 

@@ -69,6 +69,11 @@ size_t lbfgs_state_bytes(int B, int P, int H, size_t* off_si, size_t* off_sv) {
     return n;
 }
 
+void lbfgs_state_rows(int H, int* doubles_per_frame, int* ints_per_frame) {
+    *doubles_per_frame = SD_RO + H;
+    *ints_per_frame = SI_COUNT;
+}
+
 hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_staged_pairs) {
     if (a.B <= 0) return hipSuccess;
     if (a.P > 64 * kEplWide || a.H < 1 || a.H > kLbfgsMaxHistory) return hipErrorInvalidValue;

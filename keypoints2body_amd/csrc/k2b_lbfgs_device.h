@@ -13,7 +13,12 @@ namespace k2b {
 namespace lbfgs_dev {
 
 enum { PH_INIT = 0, PH_BRACKET = 1, PH_ZOOM = 2, PH_DONE = 3 };
-// per-frame scalars (double) and integers
+// per-frame scalars (double) and integers.  THE order of a frame's two state rows: the development entry k2b_debug_lbfgs_step
+// (include/k2b.h) hands the rows back as they are, and the binding names their columns after these enumerators, lower case,
+// without the prefix (native.LBFGS_STATE_DOUBLES / LBFGS_STATE_INTS; tests/test_host_logic.py holds the two together):
+//   doubles [SD_RO + H]: loss, prev_loss, hdiag, t, t_prev, f_prev, gtd_prev, f0, gtd0, dnorm, bt0, bt1, bf0, bf1, bg0, bg1, ro[H]
+//   integers [SI_COUNT]: phase, nold, niter, evals, ls_iter, max_ls, ls_evals, first, low, insuf, head
+// State: the doubles of all frames, then the integers of all frames, then (16-byte aligned) the vectors (lbfgs_state_bytes).
 enum { SD_LOSS, SD_PREV_LOSS, SD_HDIAG, SD_T, SD_T_PREV, SD_F_PREV, SD_GTD_PREV, SD_F0, SD_GTD0, SD_DNORM, SD_BT0, SD_BT1, SD_BF0, SD_BF1,
        SD_BG0, SD_BG1, SD_RO };                      // SD_RO .. SD_RO + H - 1: 1 / (y . s) of the history pairs
 enum { SI_PHASE, SI_NOLD, SI_NITER, SI_EVALS, SI_LS_ITER, SI_MAX_LS, SI_LS_EVALS, SI_FIRST, SI_LOW, SI_INSUF, SI_HEAD, SI_COUNT };
@@ -51,6 +56,17 @@ __device__ __forceinline__ float wave_max_f(float v) {
     K2B_DPP_MAX(0x142, 0xa); K2B_DPP_MAX(0x143, 0xc);
 #undef K2B_DPP_MAX
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// |v| for a maximum that a NaN must win, as torch's Tensor.abs().max() lets it: fmaxf drops a NaN operand, so here a NaN counts
+// as +inf.  Every rule these maxima feed compares "<=" / "<" against a finite bound - false for NaN and for +inf alike -, so a
+// frame whose step or gradient holds a NaN goes on exactly where torch (and the numpy twin) go on, instead of stopping on a
+// "small step" / "small gradient" of 0 (tests/test_gpu_lbfgs_branches.py, the non-finite scripts).
+// (Relies on "a <= FLT_MAX" being FALSE for a NaN: the library is built without fast-math / finite-math-only flags (Makefile), under
+//  which the compiler could fold the comparison away - the non-finite scripts of that test file would then fail.)
+__device__ __forceinline__ float abs_nan_high(float v) {
+    const float a = fabsf(v);
+    return a <= 3.402823466e38f ? a : __builtin_inff();
 }
 
 // torch's _cubic_interpolate on doubles (bounds given, or the interval [min(x1, x2), max(x1, x2)])
@@ -318,7 +334,7 @@ struct Frame {
         double gtd = 0.0;
         float dn = 0.f;
 #pragma unroll
-        for (int k = 0; k < EPL; ++k) { prev_g[k] = g[k]; gtd += (double)g[k] * (double)d[k]; dn = fmaxf(dn, fabsf(d[k])); }
+        for (int k = 0; k < EPL; ++k) { prev_g[k] = g[k]; gtd += (double)g[k] * (double)d[k]; dn = fmaxf(dn, abs_nan_high(d[k])); }
         gtd = wave_sum_d(gtd);
         dn = wave_max_f(dn);
         s.prev_loss = s.loss;
@@ -350,8 +366,8 @@ struct Frame {
             const float ge = gsrc[k];
             x[k] = x[k] + tf * d[k];
             g[k] = ge;
-            gm = fmaxf(gm, fabsf(ge));
-            sm = fmaxf(sm, fabsf(d[k] * tf));
+            gm = fmaxf(gm, abs_nan_high(ge));
+            sm = fmaxf(sm, abs_nan_high(d[k] * tf));
         }
         gm = wave_max_f(gm); sm = wave_max_f(sm);
         s.t = t; s.loss = fv; s.evals += s.ls_evals;
@@ -368,8 +384,10 @@ struct Frame {
 
     // ---- _strong_wolfe: zoom phase, loop head ---------------------------------------------------------------------------------
     __device__ __forceinline__ void zoom_next() {
+        // ("bracket is so small": LBFGS.step calls _strong_wolfe without its tolerance_change, so torch's line search always uses that
+        //  function's default 1e-9, whatever the optimiser was given - a.tol_c is for the outer iteration's rules only)
         const double width = fabs(s.bt1 - s.bt0);
-        if (s.ls_iter >= s.max_ls || width * s.dnorm < a.tol_c) {
+        if (s.ls_iter >= s.max_ls || width * s.dnorm < 1e-9) {
             const int lo = s.low;
             Vec gl;
 #pragma unroll
@@ -480,7 +498,7 @@ __device__ __forceinline__ void lbfgs_consume(Frame<EPL>& fr, double f_new) {
         for (int k = 0; k < EPL; ++k) {
             fr.V[SV_X][k] = fr.has(k) ? *fr.eval_ptr(lane + 64 * k) : 0.f;
             fr.V[SV_G][k] = fr.GN[k];
-            gm = fmaxf(gm, fabsf(fr.GN[k]));
+            gm = fmaxf(gm, abs_nan_high(fr.GN[k]));
         }
         gm = wave_max_f(gm);
         fr.s.loss = f_new; fr.s.evals = 1; fr.s.niter = 0;

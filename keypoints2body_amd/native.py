@@ -97,6 +97,8 @@ _PROTOTYPES = (
     ("k2b_shape_pass_lbfgs", C.c_int,
      _FIT_HEAD + (_i32, _vp, _i32, _i32, _vp) + (_vp,) * 5 + (_i32, _i32, _vp, _vp, _i32) + _LBFGS_TAIL + _STREAM),
     ("k2b_lbs_backward", C.c_int, (_vp, _i32) + (_vp,) * 10 + _STREAM),
+    ("k2b_debug_lbfgs_state_layout", C.c_int, (_i32, _i32, _i32) + (C.POINTER(_i64),) * 3 + (C.POINTER(_i32),) * 2),
+    ("k2b_debug_lbfgs_step", C.c_int, (_i32, _i32, _i32) + (_vp,) * 6 + (_i32, _i32, _f64, _f64, _f64, _vp, _i64, _i32, _i32) + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -515,6 +517,78 @@ def shape_pass_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, se
             _dev(betas, "betas", dev, (S, nb)), _ptr(out), int(max_iter),
             *_lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change))
     return out
+
+
+# ---- development: the device L-BFGS state machine fed a caller's closure results (k2b_debug_lbfgs_step) ------------------------
+# columns of a frame's two scalar state rows, in the order of csrc/k2b_lbfgs_device.h's SD_* / SI_* enumerators
+LBFGS_STATE_DOUBLES = ("loss", "prev_loss", "hdiag", "t", "t_prev", "f_prev", "gtd_prev", "f0", "gtd0", "dnorm", "bt0", "bt1", "bf0",
+                       "bf1", "bg0", "bg1", "ro")
+LBFGS_STATE_INTS = ("phase", "nold", "niter", "evals", "ls_iter", "max_ls", "ls_evals", "first", "low", "insuf", "head")
+
+
+def lbfgs_debug_layout(num_frames: int, num_params: int, history: int) -> dict:
+    """``k2b_debug_lbfgs_state_layout`` (host only): bytes of the optimiser's state buffer, the offsets of its integer and
+    vector blocks and the row lengths of the two scalar blocks."""
+    b, oi, ov, nd, ni = _i64(0), _i64(0), _i64(0), _i32(0), _i32(0)
+    _check(load_library().k2b_debug_lbfgs_state_layout(int(num_frames), int(num_params), int(history), C.byref(b), C.byref(oi),
+                                                       C.byref(ov), C.byref(nd), C.byref(ni)), "k2b_debug_lbfgs_state_layout")
+    return {"bytes": b.value, "offset_ints": oi.value, "offset_vectors": ov.value, "doubles_per_frame": nd.value,
+            "ints_per_frame": ni.value}
+
+
+class LbfgsDebug:
+    """B device optimisers driven one closure result at a time (``k2b_debug_lbfgs_step``): ``params`` are the four parameter
+    arrays (B, 3 | D | NB | 3) holding the start; after ``step(loss, grad)`` they hold the next point to evaluate.  The history
+    is cut to ``min(history_size, max_iter)`` slots as the fit entries cut it."""
+
+    def __init__(self, global_orient, body_pose, betas, transl, *, max_iter: int, lr: float, history_size: int = 100,
+                 tolerance_grad: float = 1e-7, tolerance_change: float = 1e-9, max_staged_pairs: int = -1):
+        self.device = require_device(global_orient.device if isinstance(global_orient, torch.Tensor) else None)
+        B = int(global_orient.shape[0])
+        self.B, self.D, self.NB = B, int(body_pose.shape[1]), int(betas.shape[1])
+        self.P = 3 + self.D + self.NB + 3
+        self.params = (global_orient, body_pose, betas, transl)
+        for t, k, w in zip(self.params, PARAM_KEYS, (3, self.D, self.NB, 3)):
+            _dev(t, k, self.device, (B, w))
+        self.max_iter, self.history = int(max_iter), min(int(history_size), max(int(max_iter), 1))
+        self.tail = (float(lr), float(tolerance_grad), float(tolerance_change))
+        self.max_staged_pairs = int(max_staged_pairs)
+        self.layout = lbfgs_debug_layout(B, self.P, self.history)
+        self.state = torch.zeros(max(self.layout["bytes"], 16), dtype=torch.uint8, device=self.device)     # zeroed: phase INIT
+
+    def _call(self, params, state, loss, grad, finalize):
+        _launch("k2b_debug_lbfgs_step", self.device, self.B, self.D, self.NB, *(_ptr(t) for t in params), loss, grad, self.max_iter,
+                self.history, *self.tail, _ptr(state), int(state.numel()), int(finalize), self.max_staged_pairs)
+
+    def step(self, loss: torch.Tensor, grad: torch.Tensor) -> None:
+        """Consume the closure's result (B,), (B, P) at the point the parameter arrays hold."""
+        self._call(self.params, self.state, _dev(loss, "loss", self.device, (self.B,)), _dev(grad, "grad", self.device, (self.B, self.P)),
+                   0)
+
+    def finalized(self):
+        """The accepted point of every frame, from a finalize call on a COPY of the state and the parameters (the run is not
+        disturbed): (B, P) tensor in the packed layout."""
+        params, state = tuple(t.clone() for t in self.params), self.state.clone()
+        self._call(params, state, None, None, 1)
+        return torch.cat(params, dim=1)
+
+    def point(self) -> torch.Tensor:
+        """The parameter arrays as one (B, P) tensor in the packed layout: the next point to evaluate."""
+        return torch.cat(self.params, dim=1)
+
+    def read_state(self) -> dict:
+        """The per-frame scalars as named host arrays: every name of LBFGS_STATE_INTS (int32 (B,)) and of LBFGS_STATE_DOUBLES
+        (float64 (B,); ``ro``: (B, history))."""
+        raw = self.state.cpu().numpy()
+        L, B = self.layout, self.B
+        sd = raw[: B * L["doubles_per_frame"] * 8].view(np.float64).reshape(B, L["doubles_per_frame"])
+        si = raw[L["offset_ints"]: L["offset_ints"] + B * L["ints_per_frame"] * 4].view(np.int32).reshape(B, L["ints_per_frame"])
+        if L["ints_per_frame"] != len(LBFGS_STATE_INTS) or L["doubles_per_frame"] != len(LBFGS_STATE_DOUBLES) - 1 + self.history:
+            raise RuntimeError("libk2b.so's L-BFGS state rows differ from native.LBFGS_STATE_*")
+        out = {k: si[:, i].copy() for i, k in enumerate(LBFGS_STATE_INTS)}
+        out.update({k: sd[:, i].copy() for i, k in enumerate(LBFGS_STATE_DOUBLES[:-1])})
+        out["ro"] = sd[:, len(LBFGS_STATE_DOUBLES) - 1:].copy()
+        return out
 
 
 def angular_error_deg(pred_rotvec: torch.Tensor, gt_rotvec: torch.Tensor) -> torch.Tensor:

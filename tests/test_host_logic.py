@@ -109,8 +109,70 @@ def test_ctypes_prototypes_match_header_argument_by_argument():
     for name in ("k2b_version", "k2b_last_error", "k2b_fit_config_size"):
         assert not getattr(lib, name).argtypes, name
     assert {n: len(getattr(lib, n).argtypes) for n in ("k2b_fit_world", "k2b_fit_sequence", "k2b_fit_world_lbfgs",
-                                                        "k2b_shape_pass_lbfgs")} == {
-        "k2b_fit_world": 21, "k2b_fit_sequence": 20, "k2b_fit_world_lbfgs": 26, "k2b_shape_pass_lbfgs": 23}
+                                                        "k2b_shape_pass_lbfgs", "k2b_debug_lbfgs_state_layout",
+                                                        "k2b_debug_lbfgs_step")} == {
+        "k2b_fit_world": 21, "k2b_fit_sequence": 20, "k2b_fit_world_lbfgs": 26, "k2b_shape_pass_lbfgs": 23,
+        "k2b_debug_lbfgs_state_layout": 8, "k2b_debug_lbfgs_step": 19}
+
+
+def test_debug_lbfgs_step_refuses_bad_calls_on_the_host_before_any_launch():
+    """``k2b_debug_lbfgs_step`` (ABI 1.5) feeds the device optimiser a caller's closure results, so a test's mistake must be a
+    refusal with a message, never a launch: every check runs on the host first.  (No device is needed for a refusal; the pointers
+    below are never followed.)"""
+    lib = native.load_library()
+    assert lib.k2b_version() >> 16 == 1 and (lib.k2b_version() & 0xffff) >= 5
+    # the two declarations carry ``K2B_SINCE(1, 5)`` behind their argument lists, so their prototypes are held to the header here
+    header = re.sub(r"/\*.*?\*/", " ", (REPO / "include" / "k2b.h").read_text(), flags=re.S)
+    decls = re.findall(r"([\w \*]+?)\b(k2b_debug_lbfgs_\w+)\s*\(([^()]*)\)\s*K2B_SINCE\(1, 5\)\s*;", header)
+    assert [name for _, name, _ in decls] == ["k2b_debug_lbfgs_state_layout", "k2b_debug_lbfgs_step"]
+    kinds = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+    for result, name, args in decls:
+        want = ["pointer" if "*" in a else next(k for k in kinds if re.search(rf"\b{k}\b", a)) for a in args.split(",")]
+        got = ["pointer" if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer) else next(k for k, c in kinds.items() if c is t)
+               for t in getattr(lib, name).argtypes]
+        assert got == want, (name, want, got)
+        assert result.strip() == "int" and getattr(lib, name).restype is ctypes.c_int
+    buf = (ctypes.c_double * 66)()
+    ptr = ctypes.c_void_p((ctypes.addressof(buf) + 15) // 16 * 16)          # 16-byte aligned by construction: only `ptr + 8` is not
+    assert ptr.value % 16 == 0 and ptr.value + 512 <= ctypes.addressof(buf) + ctypes.sizeof(buf)
+    good = dict(B=2, D=60, NB=4, go=ptr, bp=ptr, be=ptr, tr=ptr, loss=ptr, grad=ptr, max_iter=5, H=3, lr=1.0, tol_g=1e-7, tol_c=1e-9,
+                state=ptr, state_bytes=1 << 30, finalize=0, cap=-1, stream=None)
+
+    def call(**kw):
+        rc = lib.k2b_debug_lbfgs_step(*{**good, **kw}.values())
+        return rc, lib.k2b_last_error().decode()
+    inv, uns = native.K2B_ERR_INVALID_ARGUMENT, native.K2B_ERR_UNSUPPORTED
+    for kw, code, text in (
+            (dict(B=-1), inv, "num_frames=-1"), (dict(D=0), inv, "pose_dim=0"), (dict(NB=0), inv, "num_betas=0"),
+            (dict(D=1, NB=0), inv, "num_betas=0"), (dict(D=250, NB=1), uns, "257 parameters per frame"),
+            (dict(D=2 ** 31 - 1, NB=2 ** 31 - 1), uns, "parameters per frame"), (dict(H=0), uns, "history=0"),
+            (dict(H=101), uns, "history=101"), (dict(max_iter=0), inv, "max_iter=0"), (dict(max_iter=10001), inv, "max_iter=10001"), (dict(lr=0.0), inv, "lr must be positive"),
+            (dict(lr=float("nan")), inv, "lr must be positive"), (dict(tol_c=-1.0), inv, "negative tolerance"),
+            (dict(go=None), inv, "NULL parameter / state buffer"), (dict(tr=None), inv, "NULL parameter / state buffer"),
+            (dict(state=None), inv, "NULL parameter / state buffer"), (dict(loss=None), inv, "NULL closure result"),
+            (dict(grad=None), inv, "NULL closure result"), (dict(state_bytes=1000), inv, "state buffer of 1000 bytes"),
+            (dict(state_bytes=-5), inv, "state buffer of -5 bytes"),
+            (dict(state=ctypes.c_void_p(ptr.value + 8)), inv, "not 16-byte aligned")):
+        rc, msg = call(**kw)
+        assert rc == code and text in msg and msg.startswith("k2b_debug_lbfgs_step: "), (kw, rc, msg)
+    assert call(B=0, go=None, state=None)[0] == native.K2B_OK              # an empty batch is a no-op
+    # the layout query: the same limits, and the state's blocks
+    L = native.lbfgs_debug_layout(64, 70, 3)
+    assert L["doubles_per_frame"] == len(native.LBFGS_STATE_DOUBLES) - 1 + 3 and L["ints_per_frame"] == len(native.LBFGS_STATE_INTS)
+    assert L["offset_ints"] == 64 * L["doubles_per_frame"] * 8 and L["offset_vectors"] % 16 == 0
+    assert L["offset_vectors"] >= L["offset_ints"] + 64 * L["ints_per_frame"] * 4
+    assert L["bytes"] == L["offset_vectors"] + 64 * (8 + 2 * 3) * 70 * 4   # eight state vectors and 2 H history vectors per frame
+    for args, exc, text in (((1, 7, 3), NotImplementedError, "7 parameters"), ((1, 257, 3), NotImplementedError, "257 parameters"),
+                            ((1, 70, 0), NotImplementedError, "history=0"), ((-1, 70, 3), ValueError, "num_frames=-1")):
+        with pytest.raises(exc, match=text):
+            native.lbfgs_debug_layout(*args)
+    # the binding names the state rows' columns after the enumerators of csrc/k2b_lbfgs_device.h, in their order
+    dev = (REPO / "keypoints2body_amd" / "csrc" / "k2b_lbfgs_device.h").read_text()
+    sd = re.search(r"enum \{ (SD_LOSS.*?) \};", dev, flags=re.S).group(1)
+    si = re.search(r"enum \{ (SI_PHASE.*?) \};", dev, flags=re.S).group(1)
+    names = lambda text, prefix: tuple(n[len(prefix):].lower() for n in re.findall(rf"\b{prefix}[A-Z0-9_]+", text))
+    assert names(sd, "SD_") == native.LBFGS_STATE_DOUBLES
+    assert names(si, "SI_") == native.LBFGS_STATE_INTS + ("count",)
 
 
 def test_header_is_plain_c_and_struct_size_matches(tmp_path):
