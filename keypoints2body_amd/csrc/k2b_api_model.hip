@@ -344,7 +344,7 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
         const bool streams = K2B_LBS_STREAM && !(tile_env && atoi(tile_env) != 0);
         m->stream = streams && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
         m->stream_x = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
-        m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 25-32 shape coefficients
+        m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 513-544 features: 55 joints from 25 shape coefficients on, 56 from 16
         HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
         std::vector<int> all(V), ex(extra_vertex_ids, extra_vertex_ids + E), tag(V, 0);
         for (int v = 0; v < V; ++v) all[v] = v;

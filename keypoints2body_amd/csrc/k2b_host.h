@@ -121,7 +121,7 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     bool joints_in_mesh = false;                             // every extra joint's vertex is tagged in mesh.w2 (no gather launch)
     bool stream = false;                                     // 17-24 joints and 7 pose k-steps: the stream kernel skins this model
     bool stream_x = false;                                   // 49-56 joints and 16 pose k-steps (SMPL-X): k2b_lbs_stream_x_kernel
-    bool stream_xw = false;                                  // 49-56 joints and 17 pose k-steps (25-32 shape coefficients): k2b_lbs_stream_xw_kernel
+    bool stream_xw = false;                                  // 49-56 joints and 17 pose k-steps (513-544 features: 55 joints with 25-32 shape coefficients, 56 with 16-32): k2b_lbs_stream_xw_kernel
     bool streams() const { return stream || stream_x || stream_xw; }   // one of the stream kernels (none: the tile kernel)
     // tables of the tree fit kernel (any J <= 64), lane order = DFS pre-order
     DevBuf<float> tt_dt, tt_dd;

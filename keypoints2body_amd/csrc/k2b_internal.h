@@ -219,8 +219,8 @@ inline int persistent_grid(int num_cus, long long tiles) {
 // One kernel body (stream_body<S>) behind three entry points, one description S each; the descriptions hold what differs (pose
 // k-steps, X resident or in a ring, fragment counts and products, the counted-wait tables) and live in k2b_lbs_stream.hip.
 //   k2b_lbs_stream_kernel     17-24 joints, 7 pose k-steps (SMPL)                                      launch_skin_stream
-//   k2b_lbs_stream_x_kernel   49-56 joints, 16 pose k-steps (SMPL-H / SMPL-X, <= 24 shape coefficients) launch_skin_stream_x
-//   k2b_lbs_stream_xw_kernel  49-56 joints, 17 pose k-steps (25-32 shape coefficients)                  launch_skin_stream_xw
+//   k2b_lbs_stream_x_kernel   49-56 joints, 16 pose k-steps (<= 512 features: SMPL-H, SMPL-X up to 24 shape coefficients) launch_skin_stream_x
+//   k2b_lbs_stream_xw_kernel  49-56 joints, 17 pose k-steps (513-544 features: SMPL-X with 25-32, 56 joints with 16-32)   launch_skin_stream_xw
 // Every other model with 17-24 or 49-56 joints, and any model created under K2B_LBS_TILE=1, runs the tile kernel.
 // Operands (1 KiB pieces = 64 lanes x 8 halfs in v_mfma_f32_16x16x32_f16 operand order: lane = row + 16 k-group), SMPL:
 //   X   as for the tile kernel
@@ -248,7 +248,7 @@ hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stre
 //   W   [16-vertex tile][5]: hi_0-3, [hi_4-6 | ONES], lo_0-3, [lo_4-6 | 0], [hi_4-6 | tag]
 constexpr int kStreamXKSteps = 16;
 hipError_t launch_skin_stream_x(const StreamArgs& a, int num_cus, hipStream_t stream);
-// SMPL-X with 25-32 shape coefficients: SMPL-X's operands, Pd [k-step 17]
+// 49-56 joints with 513-544 features (SMPL-X with 25-32 shape coefficients; 56 joints from 16 on): SMPL-X's operands, Pd [k-step 17]
 constexpr int kStreamXWKSteps = 17;
 hipError_t launch_skin_stream_xw(const StreamArgs& a, int num_cus, hipStream_t stream);
 hipError_t launch_gather_joints(const float* verts, const int* ids, float* joints, int num_frames, int V, int J, int E,

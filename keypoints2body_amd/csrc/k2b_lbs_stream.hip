@@ -30,8 +30,8 @@
 // its description, under the table that justifies them, and nowhere else.
 //
 // LDS: X slots x 16 KiB + 2 A units = 7 x 16 + 2 x 24 = 4 x 16 + 2 x 48 = 160 KiB.  SMPL: 9 (J - 1) + NB + 2 <= 224 (up to 15
-// shape coefficients); SMPL-X: 9 x 54 + NB + 2 <= 512 features (up to 24 shape coefficients) in 16 k-steps, <= 544 (25-32) in
-// 17; everything else runs the tile kernel.
+// shape coefficients); SMPL-X: 9 x 54 + NB + 2 <= 512 features (up to 24 shape coefficients) in 16 k-steps, <= 544 (25-32; a
+// 56-joint model from 16 coefficients on, 529 at most) in 17; everything else runs the tile kernel.
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
