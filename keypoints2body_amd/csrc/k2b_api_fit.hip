@@ -52,15 +52,9 @@ int classify_targets(const k2b_model* model, const FitCall& c, const int* lane_o
         if (t->lane_target[l] >= 0) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: joint %d is targeted twice", j);
         t->lane_target[l] = k;
         ++t->num_kinematic;
-        t->max_depth = std::max(t->max_depth, model->depth[j]);
+        t->max_depth = std::max(t->max_depth, model->kin.depth[j]);
     }
     return K2B_OK;
-}
-// global transforms are only needed down to the deepest targeted joint: 2^rounds > its depth
-int rounds_for_depth(int depth) {
-    int rounds = 0;
-    while ((1 << rounds) < depth + 1) ++rounds;
-    return rounds;
 }
 int check_surface_targets(const Targets& t, const FitCall& c, int J) {
     if (t.vsel.empty()) return K2B_OK;
@@ -212,7 +206,7 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     if (const int rc = validate_call(model, cfg, c); rc != K2B_OK || c.B == 0) return rc;
     k2b::FitTreeArgs a{};
     Targets t;
-    if (const int rc = classify_targets(model, c, model->tt_lane_of.data(), &t); rc != K2B_OK) return rc;
+    if (const int rc = classify_targets(model, c, model->kin.pos.data(), &t); rc != K2B_OK) return rc;
     memcpy(a.lane_target, t.lane_target, sizeof a.lane_target);
     for (int i = 0; i < 4; ++i) {
         const int ai = cfg->angle_prior_index[i];
@@ -224,28 +218,10 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     if (const int rc = folded_prior(prior, prior_dims, &f); rc != K2B_OK) return rc;
     float2* coef = nullptr;
     if (const int rc = chain_adam_table(model, cfg, c, &coef); rc != K2B_OK) return rc;
-    {   // prior columns of the lane table (depend on prior_dims): uploaded when the value changes.  The state lives in the
-        // model (a per-thread cache keyed by the handle's address would go stale when a handle is destroyed and another one
-        // created at the same address, or when two threads use one model with different values); launches of one model with
-        // DIFFERENT prior_pose_dims must not be in flight on different streams at once.
-        std::lock_guard<std::mutex> lk(model->mu);
-        if (model->tt_prior_dims != prior_dims) {
-            std::vector<int> cols((size_t)64 * 3, -1);
-            for (int i = 0; i < prior_dims; ++i) {               // prior dimension i = component i % 3 of joint 1 + i / 3
-                cols[i * 3 + 0] = model->tt_lane_of[1 + i / 3];
-                cols[i * 3 + 1] = i % 3;
-            }
-            for (int j = 1; j < J; ++j)
-                if (3 * (j - 1) + 2 < prior_dims) cols[model->tt_lane_of[j] * 3 + 2] = 3 * (j - 1);
-            HIP_TRY(hipStreamSynchronize(c.stream));
-            for (int l = 0; l < 64; ++l)
-                HIP_TRY(hipMemcpy(model->tt_tab.get() + l * 8 + 4, cols.data() + l * 3, 3 * sizeof(int), hipMemcpyHostToDevice));
-            model->tt_prior_dims = prior_dims;
-        }
-    }
-    a.dt = model->tt_dt.get(); a.dd = model->tt_dd.get(); a.tab = model->tt_tab.get(); a.anc = model->tt_anc.get();
+    if (const int rc = tree_lane_table(model, prior_dims, &a.tab); rc != K2B_OK) return rc;
+    a.dt = model->tt_dt.get(); a.dd = model->tt_dd.get(); a.anc = model->tt_anc.get();
     a.num_joints = J; a.num_shape = NB;
-    a.num_rounds = rounds_for_depth(t.max_depth);
+    a.num_rounds = k2b::rounds_for_depth(t.max_depth);      // global transforms are only needed down to the deepest targeted joint
     if (J > 63 || a.num_rounds > 4) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the tree kernel takes up to 63 joints and depth 15");
     a.pfrag = prior->frag32.get(); a.ph = f->ph.get(); a.pb = f->pb.get(); a.pmu = f->pmu.get(); a.pcl = f->pcl.get();
     for (int m = 0; m < k2b::kPriorMaxGauss; ++m) a.inv_scale[m] = prior->inv_scale[m];
@@ -282,7 +258,7 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
 
     a.dt = model->dt.get(); a.dd = model->dd.get(); a.lane_tab = model->tree.get();
     a.scan64 = model->fit_scan64 ? 1 : 0;
-    a.num_rounds = rounds_for_depth(t.max_depth);
+    a.num_rounds = k2b::rounds_for_depth(t.max_depth);
     a.num_betas = model->NB;
     a.pa_image = prior->pa_image.get(); a.row_const = prior->row_const.get(); a.neg_log_nllw = prior->nlw.get();
     a.pa_frag32 = prior->frag32.get();

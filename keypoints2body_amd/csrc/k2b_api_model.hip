@@ -5,9 +5,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <numeric>
 
 #include "k2b_host.h"
-#include "k2b_scan_plan.h"
 
 #ifndef K2B_LBS_STREAM
 #define K2B_LBS_STREAM 1      // 0: development builds that keep the tile kernel for 17-24 joint models (A/B timing)
@@ -16,94 +16,20 @@
 using namespace k2b::host;
 
 namespace {
-// LBS B operands of a vertex set (f16 hi/lo, MFMA fragment order; k2b_lbs.hip, k2b_lbs_stream.hip) from HOST constants in which
-// vertex v's rows are those of `ids` (posedirs row stride 3 * V).  tag[i] = 1 + e when vertex i of the set is the vertex of
-// output joint J + e (mesh set only), else 0.
+// LBS B operands of a vertex set from HOST constants in which vertex v's rows are those of `ids`: the images of the model's
+// route (k2b_model_tables.h, vertex_set_images) go up; a stream model has none of the tile kernel's (SMPL-X: 64 MB less per GPU)
 int build_vertex_set(k2b_model* m, VertexSet& vs, const std::vector<int>& ids, const std::vector<int>& tag,
                      const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights, int V) {
-    const int KX = m->k_steps_x, P = m->P, NB = m->NB, J = m->J;
-    const int n = (int)ids.size();
-    vs.num = n;
-    vs.v_tiles = (n + 31) / 32;
-    const int vp = vs.v_tiles * 32;
-    std::vector<k2b::k2b_half> pdh((size_t)KX * 3 * vp * 16, (k2b::k2b_half)0.f), pdl(pdh.size(), (k2b::k2b_half)0.f);
-    for (int i = 0; i < n; ++i) {
-        const int v = ids[i];
-        for (int c = 0; c < 3; ++c) {
-            auto put = [&](int k, k2b::k2b_half hi, k2b::k2b_half lo) {
-                const size_t o = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
-                pdh[o] = hi;
-                pdl[o] = lo;
-            };
-            auto split = [&](int k, float x) -> float {   // returns what two f16 terms leave over
-                const float xs = x * k2b::kPdScale;
-                const k2b::k2b_half hi = (k2b::k2b_half)xs;
-                const k2b::k2b_half lo = (k2b::k2b_half)(xs - (float)hi);
-                put(k, hi, lo);
-                return xs - (float)hi - (float)lo;
-            };
-            for (int k = 0; k < P; ++k) split(k, posedirs[(size_t)k * 3 * V + 3 * v + c]);
-            for (int k = 0; k < NB; ++k) split(P + k, shapedirs[((size_t)v * 3 + c) * NB + k]);
-            const float rest = split(P + NB, v_template[(size_t)v * 3 + c]);
-            // the template is metre-scale: keep its third term as an extra K row (feature = 1)
-            const k2b::k2b_half rh = (k2b::k2b_half)rest;
-            put(P + NB + 1, rh, (k2b::k2b_half)(rest - (float)rh));
-        }
-    }
-    // tile-kernel layout of W: [16-vertex tile][hi groups | lo groups | ONES | ZERO][16 rows][8 joints]
-    const int GA = k2b::tile_groups_a(J), NGP = k2b::tile_ngp(GA), v16 = vs.v_tiles * 2;
-    std::vector<k2b::k2b_half> w2((size_t)v16 * NGP * 128, (k2b::k2b_half)0.f);
-    for (int t = 0; t < v16; ++t)
-        for (int r = 0; r < 16; ++r) {
-            const int i = t * 16 + r;
-            k2b::k2b_half* rowp = w2.data() + ((size_t)t * NGP * 16 + r) * 8;
-            if (i < n)
-                for (int j = 0; j < J; ++j) {
-                    const float w = lbs_weights[(size_t)ids[i] * J + j];
-                    const k2b::k2b_half hi = (k2b::k2b_half)w;
-                    rowp[(size_t)(j >> 3) * 128 + (j & 7)] = hi;
-                    rowp[(size_t)(GA + (j >> 3)) * 128 + (j & 7)] = (k2b::k2b_half)(w - (float)hi);
-                }
-            for (int k = 0; k < 3; ++k) rowp[(size_t)(2 * GA) * 128 + k] = (k2b::k2b_half)1.f;   // ONES: picks up the PAD terms
-            if (i < n && !tag.empty() && tag[i]) rowp[(size_t)(2 * GA + 1) * 128] = (k2b::k2b_half)(float)tag[i];   // ZERO group: joint tag
-        }
-    hipError_t e;
-    if (m->streams()) {
-        // stream kernels: Pd [k-step][16-vertex tile][coord][hi | lo] and W [16-vertex tile][3 or 5 fragments], 1 KiB pieces in
-        // MFMA operand order (lane = row + 16 k-group, 8 halfs); vertex tiles padded to whole 128-vertex groups
-        const int nv16 = (n + 127) / 128 * 8, SK = KX / 2, NWF = m->stream ? 3 : 5;
-        vs.nv16 = nv16;
-        std::vector<k2b::k2b_half> spd((size_t)SK * nv16 * 6 * 512, (k2b::k2b_half)0.f), sw((size_t)nv16 * NWF * 512, (k2b::k2b_half)0.f);
-        for (int i = 0; i < n; ++i) {
-            const int v16 = i >> 4, r = i & 15;
-            for (int c = 0; c < 3; ++c)
-                for (int k = 0; k < KX * 16; ++k) {      // the split values already sit in pdh / pdl: same k, same scale
-                    const size_t src = k2b::frag_elem(((size_t)(k >> 4) * 3 + c) * vs.v_tiles + (i >> 5), k, i);
-                    const size_t dst = ((((size_t)(k >> 5) * nv16 + v16) * 3 + c) * 2) * 512 + (size_t)((((k >> 3) & 3) * 16 + r) * 8 + (k & 7));
-                    spd[dst] = pdh[src];
-                    spd[dst + 512] = pdl[src];
-                }
-            k2b::k2b_half* wt = sw.data() + (size_t)v16 * NWF * 512;
-            auto at = [&](int frag, int group, int k) -> k2b::k2b_half& { return wt[(size_t)frag * 512 + (size_t)((group * 16 + r) * 8 + k)]; };
-            for (int j = 0; j < J; ++j) {
-                const float w = lbs_weights[(size_t)ids[i] * J + j];
-                const k2b::k2b_half hi = (k2b::k2b_half)w, lo = (k2b::k2b_half)(w - (float)hi);
-                const int gj = j >> 3, kj = j & 7;
-                if (m->stream) { at(0, gj, kj) = hi; at(1, gj, kj) = hi; at(2, gj, kj) = lo; }
-                else if (gj < 4) { at(0, gj, kj) = hi; at(2, gj, kj) = lo; }
-                else { at(1, gj - 4, kj) = hi; at(4, gj - 4, kj) = hi; at(3, gj - 4, kj) = lo; }
-            }
-            // last group of the fragment that meets the PAD group of A: ONES; of the one that meets ZERO: the joint tag
-            for (int k = 0; k < 3; ++k) at(m->stream ? 0 : 1, 3, k) = (k2b::k2b_half)1.f;
-            if (!tag.empty() && tag[i]) at(m->stream ? 1 : 4, 3, 0) = (k2b::k2b_half)(float)tag[i];
-        }
-        if ((e = vs.spd.upload(spd.data(), spd.size())) != hipSuccess) return (int)e;
-        if ((e = vs.sw.upload(sw.data(), sw.size())) != hipSuccess) return (int)e;
-    }
-    if (m->streams()) return 0;                      // the tile kernel's images stay on the host (SMPL-X: 64 MB less per GPU)
-    if ((e = vs.w2.upload(w2.data(), w2.size())) != hipSuccess) return (int)e;
-    if ((e = vs.pdh.upload(pdh.data(), pdh.size())) != hipSuccess) return (int)e;
-    if ((e = vs.pdl.upload(pdl.data(), pdl.size())) != hipSuccess) return (int)e;
+    const k2b::tables::VertexSetShape shape{m->J, m->NB, m->P, m->k_steps_x, m->stream ? 3 : m->streams() ? 5 : 0};
+    const k2b::tables::VertexSetImages im = k2b::tables::vertex_set_images(shape, ids, tag, v_template, shapedirs, posedirs, lbs_weights, V);
+    vs.num = (int)ids.size();
+    vs.v_tiles = im.v_tiles;
+    vs.nv16 = im.nv16;
+    const std::pair<DevBuf<k2b::k2b_half>*, const std::vector<k2b::k2b_half>*> images[] = {
+        {&vs.spd, &im.spd}, {&vs.sw, &im.sw}, {&vs.w2, &im.w2}, {&vs.pdh, &im.pdh}, {&vs.pdl, &im.pdl}};
+    for (const auto& [dev, host] : images)
+        if (!host->empty())
+            if (const hipError_t e = dev->upload(host->data(), host->size()); e != hipSuccess) return (int)e;
     return 0;
 }
 
@@ -137,6 +63,97 @@ int set_landmarks_locked(k2b_model* m, int32_t L, const int32_t* vertex_ids, con
     lm.L = L;
     // a workspace reserved before this call covers the landmark vertices too
     if (m->ws_bpad > 0) return reserve_lbs_workspace(m, m->ws_bpad);
+    return K2B_OK;
+}
+
+// ---- the steps of k2b_model_create, in its order -------------------------------------------------------------------------------
+// LBS operands: the route (stream kernels or the tile kernel), then the B side of the two GEMMs for the mesh and the extra joints
+int create_lbs_operands(k2b_model* m, const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights) {
+    const int V = m->V, J = m->J, NB = m->NB, E = m->E;
+    int KX = ((m->P + NB + 2 + 31) / 32) * 2;      // even: the kernels stage 32-deep slices
+    m->groups_a = k2b::tile_groups_a(J);
+    // 49-56 joints with fewer features than SMPL-X (SMPL-H: 477 -> 15 k-steps): one all-zero k-step more buys the stream kernel
+    if (K2B_LBS_STREAM && m->groups_a == 7 && KX < 2 * k2b::kStreamXKSteps) KX = 2 * k2b::kStreamXKSteps;
+    m->k_steps_x = KX;
+    // development switch K2B_LBS_TILE (non-zero): this model is skinned by the tile kernel whatever the stream kernels would
+    // take - their run-time twin.  Per model, fixed here; nothing else reads it.
+    const char* tile_env = getenv("K2B_LBS_TILE");
+    const bool streams = K2B_LBS_STREAM && !(tile_env && atoi(tile_env) != 0);
+    m->stream = streams && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
+    m->stream_x = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
+    m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 513-544 features: 55 joints from 25 shape coefficients on, 56 from 16
+    HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
+    std::vector<int> all(V), tag(V, 0);
+    std::iota(all.begin(), all.end(), 0);
+    // an output joint rides in the W image of its vertex (k2b_lbs.hip) - unless two joints share a vertex or the index
+    // does not fit an f16 integer, in which case the gather launch stays
+    m->joints_in_mesh = E > 0 && E <= 1024;
+    for (int e = 0; e < E && m->joints_in_mesh; ++e) {
+        if (tag[m->h_extra_ids[e]]) m->joints_in_mesh = false;
+        tag[m->h_extra_ids[e]] = e + 1;
+    }
+    if (!m->joints_in_mesh) std::fill(tag.begin(), tag.end(), 0);
+    if (build_vertex_set(m, m->mesh, all, tag, v_template, shapedirs, posedirs, lbs_weights, V) != 0 ||
+        (E > 0 && build_vertex_set(m, m->extra, m->h_extra_ids, std::vector<int>(), v_template, shapedirs, posedirs, lbs_weights, V) != 0))
+        return fail(K2B_ERR_HIP, "k2b_model_create: uploading LBS operands failed");
+    return K2B_OK;
+}
+
+// joint basis: the J x V contraction on the matrix cores, its host copy, and the lane-major image of the pose set-up kernel
+int create_joint_basis(k2b_model* m) {
+    const int V = m->V, J = m->J, NB = m->NB, splits = 32;
+    const int Jp = (J + 15) / 16 * 16, Np = (3 * NB + 15) / 16 * 16;
+    DevBuf<float> ws;
+    HIP_TRY(ws.alloc((size_t)splits * Jp * Np));
+    HIP_TRY(m->j_template.alloc((size_t)J * 3));
+    HIP_TRY(m->j_dirs.alloc((size_t)J * 3 * NB));
+    HIP_TRY(k2b::launch_jreg_contract(m->j_regressor.get(), m->v_template.get(), m->j_template.get(), J, V, 3, ws.get(), splits, nullptr));
+    HIP_TRY(k2b::launch_jreg_contract(m->j_regressor.get(), m->shapedirs.get(), m->j_dirs.get(), J, V, 3 * NB, ws.get(), splits, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    m->h_j_template.resize((size_t)J * 3);
+    m->h_j_dirs.resize((size_t)J * 3 * NB);
+    HIP_TRY(hipMemcpy(m->h_j_template.data(), m->j_template.get(), m->h_j_template.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(m->h_j_dirs.data(), m->j_dirs.get(), m->h_j_dirs.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(ws.reset());
+    // the same numbers lane-major for the pose set-up kernel (lane = joint): one of its loads touches 1-2 cache lines instead
+    // of one per joint
+    std::vector<float> lane((size_t)3 * (1 + NB) * 64, 0.f);
+    for (int j = 0; j < J; ++j)
+        for (int c = 0; c < 3; ++c) {
+            lane[((size_t)c * (1 + NB)) * 64 + j] = m->h_j_template[j * 3 + c];
+            for (int k = 0; k < NB; ++k) lane[((size_t)c * (1 + NB) + 1 + k) * 64 + j] = m->h_j_dirs[((size_t)j * 3 + c) * NB + k];
+        }
+    HIP_TRY(m->j_basis_lane.upload(lane.data(), lane.size()));
+    return K2B_OK;
+}
+
+// tables of the fused fit kernel, by lane (k2b_model_tables.h, fused_tables); empty for a model the kernel does not take
+int create_fused_tables(k2b_model* m) {
+    const k2b::Tree& t = m->kin;
+    bool ok = (m->J == k2b::kFitJoints) && m->NB <= k2b::kMaxBetas;
+    if (!ok) m->fit_why = "the 24-lane fused fit kernel is built for the 24-joint SMPL tree with <= 16 betas";
+    if (ok && (k2b::rounds_for_depth(t.max_depth) > k2b::kMaxRounds || m->J > 32)) { ok = false; m->fit_why = "tree too deep / large for the fused fit kernel"; }
+    // Development switch K2B_FIT_SCAN64 (non-zero): this model gets the DFS placement and the fp64 scans whatever its tree allows -
+    // the run-time twin of the fp32 form.  Per model, fixed here; nothing else reads it.
+    const char* scan_env = getenv("K2B_FIT_SCAN64");
+    k2b::ScanPlan plan;
+    if (ok && !(scan_env && atoi(scan_env) != 0)) plan = k2b::fit_scan_plan(t);
+    m->fit_scan64 = !plan.valid;
+    const k2b::tables::LaneTables f = ok ? k2b::tables::fused_tables(t, plan, m->NB, m->h_j_template.data(), m->h_j_dirs.data()) : k2b::tables::fused_tables_empty();
+    HIP_TRY(m->dt.upload(f.dt.data(), f.dt.size()));
+    HIP_TRY(m->dd.upload(f.dd.data(), f.dd.size()));
+    HIP_TRY(m->tree.upload(f.tab.data(), f.tab.size()));
+    m->fit_ok = ok;
+    return K2B_OK;
+}
+
+// tables of the tree fit kernel (k2b_model_tables.h, tree_tables); the lane table goes up per prior width (tree_lane_table)
+int create_tree_tables(k2b_model* m) {
+    k2b::tables::LaneTables t = k2b::tables::tree_tables(m->kin, m->NB, m->h_j_template.data(), m->h_j_dirs.data());
+    HIP_TRY(m->tt_anc.upload(t.anc.data(), t.anc.size()));
+    HIP_TRY(m->tt_dt.upload(t.dt.data(), t.dt.size()));
+    HIP_TRY(m->tt_dd.upload(t.dd.data(), t.dd.size()));
+    m->h_tt_tab = std::move(t.tab);
     return K2B_OK;
 }
 }  // namespace
@@ -173,6 +190,21 @@ int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, 
     return K2B_OK;
 }
 
+// The tree kernel's lane table for a prior over the first prior_dims pose dimensions (checked by the caller): one immutable
+// [64][8] table per width, built and uploaded on the first use of that width (at most 21 widths of 2 KB: nothing is evicted).
+int tree_lane_table(k2b_model* m, int prior_dims, const int** out) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    auto it = m->tt_tabs.find(prior_dims);
+    if (it == m->tt_tabs.end()) {
+        const std::vector<int> tab = k2b::tables::tree_tab_with_prior(m->h_tt_tab, m->kin, prior_dims);
+        DevBuf<int> dev;
+        HIP_TRY(dev.upload(tab.data(), tab.size()));
+        it = m->tt_tabs.emplace(prior_dims, std::move(dev)).first;
+    }
+    *out = it->second.get();
+    return K2B_OK;
+}
+
 // Compact table of the surface-point term for targets sel[t] (model joint indices >= J) in target columns col[t]: the U distinct
 // vertices in order of first appearance, their rows gathered on the device, the (slot, weight) pairs of every target and the
 // pairs of every vertex (CSR).  Cached per model and selection; the first use of a selection synchronises `stream`.
@@ -190,53 +222,23 @@ int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<i
         *out = it->second.a;
         return K2B_OK;
     }
-    std::vector<int> ids, pair_u(3 * T, 0);
+    std::vector<int> pair_v(3 * T, -1);                      // the pairs of every target: one vertex of weight 1, or a landmark's triangle
     std::vector<float> pair_w(3 * T, 0.f);
-    std::map<int, int> slot;
     for (int t = 0; t < T; ++t) {
         const int j = sel[t];
-        for (int k = 0; k < 3; ++k) {
-            int v;
-            float w;
-            if (j < J + E) {
-                if (k > 0) break;
-                v = m->h_extra_ids[j - J]; w = 1.f;
-            } else {
-                v = m->lmk.h_ids[(j - J - E) * 3 + k]; w = m->lmk.h_w[(j - J - E) * 3 + k];
-            }
-            auto ins = slot.emplace(v, (int)ids.size());
-            if (ins.second) ids.push_back(v);
-            pair_u[t * 3 + k] = ins.first->second;
-            pair_w[t * 3 + k] = w;
-        }
+        if (j < J + E) { pair_v[t * 3] = m->h_extra_ids[j - J]; pair_w[t * 3] = 1.f; continue; }
+        for (int k = 0; k < 3; ++k) { pair_v[t * 3 + k] = m->lmk.h_ids[(j - J - E) * 3 + k]; pair_w[t * 3 + k] = m->lmk.h_w[(j - J - E) * 3 + k]; }
     }
-    const int U = (int)ids.size();
-    std::vector<int> inv_off(U + 1, 0), inv_t;
-    std::vector<float> inv_w;
-    {
-        std::vector<std::vector<std::pair<int, float>>> lists(U);
-        for (int t = 0; t < T; ++t)
-            for (int k = 0; k < 3; ++k)
-                if (pair_w[t * 3 + k] != 0.f) lists[pair_u[t * 3 + k]].push_back({t, pair_w[t * 3 + k]});
-        for (int u = 0; u < U; ++u) {
-            for (const auto& p : lists[u]) { inv_t.push_back(p.first); inv_w.push_back(p.second); }
-            inv_off[u + 1] = (int)inv_t.size();
-        }
-    }
-    const int n = (int)inv_t.size();
+    const k2b::tables::SurfaceIndex ix = k2b::tables::surface_index(T, pair_v, pair_w);
+    const int U = (int)ix.ids.size(), n = (int)ix.inv_t.size();
     // one allocation: floats (vt, sd, pd, lw, pair_w, inv_w), then ints (pair_u, sel_k, inv_off, inv_t, ids)
     const size_t n_tab = (size_t)U * 3 + (size_t)U * 3 * NB + (size_t)PF * 3 * U + (size_t)U * J;
     const size_t n_f = n_tab + 3 * (size_t)T + (size_t)n;
     const size_t n_i = 3 * (size_t)T + T + (U + 1) + (size_t)n + U;
-    std::vector<float> hf(3 * (size_t)T + n);
-    std::copy(pair_w.begin(), pair_w.end(), hf.begin());
-    std::copy(inv_w.begin(), inv_w.end(), hf.begin() + 3 * T);
-    std::vector<int> hi;
-    hi.insert(hi.end(), pair_u.begin(), pair_u.end());
-    hi.insert(hi.end(), col.begin(), col.end());
-    hi.insert(hi.end(), inv_off.begin(), inv_off.end());
-    hi.insert(hi.end(), inv_t.begin(), inv_t.end());
-    hi.insert(hi.end(), ids.begin(), ids.end());
+    std::vector<float> hf(ix.pair_w);
+    hf.insert(hf.end(), ix.inv_w.begin(), ix.inv_w.end());
+    std::vector<int> hi(ix.pair_u);
+    for (const std::vector<int>* part : {&col, &ix.inv_off, &ix.inv_t, &ix.ids}) hi.insert(hi.end(), part->begin(), part->end());
     constexpr size_t kMaxSurfaceTables = 64;
     if (m->surface_tables.size() >= kMaxSurfaceTables) {
         HIP_TRY(hipDeviceSynchronize());                     // a launch in flight may still read the table that leaves
@@ -321,6 +323,7 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
     std::unique_ptr<k2b_model> owner(new k2b_model);
     k2b_model* m = owner.get();
     m->V = V; m->J = J; m->NB = NB; m->E = E; m->P = 9 * (J - 1);
+    m->kin = k2b::Tree(J, parents);
     HIP_TRY(m->v_template.upload(v_template, (size_t)V * 3));
     HIP_TRY(m->shapedirs.upload(shapedirs, (size_t)V * 3 * NB));
     HIP_TRY(m->posedirs.upload(posedirs, (size_t)m->P * 3 * V));
@@ -329,173 +332,10 @@ int k2b_model_create(k2b_model** out, int32_t V, int32_t J, int32_t NB, int32_t 
     HIP_TRY(m->parents.upload(parents, (size_t)J));
     HIP_TRY(m->extra_ids.upload(extra_vertex_ids, (size_t)E));
     m->h_extra_ids.assign(extra_vertex_ids, extra_vertex_ids + E);
-
-    // LBS operands: B side of the two GEMMs, f16 hi/lo in fragment order (k2b_lbs.hip)
-    {
-        const int P = m->P;
-        int KX = ((P + NB + 2 + 31) / 32) * 2;         // even: the kernels stage 32-deep slices
-        m->groups_a = k2b::tile_groups_a(J);
-        // 49-56 joints with fewer features than SMPL-X (SMPL-H: 477 -> 15 k-steps): one all-zero k-step more buys the stream kernel
-        if (K2B_LBS_STREAM && m->groups_a == 7 && KX < 2 * k2b::kStreamXKSteps) KX = 2 * k2b::kStreamXKSteps;
-        m->k_steps_x = KX;
-        // development switch K2B_LBS_TILE (non-zero): this model is skinned by the tile kernel whatever the stream kernels would
-        // take - their run-time twin.  Per model, fixed here; nothing else reads it.
-        const char* tile_env = getenv("K2B_LBS_TILE");
-        const bool streams = K2B_LBS_STREAM && !(tile_env && atoi(tile_env) != 0);
-        m->stream = streams && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
-        m->stream_x = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
-        m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 513-544 features: 55 joints from 25 shape coefficients on, 56 from 16
-        HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
-        std::vector<int> all(V), ex(extra_vertex_ids, extra_vertex_ids + E), tag(V, 0);
-        for (int v = 0; v < V; ++v) all[v] = v;
-        // an output joint rides in the W image of its vertex (k2b_lbs.hip) - unless two joints share a vertex or the index
-        // does not fit an f16 integer, in which case the gather launch stays
-        m->joints_in_mesh = E > 0 && E <= 1024;
-        for (int e = 0; e < E && m->joints_in_mesh; ++e) {
-            if (tag[extra_vertex_ids[e]]) m->joints_in_mesh = false;
-            tag[extra_vertex_ids[e]] = e + 1;
-        }
-        if (!m->joints_in_mesh) std::fill(tag.begin(), tag.end(), 0);
-        if (build_vertex_set(m, m->mesh, all, tag, v_template, shapedirs, posedirs, lbs_weights, V) != 0 ||
-            (E > 0 && build_vertex_set(m, m->extra, ex, std::vector<int>(), v_template, shapedirs, posedirs, lbs_weights, V) != 0))
-            return fail(K2B_ERR_HIP, "k2b_model_create: uploading LBS operands failed");
-    }
-
-    // J x V contraction on the matrix cores
-    {
-        const int splits = 32;
-        const int Jp = (J + 15) / 16 * 16, Np = (3 * NB + 15) / 16 * 16;
-        DevBuf<float> ws;
-        HIP_TRY(ws.alloc((size_t)splits * Jp * Np));
-        HIP_TRY(m->j_template.alloc((size_t)J * 3));
-        HIP_TRY(m->j_dirs.alloc((size_t)J * 3 * NB));
-        HIP_TRY(k2b::launch_jreg_contract(m->j_regressor.get(), m->v_template.get(), m->j_template.get(), J, V, 3, ws.get(), splits, nullptr));
-        HIP_TRY(k2b::launch_jreg_contract(m->j_regressor.get(), m->shapedirs.get(), m->j_dirs.get(), J, V, 3 * NB, ws.get(), splits, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        m->h_j_template.resize((size_t)J * 3);
-        m->h_j_dirs.resize((size_t)J * 3 * NB);
-        HIP_TRY(hipMemcpy(m->h_j_template.data(), m->j_template.get(), m->h_j_template.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(m->h_j_dirs.data(), m->j_dirs.get(), m->h_j_dirs.size() * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(ws.reset());
-        // the same numbers lane-major for the pose set-up kernel (lane = joint): one of its loads touches 1-2 cache lines instead
-        // of one per joint
-        std::vector<float> lane((size_t)3 * (1 + NB) * 64, 0.f);
-        for (int j = 0; j < J; ++j)
-            for (int c = 0; c < 3; ++c) {
-                lane[((size_t)c * (1 + NB)) * 64 + j] = m->h_j_template[j * 3 + c];
-                for (int k = 0; k < NB; ++k) lane[((size_t)c * (1 + NB) + 1 + k) * 64 + j] = m->h_j_dirs[((size_t)j * 3 + c) * NB + k];
-            }
-        HIP_TRY(m->j_basis_lane.upload(lane.data(), lane.size()));
-    }
-
-    // tables of the fused fit kernel, by lane (the placement is chosen below)
-    bool ok = (J == k2b::kFitJoints) && NB <= k2b::kMaxBetas;
-    if (!ok) m->fit_why = "the 24-lane fused fit kernel is built for the 24-joint SMPL tree with <= 16 betas";
-    std::vector<std::vector<int>> children(J);
-    std::vector<int> depth(J, 0);
-    int maxd = 0;
-    for (int j = 1; j < J; ++j) {
-        children[parents[j]].push_back(j);
-        depth[j] = depth[parents[j]] + 1;
-        maxd = depth[j] > maxd ? depth[j] : maxd;
-    }
-    std::vector<int> order, lane_of(J, -1), size(J, 1);
-    {
-        std::vector<int> stack{0};
-        while (!stack.empty()) {
-            const int j = stack.back();
-            stack.pop_back();
-            lane_of[j] = (int)order.size();
-            order.push_back(j);
-            for (auto it = children[j].rbegin(); it != children[j].rend(); ++it) stack.push_back(*it);
-        }
-        for (int j = J - 1; j >= 1; --j) size[parents[j]] += size[j];
-    }
-    int rounds = 0;
-    while ((1 << rounds) < maxd + 1) ++rounds;
-    if (ok && (rounds > k2b::kMaxRounds || J > 32)) { ok = false; m->fit_why = "tree too deep / large for the fused fit kernel"; }
-    m->depth = depth;
-    // Lane placement of the fused kernel.  With a scan plan (k2b_scan_plan.h): reversed DFS order with holes, the subtree sums are
-    // fp32 chain / end scans.  Without one (a junction inside a limb, a chain of more than 8 joints, ...): DFS order, where every
-    // subtree is the lane range that starts at its joint, and the fp64 prefix differences.
-    // Development switch K2B_FIT_SCAN64 (non-zero): this model gets the DFS placement and the fp64 scans whatever its tree allows -
-    // the run-time twin of the fp32 form.  Per model, fixed here; nothing else reads it.
-    const char* scan_env = getenv("K2B_FIT_SCAN64");
-    k2b::ScanPlan plan;
-    if (ok && !(scan_env && atoi(scan_env) != 0)) plan = k2b::fit_scan_plan(J, parents);
-    m->fit_scan64 = !plan.valid;
-    std::vector<int> f_lane_of = lane_of, f_joint_at(k2b::kScanLanes, -1);
-    if (plan.valid) {
-        f_lane_of = plan.lane_of;
-        f_joint_at.assign(plan.joint_at, plan.joint_at + k2b::kScanLanes);
-    } else if (ok) {
-        for (int l = 0; l < J; ++l) f_joint_at[l] = order[l];
-    }
-    std::vector<int> tab((size_t)64 * k2b::kLaneTabStride, -1);
-    for (int l = 0; l < 64; ++l) tab[(size_t)l * k2b::kLaneTabStride + k2b::kLaneTabScan] = 0;
-    std::vector<float> dt((size_t)64 * 3, 0.f), dd((size_t)64 * 3 * k2b::kMaxBetas, 0.f);
-    if (ok) {
-        for (int l = 0; l < k2b::kScanLanes; ++l) {
-            const int j = f_joint_at[l];
-            if (j < 0) continue;                     // a hole or a lane beyond the tree: no joint, zero offset, identity transform
-            const int p = parents[j];
-            int* t = tab.data() + (size_t)l * k2b::kLaneTabStride;
-            t[0] = j;
-            t[1] = p >= 0 ? f_lane_of[p] : -1;
-            // ancestor lane 2^r levels up (pointer doubling), -1 once past the root
-            int anc = t[1];
-            for (int r = 0; r < k2b::kMaxRounds; ++r) {
-                t[2 + r] = anc;
-                for (int s = 0; s < (1 << r) && anc >= 0; ++s) {   // advance 2^r more levels
-                    const int aj = f_joint_at[anc];
-                    anc = parents[aj] >= 0 ? f_lane_of[parents[aj]] : -1;
-                }
-            }
-            t[2 + k2b::kMaxRounds] = size[j];        // DFS placement: subtree = lanes [l, l + size)
-            t[3 + k2b::kMaxRounds] = depth[j];
-            t[k2b::kLaneTabScan] = plan.valid ? plan.flags[l] : 0;
-            for (int c = 0; c < 3; ++c) {
-                dt[l * 3 + c] = m->h_j_template[j * 3 + c] - (p >= 0 ? m->h_j_template[p * 3 + c] : 0.f);
-                for (int k = 0; k < NB; ++k)
-                    dd[(l * 3 + c) * k2b::kMaxBetas + k] =
-                        m->h_j_dirs[(j * 3 + c) * NB + k] - (p >= 0 ? m->h_j_dirs[(p * 3 + c) * NB + k] : 0.f);
-            }
-        }
-    }
-    HIP_TRY(m->dt.upload(dt.data(), dt.size()));
-    HIP_TRY(m->dd.upload(dd.data(), dd.size()));
-    HIP_TRY(m->tree.upload(tab.data(), tab.size()));
-    m->fit_ok = ok;
-    {   // tree fit kernel: [64][8] lane table (prior columns filled per call), rest offsets and their shape directions
-        std::vector<int> tt((size_t)64 * 8, -1);
-        std::vector<float> tdt((size_t)64 * 3, 0.f), tdd((size_t)64 * 3 * k2b::kMaxShape, 0.f);
-        for (int l = 0; l < 64; ++l) { tt[l * 8 + 1] = 0; tt[l * 8 + 2] = 1; tt[l * 8 + 3] = 1000; }
-        for (int l = 0; l < J; ++l) {
-            const int j = order[l], p = parents[j];
-            tt[l * 8 + 0] = j; tt[l * 8 + 1] = p >= 0 ? lane_of[p] : 0; tt[l * 8 + 2] = size[j]; tt[l * 8 + 3] = depth[j];
-            for (int c = 0; c < 3; ++c) {
-                tdt[l * 3 + c] = m->h_j_template[j * 3 + c] - (p >= 0 ? m->h_j_template[p * 3 + c] : 0.f);
-                for (int k = 0; k < NB; ++k)
-                    tdd[(l * 3 + c) * k2b::kMaxShape + k] =
-                        m->h_j_dirs[(j * 3 + c) * NB + k] - (p >= 0 ? m->h_j_dirs[(p * 3 + c) * NB + k] : 0.f);
-            }
-        }
-        // ancestors 1, 2, 4, 8 levels up (pointer doubling); 63 = "none": a lane that is no joint and holds the identity
-        std::vector<int> tanc((size_t)64 * 4, 63);
-        if (J <= 63)
-            for (int l = 0; l < J; ++l) {
-                int aj = order[l];
-                for (int r = 0, dist = 0; r < 4; ++r) {
-                    for (; dist < (1 << r) && aj >= 0; ++dist) aj = parents[aj];
-                    tanc[l * 4 + r] = aj >= 0 ? lane_of[aj] : 63;
-                }
-            }
-        m->tt_lane_of = lane_of;
-        HIP_TRY(m->tt_anc.upload(tanc.data(), tanc.size()));
-        HIP_TRY(m->tt_dt.upload(tdt.data(), tdt.size()));
-        HIP_TRY(m->tt_dd.upload(tdd.data(), tdd.size()));
-        HIP_TRY(m->tt_tab.upload(tt.data(), tt.size()));
-    }
+    if (const int rc = create_lbs_operands(m, v_template, shapedirs, posedirs, lbs_weights); rc != K2B_OK) return rc;
+    if (const int rc = create_joint_basis(m); rc != K2B_OK) return rc;
+    if (const int rc = create_fused_tables(m); rc != K2B_OK) return rc;
+    if (const int rc = create_tree_tables(m); rc != K2B_OK) return rc;
     *out = owner.release();
     return K2B_OK;
 }
@@ -507,7 +347,7 @@ int k2b_dev_fit_scan_plan(int32_t J, const int32_t* parents, int32_t* lane_of, i
     if (J < 1 || J > k2b::kMaxJoints || !parents || !lane_of || !lane_flags || parents[0] >= 0) return -1;
     for (int j = 1; j < J; ++j)
         if (parents[j] < 0 || parents[j] >= j) return -1;
-    const k2b::ScanPlan plan = k2b::fit_scan_plan(J, parents);
+    const k2b::ScanPlan plan = k2b::fit_scan_plan(k2b::Tree(J, parents));
     if (!plan.valid) return 0;
     for (int j = 0; j < J; ++j) lane_of[j] = plan.lane_of[j];
     for (int l = 0; l < k2b::kScanLanes; ++l) lane_flags[l] = plan.flags[l];

@@ -12,6 +12,7 @@
 
 #include "../../include/k2b.h"
 #include "k2b_internal.h"
+#include "k2b_model_tables.h"
 
 namespace k2b {
 namespace host __attribute__((visibility("hidden"))) {
@@ -116,18 +117,18 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     std::string fit_why;
     DevBuf<float> dt, dd;
     DevBuf<int> tree;
-    std::vector<int> depth;                                  // depth of every joint (root 0)
+    k2b::Tree kin;                                           // the kinematic tree (k2b_tree.h): DFS order, depth of every joint
     VertexSet mesh, extra;                                   // the whole mesh and the E extra-joint vertices
     bool joints_in_mesh = false;                             // every extra joint's vertex is tagged in mesh.w2 (no gather launch)
     bool stream = false;                                     // 17-24 joints and 7 pose k-steps: the stream kernel skins this model
     bool stream_x = false;                                   // 49-56 joints and 16 pose k-steps (SMPL-X): k2b_lbs_stream_x_kernel
     bool stream_xw = false;                                  // 49-56 joints and 17 pose k-steps (513-544 features: 55 joints with 25-32 shape coefficients, 56 with 16-32): k2b_lbs_stream_xw_kernel
     bool streams() const { return stream || stream_x || stream_xw; }   // one of the stream kernels (none: the tile kernel)
-    // tables of the tree fit kernel (any J <= 64), lane order = DFS pre-order
+    // tables of the tree fit kernel (any J <= 64), lane order = DFS pre-order (lane of joint j: kin.pos[j])
     DevBuf<float> tt_dt, tt_dd;
-    DevBuf<int> tt_tab, tt_anc;
-    int tt_prior_dims = -1;                                  // what the prior columns of tt_tab currently describe (guarded by mu)
-    std::vector<int> tt_lane_of;                             // lane of every joint
+    DevBuf<int> tt_anc;
+    std::vector<int> h_tt_tab;                               // host: the [64][8] lane table with empty prior columns
+    std::map<int, DevBuf<int>> tt_tabs;                      // the lane table per prior width, built on first use, never written after its upload (guarded by mu)
     int groups_a = 0;                                        // GA = ceil(J / 8)
     DevBuf<k2b::k2b_half> wsA2;                              // per-frame A operand of the tile kernel
     DevBuf<float> dump;                                      // 64 x 3 floats: store target of lanes outside the batch
@@ -164,10 +165,9 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     // k2b_lbs_backward (k2b_lbs_backward.hip): the rows of grad_joints that are vertices, sorted by vertex, built on first use.
     // One int image (offsets o_*): vertex list [U] | rows [n] | positions in the mesh [n] | positions in the list [n] | item
     // offsets per chunk of the mesh | per chunk of the list
-    struct LbsBackward {
+    struct LbsBackward : k2b::tables::BackwardOffsets {
         bool built = false;
-        int U = 0, n = 0, L = 0;                             // distinct vertices, items, landmarks the table was built with
-        int o_rows = 0, o_pos_dense = 0, o_pos_compact = 0, o_off_dense = 0, o_off_compact = 0;
+        int L = 0;                                           // landmarks the table was built with
         DevBuf<int> ints;
         DevBuf<float> w;                                     // [n] weight of every item
     } bwd;
@@ -203,6 +203,7 @@ namespace host __attribute__((visibility("hidden"))) {
 int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, float2** out);
 int folded_prior(k2b_prior* p, int Dv, const k2b_prior::Folded** out);
 int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<int>& col, hipStream_t stream, SurfaceTermArgs* out);
+int tree_lane_table(k2b_model* m, int prior_dims, const int** out);
 int reserve_lbs_workspace(k2b_model* m, int bpad);           // caller holds m->mu
 int lbs_backward_tables(k2b_model* m);                       // caller holds m->mu (k2b_lbs_backward.hip)
 

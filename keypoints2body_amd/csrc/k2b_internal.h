@@ -6,19 +6,15 @@
 #include <atomic>
 
 #include "k2b_device.h"
+#include "k2b_layout.h"
 
 namespace k2b {
 
 constexpr int kFitJoints = 24;      // joints of the tree the fused fit kernel is built for (SMPL)
 constexpr int kPriorDim = 69;       // 3 * (kFitJoints - 1)
 constexpr int kPriorMaxGauss = 8;   // mixture components resident in LDS
-constexpr int kMaxBetas = 16;       // shape coefficients of the 24-joint fused fit kernel
-constexpr int kMaxShape = 32;       // shape coefficients (betas | expression) of the LBS kernels and the tree fit kernel
 constexpr int kFitMaxWaves = 8;     // frames (waves) per workgroup
 constexpr int kMaxJoints = 64;
-constexpr int kMaxRounds = 4;       // pointer-doubling rounds: tree depth < 2^4
-constexpr int kLaneTabStride = 9;   // ints per lane: joint, parent lane, anc[kMaxRounds], subtree size, depth, scan flags
-constexpr int kLaneTabScan = 8;     // scan flags of the lane (k2b_scan_plan.h: kScan*), 0 where the model has no scan plan
 // LDS image of the prior: rim rows 64..68 over columns 0..63 as [m][5][64], then mu | c = P mu of rows 0..63 as [m][2][64]
 constexpr int kPriorRimFragEntries = 4 * 21;   // per component: 4 fragments [k-step 2][hi | lo] of 20 live lanes + one zero entry, 16 B each
 constexpr int kPriorImageFloats = 2 * 5 * 64 * 4 + kPriorMaxGauss * 2 * 64 + kPriorMaxGauss * kPriorRimFragEntries * 4;
@@ -97,7 +93,6 @@ struct FitArgs {
 hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
 
 // Kernel arguments of the fused fit for large trees (k2b_fit_tree.hip: 25..64 joints, SMPL-H / SMPL-X).
-typedef _Float16 k2b_half;
 struct FitTreeArgs {
     // model (device), indexed by LANE (DFS pre-order of the kinematic tree)
     const float* dt;            // [64][3]      rest offset from the parent at shape 0 (root: its rest joint)
@@ -150,16 +145,6 @@ struct ShapePassArgs {
 hipError_t launch_shape_prep(const ShapePassArgs& a, hipStream_t stream);
 hipError_t launch_shape_reduce(const ShapePassArgs& a, hipStream_t stream);
 
-// LBS operands are f16 hi/lo pairs in MFMA fragment order: [k-step][row][16 halfs].
-constexpr float kPdScale = 256.0f;   // power-of-two scale of the vertex-GEMM B operand (keeps f16 lo terms normal)
-
-// Element (k, row) inside piece number `frag` of a piece-ordered operand: a piece is the
-// 1 KiB a wave moves for one 16-deep k-step of one 32-row tile, stored lane-linear:
-// [h = (k >> 3) & 1][row & 31][k & 7]  (lane 32 h + row owns 16 contiguous bytes).
-__host__ __device__ inline size_t frag_elem(size_t frag, int k, int row) {
-    return ((frag * 2 + ((k >> 3) & 1)) * 32 + (row & 31)) * 8 + (k & 7);
-}
-
 // Pose set-up for LBS: per frame the relative transforms A_j (3x4) and the feature vector
 // X = [vec(R_1..R_{J-1} - I) | beta | 1 | 1] as f16 hi/lo MFMA operands, plus the posed
 // kinematic joints (+ transl).
@@ -188,9 +173,7 @@ int lbs_frames_padded(int num_frames);
 // lo.hi) are ONE contraction over the concatenated group sequences  A: hi | hi | lo | PAD,  W: hi | lo | hi | ONES
 // (3 GA + 1 groups, padded to a multiple of four with ZERO): ceil((3 GA + 1) / 4) MFMAs of depth 32 per output tile, no
 // padding of J to 16, and the PAD x ONES position adds the frame's translation (three f16 terms) to the entries 3, 7, 11
-// inside the GEMM.
-constexpr int tile_groups_a(int J) { return (J + 7) / 8; }
-constexpr int tile_ngp(int GA) { return 2 * GA + 2; }
+// inside the GEMM.  (tile_groups_a, tile_ngp: k2b_layout.h)
 struct TileArgs {
     const k2b_half *xh, *xl;     // X fragments [k_steps_x][f_tiles]          (pose set-up)
     const k2b_half *a2;          // A groups    [2 f_tiles][12][NGP][16][8]   (pose set-up)

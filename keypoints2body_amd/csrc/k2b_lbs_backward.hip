@@ -489,50 +489,21 @@ hipError_t launch_dense(const BwdArgs& a, hipStream_t stream) {
 
 namespace host {
 
-// The rows of grad_joints that are vertices (extra joints, landmark corners), sorted by vertex, for both vertex sets of the dense
-// launch; built on the first backward call of a model (blocking upload).  Caller holds m->mu.
+// The rows of grad_joints that are vertices (extra joints, landmark corners) as k2b_model_tables.h (lbs_backward_image) lays them
+// out; built on the first backward call of a model (blocking upload).  Caller holds m->mu.
 int lbs_backward_tables(k2b_model* m) {
     k2b_model::LbsBackward& t = m->bwd;
     if (t.built && t.L == m->lmk.L) return K2B_OK;
     if (t.built) HIP_TRY(hipDeviceSynchronize());               // landmarks arrived after a backward call: nothing may still read the old table
-    struct Item { int vid, row; float w; };
-    std::vector<Item> items;
+    std::vector<tables::BackwardItem> items;
     for (int e = 0; e < m->E; ++e) items.push_back({m->h_extra_ids[e], m->J + e, 1.f});
     for (int l = 0; l < m->lmk.L; ++l)
         for (int k = 0; k < 3; ++k) items.push_back({m->lmk.h_ids[3 * l + k], m->J + m->E + l, m->lmk.h_w[3 * l + k]});
-    std::stable_sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.vid < y.vid; });
-    const int n = (int)items.size();
-    std::vector<int> vlist;
-    for (const Item& it : items)
-        if (vlist.empty() || vlist.back() != it.vid) vlist.push_back(it.vid);
-    const int U = (int)vlist.size();
-    const int nc_dense = (m->V + kBwdChunk - 1) / kBwdChunk, nc_compact = (U + kBwdChunk - 1) / kBwdChunk;
-    // one int image: vlist [U] | rows [n] | dense positions [n] | compact positions [n] | dense offsets | compact offsets
-    std::vector<int> img;
-    std::vector<float> w(n);
-    t.o_rows = U; t.o_pos_dense = U + n; t.o_pos_compact = U + 2 * n; t.o_off_dense = U + 3 * n; t.o_off_compact = t.o_off_dense + nc_dense + 1;
-    img.resize((size_t)t.o_off_compact + nc_compact + 1);
-    std::copy(vlist.begin(), vlist.end(), img.begin());
-    std::vector<int> cpos(n);
-    for (int i = 0, u = 0; i < n; ++i) {
-        while (vlist[u] != items[i].vid) ++u;
-        cpos[i] = u;
-        img[t.o_rows + i] = items[i].row;
-        img[t.o_pos_dense + i] = items[i].vid;
-        img[t.o_pos_compact + i] = u;
-        w[i] = items[i].w;
-    }
-    for (int c = 0, i = 0; c <= nc_dense; ++c) {
-        while (i < n && items[i].vid < c * kBwdChunk) ++i;
-        img[t.o_off_dense + c] = i;
-    }
-    for (int c = 0, i = 0; c <= nc_compact; ++c) {
-        while (i < n && cpos[i] < c * kBwdChunk) ++i;
-        img[t.o_off_compact + c] = i;
-    }
-    HIP_TRY(t.ints.upload(img.data(), img.size()));
-    HIP_TRY(t.w.upload(w.data(), w.size()));
-    t.U = U; t.n = n; t.L = m->lmk.L; t.built = true;
+    const tables::BackwardImage img = tables::lbs_backward_image(std::move(items), m->V, kBwdChunk);
+    HIP_TRY(t.ints.upload(img.ints.data(), img.ints.size()));
+    HIP_TRY(t.w.upload(img.w.data(), img.w.size()));
+    static_cast<tables::BackwardOffsets&>(t) = img;
+    t.L = m->lmk.L; t.built = true;
     return K2B_OK;
 }
 

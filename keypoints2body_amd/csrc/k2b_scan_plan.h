@@ -1,6 +1,6 @@
 // Scan plan of the fused fit kernel's tree pass: where every joint of the kinematic tree sits in the 32 tree lanes, and how its
 // subtree sum comes out of two fp32 inclusive prefix scans WITHOUT a difference of prefixes (k2b_lanes.h, chain_end_scans).
-// Host only, no device call: a pure function of the parent table (k2b_api_model.hip builds the lane tables from it).
+// Host only, no device call: a pure function of the parent table (k2b_model_tables.h builds the lane tables from it).
 //
 // With the lanes in REVERSED DFS pre-order a subtree is the lane range that ENDS at its joint, and every joint is one of two kinds:
 //   chain-type  all its descendants form a single-child path down to a leaf.  Its sum is a running sum along its own chain: a prefix
@@ -12,6 +12,8 @@
 // stays free in every plan: it is the identity source of the pointer-doubling rounds.
 #pragma once
 #include <vector>
+
+#include "k2b_tree.h"
 
 namespace k2b {
 
@@ -31,26 +33,15 @@ struct ScanPlan {
     int flags[kScanLanes];              // kScan* bits of lane l (0 for a hole)
 };
 
-// parents[0] < 0, parents[j] < j (checked by the caller).  Children are visited in ascending order, as everywhere in the library.
-inline ScanPlan fit_scan_plan(int J, const int* parents) {
+// Children are visited in ascending order, as everywhere in the library (k2b_tree.h).
+inline ScanPlan fit_scan_plan(const Tree& t) {
+    const int J = t.J;
+    const auto &parents = t.parents, &order = t.order, &pos = t.pos, &size = t.size;
+    const auto& children = t.children;
     ScanPlan p;
     for (int l = 0; l < kScanLanes; ++l) { p.joint_at[l] = -1; p.flags[l] = 0; }
-    p.lane_of.assign(J > 0 ? J : 0, -1);
-    if (J < 1 || J >= kScanLanes) { p.why = "more joints than tree lanes"; return p; }
-    std::vector<std::vector<int>> children(J);
-    for (int j = 1; j < J; ++j) children[parents[j]].push_back(j);
-    std::vector<int> order, pos(J, 0), size(J, 1);
-    {
-        std::vector<int> stack{0};
-        while (!stack.empty()) {
-            const int j = stack.back();
-            stack.pop_back();
-            pos[j] = (int)order.size();
-            order.push_back(j);
-            for (auto it = children[j].rbegin(); it != children[j].rend(); ++it) stack.push_back(*it);
-        }
-        for (int j = J - 1; j >= 1; --j) size[parents[j]] += size[j];
-    }
+    p.lane_of.assign(J, -1);
+    if (J >= kScanLanes) { p.why = "more joints than tree lanes"; return p; }
     // chain position: lanes between the joint and the leaf of its chain, -1 when its subtree is no single-child path
     std::vector<int> chain_pos(J, -1);
     for (int j = J - 1; j >= 0; --j) {
