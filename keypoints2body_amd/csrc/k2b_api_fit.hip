@@ -65,7 +65,7 @@ int check_surface_targets(const Targets& t, const FitCall& c, int J) {
     return K2B_OK;
 }
 int check_debug_shape(const k2b_fit_config* cfg) {
-    if (cfg->debug_launch_shape < 0 || cfg->debug_launch_shape > 4)
+    if (cfg->debug_launch_shape < k2b::ForceShape::automatic || cfg->debug_launch_shape > k2b::ForceShape::wide)
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: debug_launch_shape=%d must be 0..4", cfg->debug_launch_shape);
     return K2B_OK;
 }
@@ -230,13 +230,14 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     a.num_betas_prior = cfg->num_betas_prior > 0 ? (cfg->num_betas_prior < NB ? cfg->num_betas_prior : NB) : NB;
     a.opt_mask = cfg->optimize_mask & 15;
     if (const int rc = check_debug_shape(cfg); rc != K2B_OK) return rc;
-    a.debug_shape = cfg->debug_launch_shape <= 2 ? cfg->debug_launch_shape : 0;   // tree kernel: 1 = plain, 2 = component waves
+    a.debug_shape = cfg->debug_launch_shape <= k2b::TreeShape::comp_waves ? cfg->debug_launch_shape : k2b::TreeShape::automatic;
+    const int cus = device_cus();
     if (!t.vsel.empty()) {
         if (const int rc = check_surface_targets(t, c, J); rc != K2B_OK) return rc;
         return fit_world_vertex_joints(model, cfg, a, nullptr, cfg->freeze_betas ? a.num_betas_prior : 0, t, c.stream,
-                                       [&](const k2b::FitTreeArgs& e) { return k2b::launch_fit_tree(e, c.stream); });
+                                       [&](const k2b::FitTreeArgs& e) { return k2b::launch_fit_tree(e, cus, c.stream); });
     }
-    HIP_TRY(k2b::launch_fit_tree(a, c.stream));
+    HIP_TRY(k2b::launch_fit_tree(a, cus, c.stream));
     return K2B_OK;
 }
 
@@ -276,7 +277,7 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
     a.lb_mode = c.lbfgs.mode;
     if (const k2b::LbfgsArgs* lb = c.lbfgs.args) { a.lbv = *lb; a.lb_loss = lb->loss_in; a.lb_grad = lb->grad_in; a.lb_history = lb->H; }
     a.lb_chain_max_iter = c.lbfgs.chain_max_iter;
-    if (c.lbfgs.mode != 0 && (!t.vsel.empty() || (c.chain.len > 1 && c.lbfgs.mode != 3) || !c.lbfgs.args))
+    if (c.lbfgs.mode != k2b::LbMode::none && (!t.vsel.empty() || (c.chain.len > 1 && c.lbfgs.mode != k2b::LbMode::persistent) || !c.lbfgs.args))
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the fused L-BFGS step needs kinematic targets and independent frames");
     if (!t.vsel.empty())
         return fit_world_vertex_joints(model, cfg, a, a.tr_prior, 0, t, c.stream,

@@ -82,35 +82,34 @@ int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_conf
         ev.loss_out = loss; ev.grad_out = grad;
         return fit_world_impl(model, prior, &c, ev);
     };
-    auto closure = [&](float* loss, float* grad) { return launch(ec, 0, nullptr, loss, grad); };
+    auto closure = [&](float* loss, float* grad) { return launch(ec, k2b::LbMode::none, nullptr, loss, grad); };
     k2b::LbfgsArgs la = make_lbfgs_args(B, model, o, at.out, w);
     const int rounds = la.max_eval + 2;
     // One launch per round where the fused kernel takes the frames (24-joint model, the prior over the whole pose, kinematic
-    // targets only, at most four frames per CU): launch r = [step on the result of launch r - 1 | closure]; the last launch =
-    // [finalise | closure] with the caller's outputs.  Two result buffers alternate (a launch reads the one its predecessor
+    // targets only, at most four frames per CU - lbfgs_scheme_for, k2b_launch_plan.h): launch r = [step on the result of
+    // launch r - 1 | closure]; the last launch = [finalise | closure] with the caller's outputs.  Two result buffers alternate (a launch reads the one its predecessor
     // wrote while writing the other).  Otherwise two launches per round.
-    const int frames_per_cu = (B + device_cus() - 1) / device_cus();
     const int stage_cap = lbfgs_stage_cap();
-    const bool fused = stage_cap < 0 && lbfgs_scheme() != 1 && frames_per_cu <= 4 && fused_eligibility(model, prior, cfg).fused &&
-                       kinematic_only(model, at.K, at.model_joint_index);
-    if (fused) {
+    const bool fused_ok = fused_eligibility(model, prior, cfg).fused && kinematic_only(model, at.K, at.model_joint_index);
+    const k2b::LbfgsScheme scheme = k2b::lbfgs_scheme_for(B, device_cus(), fused_ok, stage_cap, lbfgs_scheme());
+    if (scheme != k2b::LbfgsScheme::two_launches) {
         // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
         k2b::LbfgsArgs both[2] = {la, la};
         both[1].loss_in = w.lbuf2; both[1].grad_in = w.gbuf2;
-        if (lbfgs_scheme() != 2 && frames_per_cu <= 2) {
+        if (scheme == k2b::LbfgsScheme::persistent) {
             // at most two frames per CU: the whole fit is ONE persistent launch - rounds closures, each followed by its step on an
-            // idle wave of the workgroup, the finalise pass and the closure at the result (k2b_fit.hip, lb_mode 3)
+            // idle wave of the workgroup, the finalise pass and the closure at the result (k2b_fit.hip, LbMode::persistent)
             k2b_fit_config pc = ec;
             pc.num_iters = rounds + 1;
-            return launch(pc, 3, &both[0], at.loss_out ? at.loss_out : w.lbuf2, at.grad_out);
+            return launch(pc, k2b::LbMode::persistent, &both[0], at.loss_out ? at.loss_out : w.lbuf2, at.grad_out);
         }
         // launch 0: closure only, writes A; launch r >= 1 reads (r - 1) & 1 and writes r & 1
         if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
         for (int r = 1; r <= rounds; ++r) {
             const int rd = (r - 1) & 1, wr = r & 1;
-            if (const int rc = launch(ec, 1, &both[rd], wr ? w.lbuf2 : w.lbuf, wr ? w.gbuf2 : w.gbuf); rc != K2B_OK) return rc;
+            if (const int rc = launch(ec, k2b::LbMode::step, &both[rd], wr ? w.lbuf2 : w.lbuf, wr ? w.gbuf2 : w.gbuf); rc != K2B_OK) return rc;
             // the last step has consumed result r - 1: the finalise launch parks every frame and evaluates the result
-            if (r == rounds) return launch(ec, 2, &both[wr], at.loss_out ? at.loss_out : (rd ? w.lbuf2 : w.lbuf), at.grad_out);
+            if (r == rounds) return launch(ec, k2b::LbMode::finalize, &both[wr], at.loss_out ? at.loss_out : (rd ? w.lbuf2 : w.lbuf), at.grad_out);
         }
     }
     for (int r = 0; r < rounds; ++r) {
@@ -136,7 +135,7 @@ int lbfgs_check(const k2b_model* model, const k2b_prior* prior, const k2b_fit_co
     return K2B_OK;
 }
 
-// The default sequence mode in ONE launch (k2b_fit.hip: chain + lb_mode 3): the frame loop runs inside the persistent launch -
+// The default sequence mode in ONE launch (k2b_fit.hip: chain + LbMode::persistent): the frame loop runs inside the persistent launch -
 // per frame a fresh optimiser on the workgroup's idle wave, the start and the preserve pose from the predecessor's result in
 // registers.  `c` = the chain's call (slots, targets, parameters, chain.len / chain.meta), `la` = the first frame's optimiser.
 int lbfgs_chain_launch(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, FitCall c, const k2b::LbfgsArgs& la,
@@ -145,7 +144,7 @@ int lbfgs_chain_launch(const k2b_model* model, const k2b_prior* prior, const k2b
     pc.num_iters = la.max_eval + 3;                                       // rounds + the closure at the result
     pc.step_size = 0.0;
     c.chain.iters = followup_iters * 5 / 4 + 3;
-    c.lbfgs.mode = 3; c.lbfgs.args = &la; c.lbfgs.chain_max_iter = followup_iters;
+    c.lbfgs.mode = k2b::LbMode::persistent; c.lbfgs.args = &la; c.lbfgs.chain_max_iter = followup_iters;
     return fit_world_impl(model, prior, &pc, c);
 }
 
@@ -221,7 +220,10 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
 #define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_sequence_lbfgs: HIP call failed")
     float* pres = lbfgs_ws_assign(&w, ws.get(), 1, P);
     // the whole sequence in ONE launch where the fused kernel takes it (24-joint model, the prior over the whole pose, kinematic targets)
-    if (lbfgs_scheme() == 0 && lbfgs_stage_cap() < 0 && T > 1 && fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)) {
+    // (one sequence = one chain slot; any K2B_LBFGS_SCHEME but 0 keeps it out of the chain)
+    const bool fused_ok = fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index);
+    if (lbfgs_scheme() == 0 && T > 1 &&
+        k2b::lbfgs_scheme_for(1, device_cus(), fused_ok, lbfgs_stage_cap(), 0) == k2b::LbfgsScheme::persistent) {
         FitCall c = fit_call(1, K, model_joint_index, j3d, conf, stream_v);
         c.in = {go_in, bp_in, be_in, tr_in};
         c.out = {go_out, bp_out, be_out, tr_out};                             // rows t of the outputs: frame t's point
@@ -285,7 +287,7 @@ int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, co
     if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) return rc;
     HIP_TRY_MSG(hipMemsetAsync(ws.get() + n_meta, 0, w.off_sv, stream), "%s: HIP call failed", who);
     (void)lbfgs_ws_assign(&w, ws.get() + n_meta, r.slots, P);
-    // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: lb_mode 3)
+    // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: LbMode::persistent)
     FitCall c = fit_call(r.slots, K, model_joint_index, j3d, conf, stream_v);
     c.in = {go_in, bp_in, be_in, tr_in};
     c.out = {go_out, bp_out, be_out, tr_out};                                 // frame rows of the outputs: each frame's point

@@ -71,11 +71,8 @@ namespace k2b {
 namespace {
 
 static_assert(kFitJoints == 24, "lane tables are built for the SMPL tree");
+using namespace fit_lds;                // MAXS, MG, NC, XS, SLOT, YX_STRIDE, DD_STRIDE_MAX, PLO / WX / RC / LDS_FLOATS (k2b_layout.h)
 constexpr int D = kPriorDim;            // 69
-constexpr int MAXW = kFitMaxWaves;      // waves per workgroup
-constexpr int MAXS = 16;                // frame slots per workgroup (= MFMA columns)
-constexpr int MG = kPriorMaxGauss;      // 8
-constexpr int NC = 64;                  // core rows / columns of a component handled by the matrix cores
 constexpr int NR = D - NC;              // 5 rim rows / columns
 // LDS (floats): rim rows of P as [m][5 rim rows][64 columns] (read transposed - lane = column - for the arg-min component's
 // rim columns), then mu | c = P mu of the core rows [m][2][64], then the per-frame-slot blocks:
@@ -84,16 +81,7 @@ constexpr int RIM_FLOATS = 2 * NR * 64 * 4;
 constexpr int CMU_FLOATS = MG * 2 * NC;
 constexpr int RF_FLOATS = MG * kPriorRimFragEntries * 4;   // rim rows 64..68 as a fifth MFMA row tile, compact (k2b_api_prior.hip)
 static_assert(RIM_FLOATS + CMU_FLOATS + RF_FLOATS == kPriorImageFloats, "host image size");
-constexpr int XS = 96;                  // strip: go@0, body@4, betas@76, transl@92, joint loss@95
-constexpr int XS_BODY = 4, XS_BETA = 76, XS_TRANSL = 92;
-constexpr int SLOT = 2 * XS + NC + 4;   // 260 floats: the +4 spreads the 16 frame columns of the MFMA-side reads over the banks
-constexpr int YX_STRIDE = MG * NC + 4;  // y exchange: [slot][m][64] (+4: b128 stores of the 16 frame columns hit distinct banks)
-constexpr int DD_STRIDE_MAX = 52;        // per-lane stride of the J_dirs table in LDS (see the kernel)
-constexpr int PLO_FLOATS = MG * 4 * 2 * 64 * 4;   // lo fragments of all components (paired shape): [m][tile][ks][64 lanes][8 halfs]
-constexpr int WX_FLOATS = MAXS * 64;                 // rim rows' products: [slot][lane 8 m + s] = (P_m[64 + s][0..63] theta)[s < 5], zeros for s >= 5
-constexpr int RC_FLOATS = 8 * 64;                    // per-lane rim constants (FitArgs::row_const) for the 16-wave shapes, which have no registers for them
-constexpr int LDS_FLOATS = RIM_FLOATS + CMU_FLOATS + RF_FLOATS + MAXS * SLOT + MAXS * MG + MAXS * YX_STRIDE + 64 * DD_STRIDE_MAX + PLO_FLOATS + WX_FLOATS + RC_FLOATS;
-static_assert(LDS_FLOATS * 4 <= 163840, "LDS budget");
+constexpr int XS_BODY = 4, XS_BETA = 76, XS_TRANSL = 92;   // offsets in a strip (XS floats: go@0, body@4, betas@76, transl@92, joint loss@95)
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -177,13 +165,12 @@ __device__ __forceinline__ float butterfly8(const float (&v)[8], int lane) {
 // (Measured and NOT kept in round 4: `split` with eight row waves of one component each (12 waves: the row waves' component
 //  chain is halved but runs in the tree wave's shadow either way - 0.2465 against 0.2428 ms at 1024 frames), and a 16-wave shape
 //  with one frame per wave (twice the tree instructions per frame: 0.399 against 0.294 ms at 2048 frames).)
-enum { MODE_SPLIT = 0, MODE_SPLIT_PAIRED = 1, MODE_PAIRED = 2, MODE_WIDE = 3, MODE_SPLIT_LBFGS = 4 };   // 4: split + the L-BFGS step as a prologue
-
+// (MODE_*: FitShape, k2b_launch_plan.h; waves and frames per wave from the shape's description there)
 template <int MODE> struct Shape {
     static constexpr bool SPLIT = MODE != MODE_PAIRED;
-    static constexpr bool PAIR = MODE != MODE_SPLIT && MODE != MODE_SPLIT_LBFGS;
-    static constexpr int NROW = MODE == MODE_WIDE ? 8 : 4;                                   // row waves (split shapes)
-    static constexpr int NWAVES = SPLIT ? 2 * NROW : MAXW;                                   // as many tree waves as row waves
+    static constexpr bool PAIR = fit_shape_desc(MODE).frames_per_wave == 2;
+    static constexpr int NWAVES = fit_shape_desc(MODE).waves;
+    static constexpr int NROW = MODE == MODE_WIDE ? 8 : 4;                                   // row waves (split shapes: as many tree waves)
     static constexpr int CPW = MG / NROW;                                                    // mixture components per row wave
 };
 
@@ -446,16 +433,12 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     // rim products: 116 KiB that nothing has written yet - a barrier separates the step from their first use), shared out over the
     // workgroup's frames (one frame: 116 KiB, four: 29 KiB = 28 pairs of a 128-float parameter vector).
     if constexpr (MODE == MODE_SPLIT_LBFGS) {
-        if (a.lb_mode == 1 || a.lb_mode == 2) {
+        if (a.lb_mode == LbMode::step || a.lb_mode == LbMode::finalize) {
             if (do_row && f_valid[0]) {
                 LbfgsArgs la = a.lbv;
-                la.finalize = a.lb_mode == 2 ? 1 : 0;
-                constexpr int kFree = (MAXS * YX_STRIDE + 64 * DD_STRIDE_MAX + PLO_FLOATS + WX_FLOATS) * 4;
-                const int per_wave = (kFree / F) & ~15;
-                const int PL = (la.P + 63) / 64 * 64;
-                const int head = 2 * la.H * (int)sizeof(double);
-                int pairs = (per_wave - head) / (2 * PL * (int)sizeof(float));
-                pairs = pairs < 0 ? 0 : pairs;
+                la.finalize = a.lb_mode == LbMode::finalize ? 1 : 0;
+                const int per_wave = lbfgs_prologue_lds_bytes(F);
+                const int pairs = lbfgs_staged_pairs(per_wave, la.P, la.H);
                 unsigned char* stage = reinterpret_cast<unsigned char*>(yx) + wave * per_wave;
                 lbfgs_dev::lbfgs_step_frame<lbfgs_dev::kEpl>(la, f[0], lane, stage, pairs);
             }
@@ -465,8 +448,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         }
     }
 
-    // persistent L-BFGS (lb_mode 3): see the tree waves' loop
-    const bool lb_loop = MODE == MODE_SPLIT_LBFGS && a.lb_mode == 3;
+    // persistent L-BFGS (LbMode::persistent): see the tree waves' loop
+    const bool lb_loop = MODE == MODE_SPLIT_LBFGS && a.lb_mode == LbMode::persistent;
     bool lb_step = false;
     int lb_frame = 0, lb_pairs = 0, lb_off = 0, lb_len = 1;
     unsigned char* lb_stage = nullptr;
@@ -482,11 +465,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 lb_len = __builtin_amdgcn_readfirstlane(lb_len);
             }
             // staging LDS: the half of the lo-fragment area the split shape never writes (components 0..3 keep theirs in registers)
-            constexpr int kFree = PLO_FLOATS * 4 / 2;
-            const int per = (kFree / F) & ~15;
-            const int P_ = 3 + D + NB + 3, PL = (P_ + 63) / 64 * 64, head = 2 * a.lb_history * (int)sizeof(double);
-            lb_pairs = (per - head) / (2 * PL * (int)sizeof(float));
-            lb_pairs = lb_pairs < 0 ? 0 : lb_pairs;
+            const int per = lbfgs_persistent_lds_bytes(F);
+            lb_pairs = lbfgs_staged_pairs(per, 3 + D + NB + 3, a.lb_history);
             lb_stage = reinterpret_cast<unsigned char*>(plo) + sl * per;
         }
     }
@@ -558,44 +538,6 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     //  next to two frames of optimiser state)
     auto comp_issue = [&](const half8 (&ph)[4][2], const half8 (&plr)[4][2], floatx4 (&yacc)[5], int lds_comp, int comp) __attribute__((always_inline)) {
         // lds_comp >= 0: the lo fragments of that component are read from LDS instead of registers
-        if constexpr (WIDE16) {
-            // 128 registers per lane: the lo fragments of a tile are requested one tile ahead (8 registers in flight instead of 32),
-            // the rim fragments behind the third tile; tile-major, every tile's own chain in the usual order (bit-identical)
-            const half8* plc = plo + (size_t)lds_comp * 4 * 2 * 64 + lane;
-            const half8 bh0 = *reinterpret_cast<const half8*>(cth_hi + 8 * cg);
-            const half8 bh1 = *reinterpret_cast<const half8*>(cth_hi + 32 + 8 * cg);
-            const half8 bl0 = *reinterpret_cast<const half8*>(cth_lo + 8 * cg);
-            const half8 bl1 = *reinterpret_cast<const half8*>(cth_lo + 32 + 8 * cg);
-            const half8* rf = rimfrag + comp * kPriorRimFragEntries + ridx;
-            half8 nl0 = plc[0], nl1 = plc[64];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const half8 l0 = nl0, l1 = nl1;
-                if (t < 3) { nl0 = plc[((t + 1) * 2) * 64]; nl1 = plc[((t + 1) * 2 + 1) * 64]; }
-                else { nl0 = rf[21]; nl1 = rf[63]; }                       // rl0, rl1
-                __builtin_amdgcn_sched_barrier(0);
-                floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(l0, bh0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(l1, bh1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph[t][0], bl0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph[t][1], bl1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph[t][0], bh0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph[t][1], bh1, acc, 0, 0, 0);
-                yacc[t] = acc;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const half8 rh0 = rf[0], rh1 = rf[42];
-            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(nl0, bh0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(nl1, bh1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rh0, bl0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rh1, bl1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rh0, bh0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(rh1, bh1, acc, 0, 0, 0);
-            yacc[4] = acc;
-            asm volatile("" ::"v"(bh0), "v"(bh1), "v"(bl0), "v"(bl1));
-            return;
-        }
         half8 pl[4][2];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -895,14 +837,9 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             const float t68 = xs[XS_BODY + NC + 4];
             float yBv, qrim;
             {
-                float pbb[NR], cB, kB, muB;
-#pragma unroll
-                for (int k = 0; k < NR; ++k) pbb[k] = RC_IN_LDS ? rcl[lane * 8 + k] : pbb_r[k];
-                cB = RC_IN_LDS ? rcl[lane * 8 + 5] : cB_r;
-                kB = RC_IN_LDS ? rcl[lane * 8 + 6] : kB_r;
-                muB = RC_IN_LDS ? rcl[lane * 8 + 7] : muB_r;
+                const float cB = cB_r, kB = kB_r, muB = muB_r;
                 const float wm = wx[slot * 64 + lane], tB = xs[tBoff];
-                const float vB = pbb[0] * t64.x + pbb[1] * t64.y + pbb[2] * t64.z + pbb[3] * t64.w + pbb[4] * t68;
+                const float vB = pbb_r[0] * t64.x + pbb_r[1] * t64.y + pbb_r[2] * t64.z + pbb_r[3] * t64.w + pbb_r[4] * t68;
                 const float y = wm + vB - cB;
                 const float term = tB * (wm - kB) + (tB - muB) * y;
                 yBv = gs < NR ? y : 0.f;
@@ -978,7 +915,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         //  the row waves issue few instructions and are starved either way, the tree waves are what the SIMD must keep fed)
         __builtin_amdgcn_s_setprio(3);
         const int steps = PAIR ? 1 : c_steps;
-        // persistent L-BFGS (lb_mode 3, at most two frames per workgroup): the IDLE tree wave 4 + s is slot s's optimiser, its state -
+        // persistent L-BFGS (LbMode::persistent, at most two frames per workgroup): the IDLE tree wave 4 + s is slot s's optimiser, its state -
         // 27 scalars, eight vectors, the history in LDS by ring slot - RESIDENT in registers and LDS for the whole fit (the state
         // arrays in global memory are only written at the end).  Between two more barriers per iteration it consumes the closure
         // result the row wave has just written (loss, gradient: global memory, same CU) and puts the next point into the parameter
@@ -1300,8 +1237,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 if (a.grad_out) a.grad_out[(size_t)fr * P + pq] = gqo;
             }
         }
-        return;
-    }
+    } else {   // ---- the 8-wave shapes (to the end of the kernel; the wide instantiation compiles none of it) ------------------------
     if (SPLIT) {
         // row waves: optimiser state of slot `wave`, mixture components `wave` and `wave + 4`
         // (the lo fragments of the second component are parked in LDS: 96 instead of 128 resident registers,
@@ -1462,6 +1398,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             if (actB) a.grad_out[(size_t)fr * P + pB] = g1[h];
         }
     }
+    }  // 8-wave shapes
 }
 
 // the same call restricted to frames [f0, f0 + n): every per-frame array advanced by f0 frames
@@ -1480,84 +1417,40 @@ static FitArgs frame_range(const FitArgs& a, int f0, int n) {
     return r;
 }
 
+// one launch of a plan: the instantiation (shape, NBT, scan64) it names (the scan form is the model's: FitArgs::scan64)
+template <int MODE>
+static void launch_shape(const FitLaunch& l, const FitArgs& a, hipStream_t stream) {
+    const dim3 grid(l.grid), block(l.block_threads);
+    if (l.NBT == 10) {
+        if (l.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE, false>), grid, block, 0, stream, a);
+    } else {
+        if (l.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<16, MODE, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k2b_fit_world_kernel<16, MODE, false>), grid, block, 0, stream, a);
+    }
+}
+
+// executes plan_fit_world (k2b_launch_plan.h: shapes, frames per workgroup, the split of a batch beyond one full-width launch)
 hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
-    if (a_in.num_frames <= 0) return hipSuccess;
-    if (a_in.chain_len > 1) {
-        // warm-start chains: num_frames sequences, one split-shape slot each (the chain is serial, so the shape that
-        // gives one frame the most hardware is the one to use), up to four sequences per workgroup
-        FitArgs a = a_in;
-        int fpw = (a.num_frames + a.num_cus - 1) / a.num_cus;
-        fpw = fpw < 1 ? 1 : (fpw > 4 ? 4 : fpw);
-        if (a.lb_mode == 3 && fpw > 2) fpw = 2;                  // (the optimisers sit on the idle tree waves: two sequences per workgroup)
-        a.frames_per_wg = fpw;
-        const dim3 grid((a.num_frames + fpw - 1) / fpw), block(MAXW * 64);
-        // (the scan form is the model's: FitArgs::scan64)
-#define K2B_LAUNCH_CHAIN(NBT_, MODE_)                                                                                   \
-    do {                                                                                                                \
-        if (a.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, true>), grid, block, 0, stream, a);         \
-        else hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, false>), grid, block, 0, stream, a);                 \
-    } while (0)
-        if (a.lb_mode == 3) {
-            if (a.num_betas <= 10) K2B_LAUNCH_CHAIN(10, MODE_SPLIT_LBFGS);
-            else K2B_LAUNCH_CHAIN(16, MODE_SPLIT_LBFGS);
-            return hipGetLastError();
+    const FitPlan plan = plan_fit_world(a_in.num_frames, a_in.num_cus, a_in.num_betas, a_in.scan64 != 0, a_in.force_shape, a_in.lb_mode,
+                                        a_in.chain_len);
+    if (!plan.ok) return hipErrorInvalidValue;       // lb_mode and the batch disagree: the caller asks lbfgs_scheme_for first
+    for (int i = 0; i < plan.num_launches; ++i) {
+        const FitLaunch& l = plan.launch[i];
+        FitArgs a = frame_range(a_in, l.first_frame, l.num_frames);
+        a.frames_per_wg = l.frames_per_wg;
+        if (a.chain_len < 1) a.chain_len = 1;
+        switch (l.shape) {
+            case MODE_SPLIT_LBFGS: launch_shape<MODE_SPLIT_LBFGS>(l, a, stream); break;
+            case MODE_SPLIT: launch_shape<MODE_SPLIT>(l, a, stream); break;
+            case MODE_SPLIT_PAIRED: launch_shape<MODE_SPLIT_PAIRED>(l, a, stream); break;
+            case MODE_PAIRED: launch_shape<MODE_PAIRED>(l, a, stream); break;
+            default: launch_shape<MODE_WIDE>(l, a, stream); break;
         }
-        if (a.lb_mode != 0) return hipErrorInvalidValue;
-        if (a.num_betas <= 10) K2B_LAUNCH_CHAIN(10, MODE_SPLIT);
-        else K2B_LAUNCH_CHAIN(16, MODE_SPLIT);
-#undef K2B_LAUNCH_CHAIN
-        return hipGetLastError();
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
-    // More frames than one full-width launch of the densest shape holds (16 per CU): such a launch runs in rounds of
-    // num_cus workgroups, each as long as a full one however few workgroups it has (10 000 frames: 625 workgroups =
-    // 2.4 rounds, paid as 3).  Launch the whole rounds first and the remainder on its own, in the shape that suits
-    // ITS size (1 808 frames: split-paired, 0.6 of a paired round).  Frames are independent: results do not change.
-    const int full = MAXS * a_in.num_cus;
-    if (a_in.num_frames > full && a_in.num_frames % full != 0 && !a_in.force_shape) {
-        const int head = (a_in.num_frames / full) * full;
-        const hipError_t e = launch_fit_world(frame_range(a_in, 0, head), stream);
-        if (e != hipSuccess) return e;
-        return launch_fit_world(frame_range(a_in, head, a_in.num_frames - head), stream);
-    }
-    FitArgs a = a_in;
-    a.chain_len = 1;
-    // frame slots per workgroup: enough to cover the batch with one workgroup per CU.  Up to 4: split
-    // (SIMDs would idle, so every frame gets two cooperating waves); up to 8: one wave per frame;
-    // beyond: two frames per wave.
-    int fpw = (a.num_frames + a.num_cus - 1) / a.num_cus;
-    int mode = fpw <= 4 ? MODE_SPLIT : (fpw <= MAXW ? MODE_SPLIT_PAIRED : MODE_WIDE);
-    // k2b_fit_config::debug_launch_shape forces a shape regardless of the batch size, so that the parity tests can
-    // drive every shape with the small golden cases (1..3: the 8-wave shapes of rounds 1-3; 4: the 16-wave one)
-    static const int forced[5] = {0, MODE_SPLIT, MODE_SPLIT_PAIRED, MODE_PAIRED, MODE_WIDE};
-    auto cap_of = [](int m) { return (m == MODE_SPLIT || m == MODE_SPLIT_LBFGS) ? 4 : ((m == MODE_PAIRED || m == MODE_WIDE) ? MAXS : MAXW); };
-    if (a.lb_mode != 0) {
-        if (fpw > (a.lb_mode == 3 ? 2 : 4)) return hipErrorInvalidValue;     // the caller checks (k2b_api_lbfgs.hip: lbfgs_run)
-        mode = MODE_SPLIT_LBFGS;
-    } else if (a.force_shape) {
-        mode = forced[a.force_shape];
-        // small (test) batches fill the shape's slots; batches of a CU count or more keep one workgroup per CU where the shape can
-        if (a.num_frames < a.num_cus) { fpw = cap_of(mode); if (fpw > a.num_frames) fpw = a.num_frames; }
-    }
-    const int cap = cap_of(mode);
-    fpw = fpw < 1 ? 1 : (fpw > cap ? cap : fpw);
-    a.frames_per_wg = fpw;
-    const dim3 grid((a.num_frames + fpw - 1) / fpw);
-#define K2B_LAUNCH(NBT_, MODE_)                                                                                                      \
-    do {                                                                                                                            \
-        if (a.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, true>), grid, dim3(Shape<MODE_>::NWAVES * 64), 0, stream, a); \
-        else hipLaunchKernelGGL((k2b_fit_world_kernel<NBT_, MODE_, false>), grid, dim3(Shape<MODE_>::NWAVES * 64), 0, stream, a);   \
-    } while (0)
-#define K2B_LAUNCH_NB(MODE_) do { if (a.num_betas <= 10) K2B_LAUNCH(10, MODE_); else K2B_LAUNCH(16, MODE_); } while (0)
-    switch (mode) {
-        case MODE_SPLIT: K2B_LAUNCH_NB(MODE_SPLIT); break;
-        case MODE_SPLIT_PAIRED: K2B_LAUNCH_NB(MODE_SPLIT_PAIRED); break;
-        case MODE_PAIRED: K2B_LAUNCH_NB(MODE_PAIRED); break;
-        case MODE_SPLIT_LBFGS: K2B_LAUNCH_NB(MODE_SPLIT_LBFGS); break;
-        default: K2B_LAUNCH_NB(MODE_WIDE); break;
-    }
-#undef K2B_LAUNCH_NB
-#undef K2B_LAUNCH
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 }  // namespace k2b
+

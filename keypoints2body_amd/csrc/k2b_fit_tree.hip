@@ -33,7 +33,7 @@ namespace k2b {
 
 namespace {
 
-constexpr int TW = 8;                    // frames (waves) per workgroup
+constexpr int TW = kTreeMaxFrames;       // frames (waves) per workgroup: 8
 constexpr int TMG = kPriorMaxGauss;      // 8 mixture components
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -491,38 +491,29 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     }
 }
 
+template <int NS, bool CHAIN>
+hipError_t launch_tree(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
+    static std::atomic<unsigned long long> lds_set{0};
+    if (const hipError_t e = ensure_dynamic_lds(k2b_fit_tree_kernel<NS, CHAIN>, lds_set, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k2b_fit_tree_kernel<NS, CHAIN>), dim3(p.grid), dim3(p.block_threads), lds, stream, a);
+    return hipGetLastError();
+}
+template <int NS>
+hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
+    return p.chain ? launch_tree<NS, true>(p, lds, a, stream) : launch_tree<NS, false>(p, lds, a, stream);
+}
+
 }  // namespace
 
-hipError_t launch_fit_tree(const FitTreeArgs& a_in, hipStream_t stream) {
+// executes plan_fit_tree (k2b_launch_plan.h: frames per workgroup, component waves, the shape-coefficient capacity)
+hipError_t launch_fit_tree(const FitTreeArgs& a_in, int num_cus, hipStream_t stream) {
     if (a_in.num_frames <= 0) return hipSuccess;
     if (a_in.num_joints > 64 || a_in.num_shape > 32 || a_in.prior_dims > 64 || a_in.num_gauss > TMG) return hipErrorInvalidValue;
     const size_t lds = (size_t)(TMG * 16 * 64 * 4 + 3 * TMG * 64 + 2 * TW * 64 + TW * TMG * 64 + TW * TMG + 2 * TMG) * sizeof(float);
-    // frames per workgroup: enough to cover the batch with one workgroup per CU (up to 8: two waves per SIMD); small
-    // batches get fewer waves per CU, so that every SIMD hosts at most one frame and all CUs work
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int tw = (a_in.num_frames + cus - 1) / cus;
-    tw = tw < 1 ? 1 : (tw > TW ? TW : tw);
+    const FitTreePlan p = plan_fit_tree(a_in.num_frames, num_cus, a_in.num_shape, a_in.chain_len > 1, a_in.debug_shape);
     FitTreeArgs a = a_in;
-    // at most one frame per SIMD: four component waves ride along (one per SIMD) and take the mixture off the frame waves
-    a.comp_waves = a.debug_shape == 1 ? 0 : ((tw <= 4 || a.debug_shape == 2) ? 4 : 0);
-    if (a.debug_shape == 2 && tw > 4) tw = 4;
-    const dim3 grid((a.num_frames + tw - 1) / tw), block(64 * (tw + a.comp_waves));
-    hipError_t e;
-#define K2B_TREE(NS_, CH_)                                                                                             \
-    do {                                                                                                               \
-        static std::atomic<unsigned long long> lds_set{0};                                                             \
-        e = ensure_dynamic_lds(k2b_fit_tree_kernel<NS_, CH_>, lds_set, lds);                                    \
-        if (e != hipSuccess) return e;                                                                                 \
-        hipLaunchKernelGGL((k2b_fit_tree_kernel<NS_, CH_>), grid, block, lds, stream, a);                              \
-    } while (0)
-    const bool chain = a.chain_len > 1;
-    // (capacity 20 = SMPL-X's betas | expression: twelve coefficients of padding cost 36 registers in the 32-wide instantiation)
-    if (a.num_shape <= 16) { if (chain) K2B_TREE(16, true); else K2B_TREE(16, false); }
-    else if (a.num_shape <= 20) { if (chain) K2B_TREE(20, true); else K2B_TREE(20, false); }
-    else { if (chain) K2B_TREE(32, true); else K2B_TREE(32, false); }
-#undef K2B_TREE
-    return hipGetLastError();
+    a.comp_waves = p.comp_waves;
+    return p.NS == 16 ? launch_tree_ns<16>(p, lds, a, stream) : (p.NS == 20 ? launch_tree_ns<20>(p, lds, a, stream) : launch_tree_ns<32>(p, lds, a, stream));
 }
 
 }  // namespace k2b

@@ -19,7 +19,7 @@ namespace host __attribute__((visibility("hidden"))) {
 
 // records the calling thread's message for k2b_last_error() and returns `code` (k2b_api_misc.hip)
 int fail(int code, const char* fmt, ...);
-int device_cus();
+int device_cus();                        // CUs of the calling thread's current device (cached per device ordinal)
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -225,7 +225,7 @@ struct FitCall {
     // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta)
     struct Chain { int len = 1, iters = 0; const int* meta = nullptr; } chain;
     // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
-    struct Lbfgs { int mode = 0; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
+    struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
 };
 // what every entry knows of its call; the parameter arrays and the outputs are set by name
 inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, void* stream) {

@@ -6,18 +6,11 @@
 #include <atomic>
 
 #include "k2b_device.h"
-#include "k2b_layout.h"
+#include "k2b_launch_plan.h"   // (and k2b_layout.h: kFitJoints, kPrior*, the fit kernel's LDS layout)
 
 namespace k2b {
 
-constexpr int kFitJoints = 24;      // joints of the tree the fused fit kernel is built for (SMPL)
-constexpr int kPriorDim = 69;       // 3 * (kFitJoints - 1)
-constexpr int kPriorMaxGauss = 8;   // mixture components resident in LDS
-constexpr int kFitMaxWaves = 8;     // frames (waves) per workgroup
 constexpr int kMaxJoints = 64;
-// LDS image of the prior: rim rows 64..68 over columns 0..63 as [m][5][64], then mu | c = P mu of rows 0..63 as [m][2][64]
-constexpr int kPriorRimFragEntries = 4 * 21;   // per component: 4 fragments [k-step 2][hi | lo] of 20 live lanes + one zero entry, 16 B each
-constexpr int kPriorImageFloats = 2 * 5 * 64 * 4 + kPriorMaxGauss * 2 * 64 + kPriorMaxGauss * kPriorRimFragEntries * 4;
 // the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api_prior.hip):
 //   [m][tile 4][ks0 hi, ks1 hi, ks0 lo, ks1 lo][64 lanes][8 halfs]
 constexpr int kPriorFrag32Halfs = kPriorMaxGauss * 4 * 4 * 64 * 8;
@@ -73,17 +66,17 @@ struct FitArgs {
     float angle_sign[4];
     int num_cus;
     int chain_len, chain_iters; // warm-start chain: num_frames SEQUENCES of chain_len frames each (1: independent frames)
-    int force_shape;            // 0 = chosen by the batch size; 1..4 = split / split-paired / paired / wide (k2b_fit_config::debug_launch_shape)
-    // L-BFGS step as a prologue of the closure's own launch (k2b_lbfgs.hip): 0 = none; 1 = every frame's row wave first consumes the
-    // PREVIOUS launch's loss / gradient (lb->loss_in / grad_in) and writes the next point into the parameter arrays, then the launch
-    // evaluates it; 2 = the finalise step (accepted points into the parameter arrays), then the evaluation.  Split shape only.
+    int force_shape;            // ForceShape (k2b_launch_plan.h): automatic = chosen by the batch size, or k2b_fit_config::debug_launch_shape
+    // L-BFGS step as a prologue of the closure's own launch (k2b_lbfgs.hip), an LbMode: none; step = every frame's row wave first
+    // consumes the PREVIOUS launch's loss / gradient (lb->loss_in / grad_in) and writes the next point into the parameter arrays, then
+    // the launch evaluates it; finalize = the finalise step (accepted points into the parameter arrays), then the evaluation.  Split shape only.
     int lb_mode;
     LbfgsArgs lbv;              // the optimiser's arguments (by value: no device copy to keep in step)
-    // 3 = persistent: the whole fit in ONE launch (num_iters = rounds + 1 closures; at most two frames per workgroup); the row wave
+    // LbMode::persistent: the whole fit in ONE launch (num_iters = rounds + 1 closures; at most two frames per workgroup); the row wave
     // writes each closure's result to lb_loss / lb_grad (= lb->loss_in / grad_in), lb_history = lb->H (host copies: no device read)
     const float *lb_loss, *lb_grad;
     int lb_history;
-    int lb_chain_max_iter;      // lb_mode 3 with chain_len > 1 (the default sequence mode in ONE launch): max_iter of the follow-up frames (lbv: the first's)
+    int lb_chain_max_iter;      // LbMode::persistent with chain_len > 1 (the default sequence mode in ONE launch): max_iter of the follow-up frames (lbv: the first's)
     // ragged chains (chain_len > 1): NULL = every slot s is sequence s with chain_len frames at rows s * chain_len; else [slot][4] =
     // {row of the start parameters, first frame row, frame count >= 1, 0} (device).  A workgroup runs as many steps as its
     // longest slot; a slot whose sequence has ended takes the barriers and writes nothing.
@@ -127,9 +120,9 @@ struct FitTreeArgs {
     int chain_len, chain_iters;  // warm-start chain: num_frames SEQUENCES of chain_len frames each (<= 1: independent frames)
     const int* chain_meta;       // ragged chains: as FitArgs::chain_meta
     int comp_waves;             // set by launch_fit_tree: 4 = the mixture runs on four dedicated component waves (<= 4 frames per CU)
-    int debug_shape;             // 0 = chosen by the batch size; 1 = force the plain shape, 2 = force the component-wave shape (tests)
+    int debug_shape;             // TreeShape (k2b_launch_plan.h): automatic = chosen by the batch size; plain / comp_waves force one (tests)
 };
-hipError_t launch_fit_tree(const FitTreeArgs& a, hipStream_t stream);
+hipError_t launch_fit_tree(const FitTreeArgs& a, int num_cus, hipStream_t stream);
 
 // Batched shape pre-pass (k2b_shape.hip, k2b_shape_pass_lbfgs): S sequences, sequence s owns frames seq_off[s] .. seq_off[s + 1].
 struct ShapePassArgs {
@@ -192,11 +185,6 @@ struct TileArgs {
     int num_wgs;                 // grid size (a multiple of 8), set by the launcher
 };
 hipError_t launch_skin_tiles(const TileArgs& a, int num_cus, hipStream_t stream);
-// grid of the persistent vertex kernels: one workgroup per CU, a multiple of the 8 XCD labels, no more than the tiles need
-inline int persistent_grid(int num_cus, long long tiles) {
-    const int wgs = num_cus < 8 ? 8 : num_cus / 8 * 8;
-    return tiles < wgs ? (int)((tiles + 7) / 8 * 8) : wgs;
-}
 
 // ---- stream kernels (k2b_lbs_stream.hip): the same tile, Pd global -> registers -------------------------------------------------
 // One kernel body (stream_body<S>) behind three entry points, one description S each; the descriptions hold what differs (pose

@@ -18,10 +18,10 @@
 //   * the host only ENQUEUES a fixed number of [closure, step] rounds - max_eval + 2, the most any frame can need - without
 //     reading anything back: frames that finish early idle at their final point.  No host synchronisation, no PCIe traffic.
 //     THREE ways the rounds reach the device, by the batch size, bit-identical (tests/test_gpu_lbfgs.py):
-//       - at most two frames per CU: ONE persistent launch of the fused fit kernel (k2b_fit.hip, lb_mode 3) - the closures are
+//       - at most two frames per CU: ONE persistent launch of the fused fit kernel (LbMode::persistent) - the closures are
 //         iterations of its loop, the optimiser lives on an idle wave of the workgroup with its state resident; with chain_len
 //         frames the same launch runs the whole warm-start sequence (k2b_fit_sequence_lbfgs);
-//       - at most four: one launch per round, the step as a prologue of the closure's launch (lb_mode 1 / 2);
+//       - at most four: one launch per round, the step as a prologue of the closure's launch (LbMode::step / finalize);
 //       - beyond, and for the larger models: two launches per round - the closure's, and k2b_lbfgs_step_kernel below.
 //
 // CPU twin: keypoints2body_amd/core/lbfgs_batched.py (itself pinned to torch.optim.LBFGS iterate by iterate in float64,
@@ -81,13 +81,11 @@ hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_sta
     // several frames share a CU; pairs beyond that are read from global memory.  (P > 192: a pair is 2 KiB and H = 30 leaves room
     // for 23 of the 30, so the reference's default max_iter = 30 reads pairs 23.. from global memory - tests/test_gpu_lbfgs_wide.py.)
     // max_staged_pairs >= 0 caps the number further (development switch: the results do not depend on it).
-    const int PL = (a.P + 63) / 64 * 64;
+    const int PL = (a.P + 63) / 64 * 64, room = lbfgs_staged_pairs(lbfgs_step_lds_bytes(), a.P, a.H);
     int pairs = a.H < a.max_iter ? a.H : a.max_iter;
-    const size_t per_pair = (size_t)2 * PL * sizeof(float), head = (size_t)2 * a.H * sizeof(double);
-    const size_t room = 48 * 1024 - head;
-    if ((size_t)pairs * per_pair > room) pairs = (int)(room / per_pair);
+    if (pairs > room) pairs = room;
     if (max_staged_pairs >= 0 && pairs > max_staged_pairs) pairs = max_staged_pairs;
-    const size_t lds = head + (size_t)pairs * per_pair;
+    const size_t lds = (size_t)2 * a.H * sizeof(double) + (size_t)pairs * 2 * PL * sizeof(float);
     if (a.P <= 64 * kEpl) hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEpl>, dim3(a.B), dim3(64), lds, stream, a, pairs);
     else hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEplWide>, dim3(a.B), dim3(64), lds, stream, a, pairs);
     return hipGetLastError();

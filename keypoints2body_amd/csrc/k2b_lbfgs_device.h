@@ -523,11 +523,6 @@ __device__ __forceinline__ void lbfgs_step_frame(const LbfgsArgs& a, int f, int 
     fr.save();
 }
 
-// bytes of LDS a frame's step wants for `pairs` staged history pairs
-__host__ __device__ inline size_t lbfgs_lds_bytes(int H, int P, int pairs) {
-    return (size_t)2 * H * sizeof(double) + (size_t)pairs * 2 * ((P + 63) / 64 * 64) * sizeof(float);
-}
-
 }  // namespace lbfgs_dev
 }  // namespace k2b
 

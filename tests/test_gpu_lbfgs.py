@@ -102,8 +102,9 @@ def test_device_lbfgs_launch_schemes_agree_bitwise():
         assert torch.equal(small[k], mid[k][:2 * cus]), k
         assert torch.equal(small[k], big[k][:2 * cus]), k
         assert torch.equal(mid[k], big[k][:3 * cus]), k
-    # more history pairs than the staging LDS of any scheme holds (60 iterations; 30 / 28 / 47 pairs fit): the pairs beyond it are
-    # read from global memory, in the resident optimiser too
+    # more history pairs than the staging LDS of any scheme holds (60 iterations, 85 parameters; lbfgs_staged_pairs of
+    # csrc/k2b_launch_plan.h: 15 / 36 / 47 pairs fit at two frames per workgroup of the persistent launch, three of the fused
+    # rounds and in the step kernel): the pairs beyond it are read from global memory, in the resident optimiser too
     long = lambda n: native.fit_world_lbfgs(H.native_model(), H.native_prior(), cfg, list(range(22)), j3d[:n].contiguous(), None,
                                             *[t[:n].contiguous() for t in init], max_iter=60, lr=1e-2, tolerance_grad=0.0,
                                             tolerance_change=0.0)

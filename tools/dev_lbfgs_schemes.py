@@ -1,5 +1,6 @@
 """Development: the three launch schemes of the device L-BFGS on the same frames (persistent / fused rounds / two launches per
-round): which frames differ, by how much, and whether each scheme repeats itself."""
+round): which frames differ, by how much, and whether each scheme repeats itself.  ``dev_lbfgs_schemes.py MAX_ITER time`` prints
+the wall time of a fit in each scheme instead (one JSON line)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
@@ -14,6 +15,18 @@ run = lambda n: native.fit_world_lbfgs(H.native_model(), H.native_prior(), cfg, 
                                        *[t[:n].contiguous() for t in init], max_iter=MI, lr=1e-2)
 sizes = {"persistent": 2 * cus, "fused": 3 * cus, "two-launch": 5 * cus}
 names = list(sizes)
+if len(sys.argv) > 2 and sys.argv[2] == "time":
+    # wall time of one fit per scheme's own batch size (host clock between device synchronisations; two untimed fits first)
+    import json, statistics, time
+    out = {"max_iter": MI, "cus": cus}
+    for k, n in sizes.items():
+        ms = []
+        for rep in range(12):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            run(n)
+            torch.cuda.synchronize(); ms.append((time.perf_counter() - t0) * 1e3)
+        out[k] = {"frames": n, "median_ms": round(statistics.median(ms[2:]), 4), "min_ms": round(min(ms[2:]), 4)}
+    print(json.dumps(out)); sys.exit(0)
 if len(sys.argv) > 2:
     torch.save(run(2 * cus)["body_pose"].cpu(), sys.argv[2]); sys.exit(0)
 res = {k: run(n) for k, n in sizes.items()}
