@@ -382,7 +382,7 @@ int k2b_debug_read_dump(const k2b_model *model, void *host, int64_t nbytes);
  * k2b_debug_lbfgs_state_layout: for num_frames optimisers of num_params = 3 + pose_dim + num_betas + 3 parameters and `history`
  *   pairs, the bytes of the state buffer, the byte offsets of its integer and vector blocks, and the row lengths of the two scalar
  *   blocks: doubles [num_frames][doubles_per_frame] at offset 0, int32 [num_frames][ints_per_frame] at offset_ints (column order:
- *   csrc/k2b_lbfgs_device.h).  Host only.
+ *   csrc/k2b_lbfgs_plan.h).  Host only.
  * k2b_debug_lbfgs_step: advances the num_frames optimisers by ONE closure result.
  *   global_orient [B][3], body_pose [B][pose_dim], betas [B][num_betas], transl [B][3] (dev, in / out): the parameter arrays the
  *     closure would read.  Before the first call they hold the start; after a call, the point whose loss and gradient the next

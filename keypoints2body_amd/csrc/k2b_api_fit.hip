@@ -131,19 +131,15 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
     }
     // stream-ordered scratch: gradient and loss of the evaluate launch, Adam state, copies of the preserve pose and the
     // translation prior's centre (their defaults are the INITIAL parameters, which the in-place steps overwrite)
-    const size_t n_g = (size_t)B * P, n_all = 3 * n_g + B + (size_t)B * D + (size_t)B * 3;
+    const k2b::VertexJointsMap m = k2b::vertex_joints_map(B, P, D);
     StreamWorkspace scratch(stream);
-    HIP_TRY(scratch.alloc(n_all * sizeof(float)));
-    float* ws = reinterpret_cast<float*>(scratch.get());
-    float *gbuf = ws, *mbuf = ws + n_g, *vbuf = ws + 2 * n_g, *lbuf = ws + 3 * n_g, *pres = lbuf + B, *trp = pres + (size_t)B * D;
+    HIP_TRY(scratch.alloc(m.total));
+    auto f = [&](size_t off) { return reinterpret_cast<float*>(scratch.get() + off); };
+    float *gbuf = f(m.grad), *mbuf = f(m.adam_m), *vbuf = f(m.adam_v), *lbuf = f(m.loss), *pres = f(m.preserve), *trp = f(m.tr_prior);
 #define TRY_VJ(expr) HIP_TRY_MSG(expr, "k2b_fit_world: HIP call failed in the vertex-joint path")
-    TRY_VJ(hipMemsetAsync(mbuf, 0, 2 * n_g * sizeof(float), stream));
-    TRY_VJ(hipMemcpyAsync(pres, a.preserve ? a.preserve : a.bp_in, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    TRY_VJ(hipMemcpyAsync(trp, tr_prior_src ? tr_prior_src : a.tr_in, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    const struct { const float* src; float* dst; size_t n; } cp[] = {
-        {a.go_in, a.go_out, (size_t)B * 3}, {a.bp_in, a.bp_out, (size_t)B * D}, {a.be_in, a.be_out, (size_t)B * NB}, {a.tr_in, a.tr_out, (size_t)B * 3}};
-    for (const auto& c : cp)
-        if (c.src != c.dst) TRY_VJ(hipMemcpyAsync(c.dst, c.src, c.n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    TRY_VJ(hipMemsetAsync(mbuf, 0, m.moments_bytes, stream));
+    TRY_VJ(start_in_place(B, D, NB, {a.go_in, a.bp_in, a.be_in, a.tr_in}, {a.go_out, a.bp_out, a.be_out, a.tr_out}, a.preserve, tr_prior_src,
+                          pres, trp, stream));
     float* user_grad = a.grad_out;
     float* user_loss = a.loss_out;
     a.go_in = a.go_out; a.bp_in = a.bp_out; a.be_in = a.be_out; a.tr_in = a.tr_out;
@@ -297,6 +293,17 @@ FusedEligibility fused_eligibility(const k2b_model* model, const k2b_prior* prio
     const bool fused = model->fit_ok && prior->D == pose_dims_all && prior_dims == pose_dims_all &&
                        (cfg->num_betas_prior == 0 || cfg->num_betas_prior == model->NB);
     return {prior_dims, fused};
+}
+
+hipError_t start_in_place(int B, int D, int NB, const ConstParams& in, const Params& out, const float* preserve, const float* tr_prior,
+                          float* pres, float* trp, hipStream_t stream) {
+    const struct { const float* src; float* dst; size_t n; } cp[] = {
+        {preserve ? preserve : in.bp, pres, (size_t)B * D}, {tr_prior ? tr_prior : in.tr, trp, (size_t)B * 3},
+        {in.go, out.go, (size_t)B * 3}, {in.bp, out.bp, (size_t)B * D}, {in.be, out.be, (size_t)B * NB}, {in.tr, out.tr, (size_t)B * 3}};
+    for (const auto& c : cp)
+        if (c.src != c.dst)
+            if (const hipError_t e = hipMemcpyAsync(c.dst, c.src, c.n * sizeof(float), hipMemcpyDeviceToDevice, stream); e != hipSuccess) return e;
+    return hipSuccess;
 }
 
 int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& c) {

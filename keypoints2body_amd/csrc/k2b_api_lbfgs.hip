@@ -1,6 +1,7 @@
-// k2b_api_lbfgs.hip — the L-BFGS entries of the C ABI (include/k2b.h): the optimiser's workspace, one device-driven fit
-// (lbfgs_run), the entries for frames, a warm-start sequence and ragged sequences, and the shape pre-pass.  The closure is
-// the evaluate-only fit launch of k2b_api_fit.hip, the optimiser k2b_lbfgs.hip's state machine; only launches are queued.
+// k2b_api_lbfgs.hip — the L-BFGS entries of the C ABI (include/k2b.h): one device-driven fit (lbfgs_run), the entries for frames, a
+// warm-start sequence and ragged sequences, and the shape pre-pass.  The closure is the evaluate-only fit launch of k2b_api_fit.hip,
+// the optimiser k2b_lbfgs.hip's state machine; only launches are queued.  Which launches, in which order, on which result buffer,
+// and where every array of a workspace lies is k2b_lbfgs_plan.h: this unit executes those plans.
 #include <cstdlib>
 
 #include "k2b_host.h"
@@ -27,22 +28,19 @@ int lbfgs_stage_cap() {
     return v < 0 ? -1 : v;
 }
 
-// Workspace of the optimiser: its state, then two closure-result buffers (the fused rounds alternate).
-struct LbfgsWs { unsigned char* base; size_t off_si, off_sv, n_state, n_res; float *gbuf, *lbuf, *gbuf2, *lbuf2; bool state_cleared; };   // (state_cleared: the caller did)
-size_t lbfgs_ws_layout(int B, int P, int H, LbfgsWs* w) {
-    w->n_state = (k2b::lbfgs_state_bytes(B, P, H, &w->off_si, &w->off_sv) + 15) / 16 * 16;
-    w->n_res = (2 * ((size_t)B * P + B) * sizeof(float) + 15) / 16 * 16;
-    return w->n_state + w->n_res;
-}
-// pointers into the workspace laid out above; returns the first byte behind it (the caller's own scratch)
-float* lbfgs_ws_assign(LbfgsWs* w, unsigned char* ws, int B, int P) {
-    w->base = ws;
-    w->gbuf = reinterpret_cast<float*>(ws + w->n_state);
-    w->lbuf = w->gbuf + (size_t)B * P;
-    w->gbuf2 = w->lbuf + B;
-    w->lbuf2 = w->gbuf2 + (size_t)B * P;
-    return reinterpret_cast<float*>(ws + w->n_state + w->n_res);
-}
+template <class T>
+T* ws_at(unsigned char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
+
+// The optimiser's part of a workspace (k2b_lbfgs_plan.h, LbfgsOptMap) as pointers: its state, closure-result buffers A and B.
+struct LbfgsWs {
+    unsigned char* ws;
+    k2b::LbfgsOptMap m;
+    bool state_cleared;                      // (the caller did)
+    float* grad(k2b::LbfgsBuf b) const { return b == k2b::LbfgsBuf::A ? ws_at<float>(ws, m.grad_a) : b == k2b::LbfgsBuf::B ? ws_at<float>(ws, m.grad_b) : nullptr; }
+    float* loss(k2b::LbfgsBuf b) const { return b == k2b::LbfgsBuf::A ? ws_at<float>(ws, m.loss_a) : b == k2b::LbfgsBuf::B ? ws_at<float>(ws, m.loss_b) : nullptr; }
+    // scalars and integers: phase INIT (vectors are written before they are read)
+    hipError_t clear(hipStream_t stream) const { return hipMemsetAsync(ws + m.state, 0, k2b::lbfgs_clear_bytes(m), stream); }
+};
 
 struct LbfgsOpts {
     int max_iter, history;                   // (history: already cut to what a fit of max_iter iterations can fill)
@@ -52,87 +50,95 @@ struct LbfgsOpts {
 k2b::LbfgsArgs make_lbfgs_args(int B, int D, int NB, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
     k2b::LbfgsArgs la{};
     la.B = B; la.P = 3 + D + NB + 3; la.D = D; la.NB = NB; la.H = o.history;
-    la.max_iter = o.max_iter; la.max_eval = o.max_iter * 5 / 4;          // torch's default
+    la.max_iter = o.max_iter; la.max_eval = k2b::lbfgs_max_eval(o.max_iter);
     la.lr = o.lr; la.tol_g = o.tol_g; la.tol_c = o.tol_c;
     la.go = p.go; la.bp = p.bp; la.be = p.be; la.tr = p.tr;
-    la.loss_in = w.lbuf; la.grad_in = w.gbuf;
-    la.sd = reinterpret_cast<double*>(w.base); la.si = reinterpret_cast<int*>(w.base + w.off_si); la.sv = reinterpret_cast<float*>(w.base + w.off_sv);
+    la.loss_in = w.loss(k2b::LbfgsBuf::A); la.grad_in = w.grad(k2b::LbfgsBuf::A);
+    la.sd = ws_at<double>(w.ws, w.m.state); la.si = ws_at<int>(w.ws, w.m.ints); la.sv = ws_at<float>(w.ws, w.m.vectors);
     return la;
 }
 k2b::LbfgsArgs make_lbfgs_args(int B, const k2b_model* model, const LbfgsOpts& o, const Params& p, const LbfgsWs& w) {
     return make_lbfgs_args(B, 3 * (model->J - 1), model->NB, o, p, w);
 }
+k2b::LbfgsArgs step_args(const k2b::LbfgsArgs& la, const k2b::LbfgsLaunch& l) {
+    k2b::LbfgsArgs s = la;
+    s.finalize = l.finalize ? 1 : 0;
+    return s;
+}
+
+// launches [0, launches) of a fit's schedule (k2b_lbfgs_plan.h), each handed to `launch`
+template <class Launch>
+int lbfgs_drive(k2b::LbfgsScheme scheme, int rounds, int launches, Launch&& launch) {
+    for (int i = 0; i < launches; ++i)
+        if (const int rc = launch(k2b::lbfgs_launch_at(scheme, rounds, i)); rc != K2B_OK) return rc;
+    return K2B_OK;
+}
 
 // One device-driven L-BFGS fit of the frames of `at`, whose start is ALREADY in the parameter arrays at.out (in place): state
-// cleared, max_eval + 2 rounds of [closure, step], finalise, loss (+ gradient) at the result.  `w` = lbfgs_ws_layout() of
-// stream-ordered scratch, at.preserve / at.tr_prior = preserve pose / translation prior centre (device, outside the arrays).
+// cleared, then the schedule of its scheme.  `w` = the optimiser's part of stream-ordered scratch, at.preserve / at.tr_prior =
+// preserve pose / translation prior centre (device, outside the arrays).
 int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& at, const LbfgsOpts& o,
               LbfgsWs& w) {
+    using Kind = k2b::LbfgsLaunchKind;
     hipStream_t stream = at.stream;
     const int B = at.B;
-    if (!w.state_cleared) HIP_TRY(hipMemsetAsync(w.base, 0, w.off_sv, stream));   // scalars and integers: phase INIT (vectors are written before they are read)
+    if (!w.state_cleared) HIP_TRY(w.clear(stream));
     w.state_cleared = false;
     k2b_fit_config ec = *cfg;
     ec.num_iters = 1;
     ec.step_size = 0.0;                                                  // evaluate-only: the closure
+    k2b_fit_config pc = ec;
+    pc.num_iters = k2b::lbfgs_persistent_closures(o.max_iter);           // at most two frames per CU: the whole fit is ONE launch (k2b_fit.hip, LbMode::persistent)
     FitCall ev = at;
     ev.in = at.out.as_const();
-    auto launch = [&](const k2b_fit_config& c, int mode, const k2b::LbfgsArgs* args, float* loss, float* grad) {
-        ev.lbfgs.mode = mode; ev.lbfgs.args = args;
-        ev.loss_out = loss; ev.grad_out = grad;
-        return fit_world_impl(model, prior, &c, ev);
-    };
-    auto closure = [&](float* loss, float* grad) { return launch(ec, k2b::LbMode::none, nullptr, loss, grad); };
-    k2b::LbfgsArgs la = make_lbfgs_args(B, model, o, at.out, w);
-    const int rounds = la.max_eval + 2;
     // One launch per round where the fused kernel takes the frames (24-joint model, the prior over the whole pose, kinematic
-    // targets only, at most four frames per CU - lbfgs_scheme_for, k2b_launch_plan.h): launch r = [step on the result of
-    // launch r - 1 | closure]; the last launch = [finalise | closure] with the caller's outputs.  Two result buffers alternate (a launch reads the one its predecessor
-    // wrote while writing the other).  Otherwise two launches per round.
+    // targets only, at most four frames per CU - lbfgs_scheme_for, k2b_launch_plan.h), otherwise two launches per round.
     const int stage_cap = lbfgs_stage_cap();
     const bool fused_ok = fused_eligibility(model, prior, cfg).fused && kinematic_only(model, at.K, at.model_joint_index);
     const k2b::LbfgsScheme scheme = k2b::lbfgs_scheme_for(B, device_cus(), fused_ok, stage_cap, lbfgs_scheme());
-    if (scheme != k2b::LbfgsScheme::two_launches) {
-        // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
-        k2b::LbfgsArgs both[2] = {la, la};
-        both[1].loss_in = w.lbuf2; both[1].grad_in = w.gbuf2;
-        if (scheme == k2b::LbfgsScheme::persistent) {
-            // at most two frames per CU: the whole fit is ONE persistent launch - rounds closures, each followed by its step on an
-            // idle wave of the workgroup, the finalise pass and the closure at the result (k2b_fit.hip, LbMode::persistent)
-            k2b_fit_config pc = ec;
-            pc.num_iters = rounds + 1;
-            return launch(pc, k2b::LbMode::persistent, &both[0], at.loss_out ? at.loss_out : w.lbuf2, at.grad_out);
+    // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
+    const k2b::LbfgsArgs la = make_lbfgs_args(B, model, o, at.out, w);
+    k2b::LbfgsArgs both[2] = {la, la};
+    both[1].loss_in = w.loss(k2b::LbfgsBuf::B); both[1].grad_in = w.grad(k2b::LbfgsBuf::B);
+    const int rounds = k2b::lbfgs_rounds(o.max_iter);
+    return lbfgs_drive(scheme, rounds, k2b::lbfgs_launch_count(scheme, rounds), [&](const k2b::LbfgsLaunch& l) -> int {
+        const k2b::LbfgsArgs& args = both[l.reads == k2b::LbfgsBuf::B];
+        if (l.kind == Kind::step) {
+            HIP_TRY(k2b::launch_lbfgs_step(step_args(args, l), stream, stage_cap));
+            return K2B_OK;
         }
-        // launch 0: closure only, writes A; launch r >= 1 reads (r - 1) & 1 and writes r & 1
-        if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
-        for (int r = 1; r <= rounds; ++r) {
-            const int rd = (r - 1) & 1, wr = r & 1;
-            if (const int rc = launch(ec, k2b::LbMode::step, &both[rd], wr ? w.lbuf2 : w.lbuf, wr ? w.gbuf2 : w.gbuf); rc != K2B_OK) return rc;
-            // the last step has consumed result r - 1: the finalise launch parks every frame and evaluates the result
-            if (r == rounds) return launch(ec, k2b::LbMode::finalize, &both[wr], at.loss_out ? at.loss_out : (rd ? w.lbuf2 : w.lbuf), at.grad_out);
-        }
-    }
-    for (int r = 0; r < rounds; ++r) {
-        if (const int rc = closure(w.lbuf, w.gbuf); rc != K2B_OK) return rc;
-        HIP_TRY(k2b::launch_lbfgs_step(la, stream, stage_cap));
-    }
-    la.finalize = 1;
-    HIP_TRY(k2b::launch_lbfgs_step(la, stream, stage_cap));
-    // loss (and gradient) at the result (world_space.py:245-246 evaluates the loss once more behind the optimiser)
-    return closure(at.loss_out ? at.loss_out : w.lbuf, at.grad_out);
+        ev.lbfgs.mode = l.kind == Kind::closure ? k2b::LbMode::none : l.kind == Kind::step_closure ? k2b::LbMode::step
+                      : l.kind == Kind::finalize_closure ? k2b::LbMode::finalize : k2b::LbMode::persistent;
+        ev.lbfgs.args = l.kind == Kind::closure ? nullptr : &args;
+        // the closure at the result leaves the loss (+ gradient) with the caller (world_space.py:245-246 evaluates the loss once
+        // more behind the optimiser)
+        const bool last = l.writes == k2b::LbfgsBuf::out;
+        ev.loss_out = last ? (at.loss_out ? at.loss_out : w.loss(l.loss_spare)) : w.loss(l.writes);
+        ev.grad_out = last ? at.grad_out : w.grad(l.writes);
+        return fit_world_impl(model, prior, l.kind == Kind::persistent ? &pc : &ec, ev);
+    });
 }
 
-int lbfgs_check(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int max_iter, int* history_size, double lr,
-                const char* who) {
+// What the entries check alike, in the order they always have: the handles, the iteration count, the history, the step length,
+// the model's width, and in a chain (`followup`) the follow-up count.  Fills the widths and the history cut.
+struct LbfgsDims { int D, NB, P, history, H; };      // history: the caller's (0: the default), H: what the longest fit can fill of it
+int lbfgs_preamble(const char* who, const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int max_iter,
+                   const int* followup, int history_size, double lr, LbfgsDims* d) {
     if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
     if (max_iter < 1 || max_iter > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: max_iter=%d", who, max_iter);
-    if (*history_size <= 0) *history_size = k2b::kLbfgsMaxHistory;
-    if (*history_size > k2b::kLbfgsMaxHistory)
-        return fail(K2B_ERR_UNSUPPORTED, "%s: history_size=%d (at most %d)", who, *history_size, k2b::kLbfgsMaxHistory);
+    if (history_size <= 0) history_size = k2b::kLbfgsMaxHistory;
+    if (history_size > k2b::kLbfgsMaxHistory)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: history_size=%d (at most %d)", who, history_size, k2b::kLbfgsMaxHistory);
     if (!(lr > 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lr must be positive", who);
-    if (3 + 3 * (model->J - 1) + model->NB + 3 > 256)
-        return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 256)", who, 3 + 3 * (model->J - 1) + model->NB + 3);
+    d->D = 3 * (model->J - 1); d->NB = model->NB; d->P = 3 + d->D + d->NB + 3;
+    if (d->P > 256) return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 256)", who, d->P);
+    if (followup && (*followup < 1 || *followup > 10000)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, *followup);
+    d->history = history_size;
+    d->H = k2b::lbfgs_history_cut(history_size, followup && *followup > max_iter ? *followup : max_iter);
     return K2B_OK;
+}
+bool any_null(const ConstParams& in, const Params& out) {
+    return !in.go || !in.bp || !in.be || !in.tr || !out.go || !out.bp || !out.be || !out.tr;
 }
 
 // The default sequence mode in ONE launch (k2b_fit.hip: chain + LbMode::persistent): the frame loop runs inside the persistent launch -
@@ -141,9 +147,9 @@ int lbfgs_check(const k2b_model* model, const k2b_prior* prior, const k2b_fit_co
 int lbfgs_chain_launch(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, FitCall c, const k2b::LbfgsArgs& la,
                        int followup_iters) {
     k2b_fit_config pc = *cfg;
-    pc.num_iters = la.max_eval + 3;                                       // rounds + the closure at the result
+    pc.num_iters = k2b::lbfgs_persistent_closures(la.max_iter);
     pc.step_size = 0.0;
-    c.chain.iters = followup_iters * 5 / 4 + 3;
+    c.chain.iters = k2b::lbfgs_followup_closures(followup_iters);
     c.lbfgs.mode = k2b::LbMode::persistent; c.lbfgs.args = &la; c.lbfgs.chain_max_iter = followup_iters;
     return fit_world_impl(model, prior, &pc, c);
 }
@@ -162,34 +168,28 @@ int k2b_fit_world_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const 
                         float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out, float* grad_out,
                         int32_t max_iter, int32_t history_size, double lr, double tolerance_grad, double tolerance_change,
                         void* stream_v) {
-    if (const int rc = lbfgs_check(model_c, prior, cfg, max_iter, &history_size, lr, "k2b_fit_world_lbfgs"); rc != K2B_OK) return rc;
-    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world_lbfgs: num_frames=%d", B);
+    const char* who = "k2b_fit_world_lbfgs";
+    LbfgsDims d;
+    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, max_iter, nullptr, history_size, lr, &d); rc != K2B_OK) return rc;
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_frames=%d", who, B);
     if (B == 0) return K2B_OK;
-    if (!go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world_lbfgs: NULL parameter buffer");
+    const ConstParams in{go_in, bp_in, be_in, tr_in};
+    const Params out{go_out, bp_out, be_out, tr_out};
+    if (any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter buffer", who);
     hipStream_t stream = (hipStream_t)stream_v;
-    const int NB = model_c->NB, D = 3 * (model_c->J - 1), P = 3 + D + NB + 3;
-    const int H = history_size < max_iter ? history_size : max_iter;      // (a fit makes at most max_iter - 1 pairs)
     // stream-ordered workspace: optimiser state, closure results, the preserve pose and the translation prior's centre (their
     // defaults are the INITIAL parameters, which the parameter arrays stop holding after the first step)
-    LbfgsWs w{};
-    const size_t n_opt = lbfgs_ws_layout(B, P, H, &w);
+    const k2b::LbfgsWorldMap m = k2b::lbfgs_world_map(B, d.P, d.D, d.H);
     StreamWorkspace ws(stream);
-    HIP_TRY(ws.alloc(n_opt + ((size_t)B * D + (size_t)B * 3) * sizeof(float)));
-#define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_world_lbfgs: HIP call failed")
-    float *pres = lbfgs_ws_assign(&w, ws.get(), B, P), *trp = pres + (size_t)B * D;
-    TRY_Q(hipMemcpyAsync(pres, preserve ? preserve : bp_in, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    TRY_Q(hipMemcpyAsync(trp, tr_prior ? tr_prior : tr_in, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    const struct { const float* src; float* dst; size_t n; } cp[] = {
-        {go_in, go_out, (size_t)B * 3}, {bp_in, bp_out, (size_t)B * D}, {be_in, be_out, (size_t)B * NB}, {tr_in, tr_out, (size_t)B * 3}};
-    for (const auto& c : cp)
-        if (c.src != c.dst) TRY_Q(hipMemcpyAsync(c.dst, c.src, c.n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-#undef TRY_Q
+    HIP_TRY(ws.alloc(m.total));
+    LbfgsWs w{ws.get(), m.opt, false};
+    float *pres = ws_at<float>(ws.get(), m.preserve), *trp = ws_at<float>(ws.get(), m.tr_prior);
+    HIP_TRY_MSG(start_in_place(B, d.D, d.NB, in, out, preserve, tr_prior, pres, trp, stream), "%s: HIP call failed", who);
     FitCall at = fit_call(B, K, model_joint_index, j3d, conf, stream_v);
-    at.out = {go_out, bp_out, be_out, tr_out};
+    at.out = out;
     at.preserve = pres; at.loss_out = loss_out; at.grad_out = grad_out;
     at.tr_prior = (tr_prior || cfg->transl_prior_weight != 0.0f) ? trp : nullptr;   // (the tree kernel has no translation prior)
-    return lbfgs_run(model_c, prior, cfg, at, {max_iter, H, lr, tolerance_grad, tolerance_change}, w);
+    return lbfgs_run(model_c, prior, cfg, at, {max_iter, d.H, lr, tolerance_grad, tolerance_change}, w);
 }
 
 // The reference's DEFAULT sequence mode in one call: the frame loop of optimize_params_sequence with use_previous_frame_init=True
@@ -202,34 +202,34 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
                            const float* bp_in, const float* be_in, const float* tr_in, float* go_out, float* bp_out, float* be_out,
                            float* tr_out, float* loss_out, int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr,
                            double tolerance_grad, double tolerance_change, void* stream_v) {
-    if (const int rc = lbfgs_check(model_c, prior, cfg, first_iters, &history_size, lr, "k2b_fit_sequence_lbfgs"); rc != K2B_OK) return rc;
-    if (followup_iters < 1 || followup_iters > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: followup_iters=%d", followup_iters);
-    if (T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: frames=%d", T);
-    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence_lbfgs: no translation prior in a chain");
+    const char* who = "k2b_fit_sequence_lbfgs";
+    LbfgsDims d;
+    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, first_iters, &followup_iters, history_size, lr, &d); rc != K2B_OK) return rc;
+    if (T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: frames=%d", who, T);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_UNSUPPORTED, "%s: no translation prior in a chain", who);
     if (T == 0) return K2B_OK;
-    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence_lbfgs: NULL parameter / target buffer");
+    const ConstParams in{go_in, bp_in, be_in, tr_in};
+    const Params out{go_out, bp_out, be_out, tr_out};
+    if (!j3d || any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
     hipStream_t stream = (hipStream_t)stream_v;
-    const int NB = model_c->NB, D = 3 * (model_c->J - 1), P = 3 + D + NB + 3;
-    const int it_max = first_iters > followup_iters ? first_iters : followup_iters;
-    const int Hmax = history_size < it_max ? history_size : it_max;
-    LbfgsWs w{};
-    const size_t n_opt = lbfgs_ws_layout(1, P, Hmax, &w);
+    const int D = d.D, NB = d.NB;
+    const k2b::LbfgsSequenceMap m = k2b::lbfgs_sequence_map(d.P, D, d.H);
     StreamWorkspace ws(stream);
-    HIP_TRY(ws.alloc(n_opt + (size_t)D * sizeof(float)));
+    HIP_TRY(ws.alloc(m.total));
 #define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_fit_sequence_lbfgs: HIP call failed")
-    float* pres = lbfgs_ws_assign(&w, ws.get(), 1, P);
+    LbfgsWs w{ws.get(), m.opt, false};
+    float* pres = ws_at<float>(ws.get(), m.preserve);
     // the whole sequence in ONE launch where the fused kernel takes it (24-joint model, the prior over the whole pose, kinematic targets)
     // (one sequence = one chain slot; any K2B_LBFGS_SCHEME but 0 keeps it out of the chain)
     const bool fused_ok = fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index);
     if (lbfgs_scheme() == 0 && T > 1 &&
         k2b::lbfgs_scheme_for(1, device_cus(), fused_ok, lbfgs_stage_cap(), 0) == k2b::LbfgsScheme::persistent) {
         FitCall c = fit_call(1, K, model_joint_index, j3d, conf, stream_v);
-        c.in = {go_in, bp_in, be_in, tr_in};
-        c.out = {go_out, bp_out, be_out, tr_out};                             // rows t of the outputs: frame t's point
+        c.in = in;
+        c.out = out;                                                          // rows t of the outputs: frame t's point
         c.loss_out = loss_out; c.chain.len = T;
-        const k2b::LbfgsArgs la = make_lbfgs_args(1, model_c, {first_iters, Hmax, lr, tolerance_grad, tolerance_change}, c.out, w);
-        TRY_Q(hipMemsetAsync(w.base, 0, w.off_sv, stream));
+        const k2b::LbfgsArgs la = make_lbfgs_args(1, model_c, {first_iters, d.H, lr, tolerance_grad, tolerance_change}, c.out, w);
+        TRY_Q(w.clear(stream));
         return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
     }
     k2b_fit_config fc = *cfg;
@@ -239,15 +239,16 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
         const float *sgo = t ? go - 3 : go_in, *sbp = t ? bp - D : bp_in, *sbe = t ? be - NB : be_in, *str = t ? tr - 3 : tr_in;
         // start of this frame = the start given (frame 0) or the previous frame's result; its body pose is also what is preserved
         // (one small launch: the four parameter rows, the preserve pose and the cleared optimiser state)
-        TRY_Q(k2b::launch_lbfgs_frame_prep(go, sgo, bp, sbp, be, sbe, tr, str, pres, D, NB, w.base, w.off_sv, stream));
+        TRY_Q(k2b::launch_lbfgs_frame_prep(go, sgo, bp, sbp, be, sbe, tr, str, pres, D, NB, ws_at<void>(ws.get(), m.opt.state),
+                                           k2b::lbfgs_clear_bytes(m.opt), stream));
         w.state_cleared = true;
         fc.pose_preserve_weight = t ? cfg->pose_preserve_weight : 0.0f;
         const int iters = t ? followup_iters : first_iters;
-        const int H = history_size < iters ? history_size : iters;
         FitCall at = fit_call(1, K, model_joint_index, j3d + (size_t)t * K * 3,
                               conf ? conf + (cfg->conf_per_frame ? (size_t)t * K : 0) : nullptr, stream_v);
         at.out = {go, bp, be, tr}; at.preserve = pres; at.loss_out = loss_out ? loss_out + t : nullptr;
-        if (const int rc = lbfgs_run(model_c, prior, &fc, at, {iters, H, lr, tolerance_grad, tolerance_change}, w); rc != K2B_OK) return rc;
+        const LbfgsOpts o{iters, k2b::lbfgs_history_cut(d.history, iters), lr, tolerance_grad, tolerance_change};
+        if (const int rc = lbfgs_run(model_c, prior, &fc, at, o, w); rc != K2B_OK) return rc;
     }
 #undef TRY_Q
     return K2B_OK;
@@ -265,34 +266,30 @@ int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, co
     const char* who = "k2b_fit_sequences_lbfgs";
     RaggedSlots r;
     if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
-    if (const int rc = lbfgs_check(model_c, prior, cfg, first_iters, &history_size, lr, who); rc != K2B_OK) return rc;
-    if (followup_iters < 1 || followup_iters > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
+    LbfgsDims d;
+    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, first_iters, &followup_iters, history_size, lr, &d); rc != K2B_OK) return rc;
     if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
     if (const int rc = check_targets(who, model_c, K, model_joint_index); rc != K2B_OK) return rc;
     if (r.slots == 0) return K2B_OK;
-    if (!j3d || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    const ConstParams in{go_in, bp_in, be_in, tr_in};
+    const Params out{go_out, bp_out, be_out, tr_out};
+    if (!j3d || any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
     if (!(fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)))
         return fail(K2B_ERR_UNSUPPORTED, "%s: one launch needs the 24-joint model, the prior over the whole pose and kinematic targets", who);
     hipStream_t stream = (hipStream_t)stream_v;
-    const int P = 3 + 3 * (model_c->J - 1) + model_c->NB + 3;
-    const int it_max = first_iters > followup_iters ? first_iters : followup_iters;
-    const int Hmax = history_size < it_max ? history_size : it_max;
-    LbfgsWs w{};
-    const size_t n_opt = lbfgs_ws_layout(r.slots, P, Hmax, &w);
-    const size_t n_meta = (r.meta.size() * sizeof(int) + 15) / 16 * 16;
+    const k2b::LbfgsSequencesMap m = k2b::lbfgs_sequences_map(r.slots, d.P, d.H);
     StreamWorkspace ws(stream);
-    HIP_TRY(ws.alloc(n_meta + n_opt));
-    int* meta = reinterpret_cast<int*>(ws.get());
+    HIP_TRY(ws.alloc(m.total));
+    int* meta = ws_at<int>(ws.get(), m.meta);
     if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) return rc;
-    HIP_TRY_MSG(hipMemsetAsync(ws.get() + n_meta, 0, w.off_sv, stream), "%s: HIP call failed", who);
-    (void)lbfgs_ws_assign(&w, ws.get() + n_meta, r.slots, P);
+    const LbfgsWs w{ws.get(), m.opt, false};
+    HIP_TRY_MSG(w.clear(stream), "%s: HIP call failed", who);
     // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: LbMode::persistent)
     FitCall c = fit_call(r.slots, K, model_joint_index, j3d, conf, stream_v);
-    c.in = {go_in, bp_in, be_in, tr_in};
-    c.out = {go_out, bp_out, be_out, tr_out};                                 // frame rows of the outputs: each frame's point
+    c.in = in;
+    c.out = out;                                                              // frame rows of the outputs: each frame's point
     c.loss_out = loss_out; c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.meta = meta;
-    const k2b::LbfgsArgs la = make_lbfgs_args(r.slots, model_c, {first_iters, Hmax, lr, tolerance_grad, tolerance_change}, c.out, w);
+    const k2b::LbfgsArgs la = make_lbfgs_args(r.slots, model_c, {first_iters, d.H, lr, tolerance_grad, tolerance_change}, c.out, w);
     return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
 }
 
@@ -307,9 +304,10 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
                          float* betas_out, int32_t max_iter, int32_t history_size, double lr, double tolerance_grad,
                          double tolerance_change, void* stream_v) {
     const char* who = "k2b_shape_pass_lbfgs";
-    if (const int rc = lbfgs_check(model_c, prior, cfg, max_iter, &history_size, lr, who); rc != K2B_OK) return rc;
+    LbfgsDims d;
+    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, max_iter, nullptr, history_size, lr, &d); rc != K2B_OK) return rc;
     if (num_sequences < 0 || num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: %d sequences, %d frames", who, num_sequences, num_frames);
-    const int J = model_c->J, NB = model_c->NB, D = 3 * (J - 1), P = 3 + D + NB + 3;
+    const int J = model_c->J, NB = d.NB, D = d.D;
     if (root_joint < 0 || root_joint >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: root_joint=%d", who, root_joint);
     if (num_free_betas < 1 || num_free_betas > NB || num_free_betas > 32)
         return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_free_betas=%d (1..min(%d, 32))", who, num_free_betas, NB);
@@ -322,48 +320,49 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
         return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL buffer", who);
     hipStream_t stream = (hipStream_t)stream_v;
     const int S = num_sequences, N = num_frames, nb = num_free_betas;
-    const int H = history_size < max_iter ? history_size : max_iter;
-    LbfgsWs w{};
-    const size_t n_opt = lbfgs_ws_layout(S, P, H, &w);
     // behind the optimiser's workspace: its parameter arrays [S][...], then the per-frame closure buffers [N][...]
-    const size_t n_par = (size_t)S * P, n_frm = (size_t)N * (NB + 3 + 3 + D + NB + 3 + 1 + P);
+    const k2b::ShapePassMap m = k2b::shape_pass_map(S, N, d.P, D, NB, d.H);
     StreamWorkspace ws(stream);
-    HIP_TRY(ws.alloc(n_opt + (n_par + n_frm) * sizeof(float)));
+    HIP_TRY(ws.alloc(m.total));
 #define TRY_Q(expr) HIP_TRY_MSG(expr, "k2b_shape_pass_lbfgs: HIP call failed")
-    float* go_s = lbfgs_ws_assign(&w, ws.get(), S, P);
-    float *bp_s = go_s + (size_t)S * 3, *be_s = bp_s + (size_t)S * D, *tr_s = be_s + (size_t)S * NB;
-    float *be_f = tr_s + (size_t)S * 3, *tr_f = be_f + (size_t)N * NB;
-    float *go_o = tr_f + (size_t)N * 3, *bp_o = go_o + (size_t)N * 3, *be_o = bp_o + (size_t)N * D, *tr_o = be_o + (size_t)N * NB;
-    float *loss_f = tr_o + (size_t)N * 3, *grad_f = loss_f + N;
-    TRY_Q(hipMemsetAsync(w.base, 0, w.off_sv, stream));                                   // every instance in phase INIT
-    TRY_Q(hipMemsetAsync(go_s, 0, n_par * sizeof(float), stream));                        // pose / transl of the points: 0, never move
-    TRY_Q(hipMemcpy2DAsync(be_s, (size_t)NB * sizeof(float), betas_in, (size_t)nb * sizeof(float), (size_t)nb * sizeof(float), S,
+    const LbfgsWs w{ws.get(), m.opt, false};
+    auto f = [&](size_t off) { return ws_at<float>(ws.get(), off); };
+    const Params pts{f(m.go_s), f(m.bp_s), f(m.be_s), f(m.tr_s)};
+    TRY_Q(w.clear(stream));                                                               // every instance in phase INIT
+    TRY_Q(hipMemsetAsync(pts.go, 0, m.points_bytes, stream));                             // pose / transl of the points: 0, never move
+    TRY_Q(hipMemcpy2DAsync(pts.be, (size_t)NB * sizeof(float), betas_in, (size_t)nb * sizeof(float), (size_t)nb * sizeof(float), S,
                            hipMemcpyDeviceToDevice, stream));
     k2b::ShapePassArgs sa{};
     sa.S = S; sa.D = D; sa.NB = NB; sa.nb = nb; sa.seq_off = seq_offsets;
     sa.jt0 = model_c->j_template.get() + (size_t)root_joint * 3; sa.jd0 = model_c->j_dirs.get() + (size_t)root_joint * 3 * NB;
-    sa.root_y = root_targets; sa.be_state = be_s; sa.be_f = be_f; sa.tr_f = tr_f; sa.grad_f = grad_f; sa.loss_f = loss_f;
-    sa.grad_state = w.gbuf; sa.loss_state = w.lbuf;
+    sa.root_y = root_targets; sa.be_state = pts.be; sa.be_f = f(m.be_f); sa.tr_f = f(m.tr_f); sa.grad_f = f(m.grad_f); sa.loss_f = f(m.loss_f);
+    sa.grad_state = w.grad(k2b::LbfgsBuf::A); sa.loss_state = w.loss(k2b::LbfgsBuf::A);
     k2b_fit_config ec = *cfg;
     ec.num_iters = 1;
     ec.step_size = 0.0;                                                                  // evaluate-only: the closure
     ec.conf_per_frame = conf ? 1 : 0;
     FitCall ev = fit_call(N, K, model_joint_index, j3d, conf, stream_v);
-    ev.in = {global_orient, body_pose, be_f, tr_f};
-    ev.out = {go_o, bp_o, be_o, tr_o};
-    ev.loss_out = loss_f; ev.grad_out = grad_f;
-    k2b::LbfgsArgs la = make_lbfgs_args(S, model_c, {max_iter, H, lr, tolerance_grad, tolerance_change}, {go_s, bp_s, be_s, tr_s}, w);
-    const int rounds = la.max_eval + 2, stage_cap = lbfgs_stage_cap();
-    for (int r = 0; r < rounds; ++r) {
+    ev.in = {global_orient, body_pose, sa.be_f, sa.tr_f};
+    ev.out = {f(m.go_o), f(m.bp_o), f(m.be_o), f(m.tr_o)};
+    ev.loss_out = f(m.loss_f); ev.grad_out = f(m.grad_f);
+    const k2b::LbfgsArgs la = make_lbfgs_args(S, model_c, {max_iter, d.H, lr, tolerance_grad, tolerance_change}, pts, w);
+    // two launches per round with [prep, fit, reduce] as the closure; nothing asks for the loss at the result: the schedule
+    // ends with its finalise step (the accepted points)
+    const k2b::LbfgsScheme scheme = k2b::LbfgsScheme::two_launches;
+    const int rounds = k2b::lbfgs_rounds(max_iter), stage_cap = lbfgs_stage_cap();
+    const int rc = lbfgs_drive(scheme, rounds, k2b::lbfgs_launch_count(scheme, rounds) - 1, [&](const k2b::LbfgsLaunch& l) -> int {
+        if (l.kind == k2b::LbfgsLaunchKind::step) {
+            TRY_Q(k2b::launch_lbfgs_step(step_args(la, l), stream, stage_cap));
+            return K2B_OK;
+        }
         TRY_Q(k2b::launch_shape_prep(sa, stream));
         if (N > 0)
-            if (const int rc = fit_world_impl(model_c, prior, &ec, ev); rc != K2B_OK) return rc;
+            if (const int frc = fit_world_impl(model_c, prior, &ec, ev); frc != K2B_OK) return frc;
         TRY_Q(k2b::launch_shape_reduce(sa, stream));
-        TRY_Q(k2b::launch_lbfgs_step(la, stream, stage_cap));
-    }
-    la.finalize = 1;
-    TRY_Q(k2b::launch_lbfgs_step(la, stream, stage_cap));                                           // the accepted points
-    TRY_Q(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), be_s, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
+        return K2B_OK;
+    });
+    if (rc != K2B_OK) return rc;
+    TRY_Q(hipMemcpy2DAsync(betas_out, (size_t)nb * sizeof(float), pts.be, (size_t)NB * sizeof(float), (size_t)nb * sizeof(float), S,
                            hipMemcpyDeviceToDevice, stream));
 #undef TRY_Q
     return K2B_OK;
@@ -408,16 +407,15 @@ int k2b_debug_lbfgs_step(int32_t B, int32_t D, int32_t NB, float* go, float* bp,
     if (B == 0) return K2B_OK;
     if (!go || !bp || !be || !tr || !state) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / state buffer", who);
     if (!finalize && (!loss || !grad)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL closure result", who);
-    LbfgsWs w{};
-    const size_t need = k2b::lbfgs_state_bytes(B, P, H, &w.off_si, &w.off_sv);
+    LbfgsWs w{static_cast<unsigned char*>(state), {}, false};
+    const size_t need = k2b::lbfgs_state_bytes(B, P, H, &w.m.ints, &w.m.vectors);
     if (state_bytes < 0 || (size_t)state_bytes < need)
         return fail(K2B_ERR_INVALID_ARGUMENT, "%s: state buffer of %lld bytes, %zu needed", who, (long long)state_bytes, need);
     if (reinterpret_cast<uintptr_t>(state) % 16) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: state buffer not 16-byte aligned", who);
-    w.base = static_cast<unsigned char*>(state);
-    // (a finalize call consumes no result, but the kernel requests the gradient row with the state vectors: any readable rows do)
-    w.lbuf = const_cast<float*>(loss);
-    w.gbuf = const_cast<float*>(grad ? grad : reinterpret_cast<const float*>(w.base + w.off_sv));
     k2b::LbfgsArgs la = make_lbfgs_args(B, D, NB, {max_iter, H, lr, tolerance_grad, tolerance_change}, {go, bp, be, tr}, w);
+    // (a finalize call consumes no result, but the kernel requests the gradient row with the state vectors: any readable rows do)
+    la.loss_in = loss;
+    la.grad_in = grad ? grad : la.sv;
     la.finalize = finalize ? 1 : 0;
     HIP_TRY_MSG(k2b::launch_lbfgs_step(la, (hipStream_t)stream_v, max_staged_pairs < 0 ? -1 : max_staged_pairs), "%s: launch failed", who);
     return K2B_OK;

@@ -234,6 +234,11 @@ inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, 
     return c;
 }
 int fit_world_impl(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& call);
+// The in-place start of a fit that steps in the output arrays: the defaults of the preserve pose and of the translation prior's
+// centre are the INITIAL parameters, so they go to scratch (`pres` [B][D], `trp` [B][3]) first; then the start goes into the
+// outputs where the two differ.
+hipError_t start_in_place(int B, int D, int NB, const ConstParams& in, const Params& out, const float* preserve, const float* tr_prior,
+                          float* pres, float* trp, hipStream_t stream);
 
 // Whether the fused 24-lane kernel takes calls of (model, prior, cfg), and the prior width the call means.  k2b_fit.hip relies
 // on `fused` having been checked here.

@@ -7,6 +7,7 @@
 
 #include "k2b_device.h"
 #include "k2b_launch_plan.h"   // (and k2b_layout.h: kFitJoints, kPrior*, the fit kernel's LDS layout)
+#include "k2b_lbfgs_plan.h"    // kLbfgsMaxHistory, lbfgs_state_bytes / lbfgs_state_rows, the schedule and the workspace maps
 
 namespace k2b {
 
@@ -314,10 +315,7 @@ inline hipError_t ensure_dynamic_lds(Kernel kernel, std::atomic<unsigned long lo
 }
 
 // ---- device-resident L-BFGS (k2b_lbfgs.hip): one state machine per frame, one closure result consumed per step launch ----------
-constexpr int kLbfgsMaxHistory = 100;    // torch.optim.LBFGS's default history_size
-size_t lbfgs_state_bytes(int B, int P, int H, size_t* off_si, size_t* off_sv);
-void lbfgs_state_rows(int H, int* doubles_per_frame, int* ints_per_frame);       // row lengths of the two scalar blocks (k2b_lbfgs_device.h)
-hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_staged_pairs = -1);   // (P <= 256; < 0: no cap on the staged pairs)
+hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_staged_pairs = -1);   // (plan_lbfgs_step; < 0: no cap on the staged pairs)
 hipError_t launch_lbfgs_frame_prep(float* go, const float* sgo, float* bp, const float* sbp, float* be, const float* sbe, float* tr,
                                    const float* str, float* pres, int D, int NB, void* state, size_t state_bytes, hipStream_t stream);
 

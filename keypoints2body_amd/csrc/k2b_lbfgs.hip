@@ -59,35 +59,12 @@ hipError_t launch_lbfgs_frame_prep(float* go, const float* sgo, float* bp, const
     return hipGetLastError();
 }
 
-size_t lbfgs_state_bytes(int B, int P, int H, size_t* off_si, size_t* off_sv) {
-    size_t n = (size_t)B * (SD_RO + H) * sizeof(double);
-    *off_si = n;
-    n += (size_t)B * SI_COUNT * sizeof(int);
-    n = (n + 15) / 16 * 16;
-    *off_sv = n;
-    n += (size_t)B * (SV_HIST + 2 * (size_t)H) * P * sizeof(float);
-    return n;
-}
-
-void lbfgs_state_rows(int H, int* doubles_per_frame, int* ints_per_frame) {
-    *doubles_per_frame = SD_RO + H;
-    *ints_per_frame = SI_COUNT;
-}
-
 hipError_t launch_lbfgs_step(const LbfgsArgs& a, hipStream_t stream, int max_staged_pairs) {
     if (a.B <= 0) return hipSuccess;
-    if (a.P > 64 * kEplWide || a.H < 1 || a.H > kLbfgsMaxHistory) return hipErrorInvalidValue;
-    // LDS: the alphas, then as many staged history pairs as a fit can collect (one per outer iteration) - within 48 KiB, so that
-    // several frames share a CU; pairs beyond that are read from global memory.  (P > 192: a pair is 2 KiB and H = 30 leaves room
-    // for 23 of the 30, so the reference's default max_iter = 30 reads pairs 23.. from global memory - tests/test_gpu_lbfgs_wide.py.)
-    // max_staged_pairs >= 0 caps the number further (development switch: the results do not depend on it).
-    const int PL = (a.P + 63) / 64 * 64, room = lbfgs_staged_pairs(lbfgs_step_lds_bytes(), a.P, a.H);
-    int pairs = a.H < a.max_iter ? a.H : a.max_iter;
-    if (pairs > room) pairs = room;
-    if (max_staged_pairs >= 0 && pairs > max_staged_pairs) pairs = max_staged_pairs;
-    const size_t lds = (size_t)2 * a.H * sizeof(double) + (size_t)pairs * 2 * PL * sizeof(float);
-    if (a.P <= 64 * kEpl) hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEpl>, dim3(a.B), dim3(64), lds, stream, a, pairs);
-    else hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEplWide>, dim3(a.B), dim3(64), lds, stream, a, pairs);
+    const LbfgsStepPlan p = plan_lbfgs_step(a.P, a.H, a.max_iter, max_staged_pairs);
+    if (!p.ok) return hipErrorInvalidValue;
+    if (!p.wide) hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEpl>, dim3(a.B), dim3(64), (size_t)p.lds_bytes, stream, a, p.pairs);
+    else hipLaunchKernelGGL(k2b_lbfgs_step_kernel<kEplWide>, dim3(a.B), dim3(64), (size_t)p.lds_bytes, stream, a, p.pairs);
     return hipGetLastError();
 }
 

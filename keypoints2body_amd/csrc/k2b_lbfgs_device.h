@@ -1,8 +1,9 @@
 // k2b_lbfgs_device.h - the per-frame L-BFGS state machine as device code: one wavefront per frame, one closure result consumed
 // per call.  Included by k2b_lbfgs.hip (the stand-alone step kernel) and by k2b_fit.hip (the step as a prologue of the closure's
-// own launch).  Algorithm, state layout and references: k2b_lbfgs.hip.
+// own launch).  Algorithm and references: k2b_lbfgs.hip; state layout: k2b_lbfgs_plan.h.
 #pragma once
 #include "k2b_internal.h"
+#include "k2b_lbfgs_plan.h"   // the state layout (PH_*, SD_*, SI_*, SV_*) and the elements per lane (kEpl, kEplWide)
 
 // No FMA contraction in the optimiser: its code is inlined into three kernels (the step kernel, the closure's prologue, the
 // persistent loop), and what the compiler fuses depends on the context - a one-ulp difference in a search direction is enough for
@@ -11,19 +12,6 @@
 
 namespace k2b {
 namespace lbfgs_dev {
-
-enum { PH_INIT = 0, PH_BRACKET = 1, PH_ZOOM = 2, PH_DONE = 3 };
-// per-frame scalars (double) and integers.  THE order of a frame's two state rows: the development entry k2b_debug_lbfgs_step
-// (include/k2b.h) hands the rows back as they are, and the binding names their columns after these enumerators, lower case,
-// without the prefix (native.LBFGS_STATE_DOUBLES / LBFGS_STATE_INTS; tests/test_host_logic.py holds the two together):
-//   doubles [SD_RO + H]: loss, prev_loss, hdiag, t, t_prev, f_prev, gtd_prev, f0, gtd0, dnorm, bt0, bt1, bf0, bf1, bg0, bg1, ro[H]
-//   integers [SI_COUNT]: phase, nold, niter, evals, ls_iter, max_ls, ls_evals, first, low, insuf, head
-// State: the doubles of all frames, then the integers of all frames, then (16-byte aligned) the vectors (lbfgs_state_bytes).
-enum { SD_LOSS, SD_PREV_LOSS, SD_HDIAG, SD_T, SD_T_PREV, SD_F_PREV, SD_GTD_PREV, SD_F0, SD_GTD0, SD_DNORM, SD_BT0, SD_BT1, SD_BF0, SD_BF1,
-       SD_BG0, SD_BG1, SD_RO };                      // SD_RO .. SD_RO + H - 1: 1 / (y . s) of the history pairs
-enum { SI_PHASE, SI_NOLD, SI_NITER, SI_EVALS, SI_LS_ITER, SI_MAX_LS, SI_LS_EVALS, SI_FIRST, SI_LOW, SI_INSUF, SI_HEAD, SI_COUNT };
-// per-frame vectors (float [P] each), then Y [H][P] and S [H][P]
-enum { SV_X, SV_G, SV_PREV_G, SV_D, SV_G_PREV, SV_G0, SV_BG0, SV_BG1, SV_HIST };
 
 // sum over the wave in double, the same in every lane: an inclusive DPP scan (five row steps + the lower half's total into the
 // upper half, k2b_lanes.h) and lane 63's value.  (Six rounds of `__shfl_xor` on doubles - twelve ds_bpermute round trips - were
@@ -90,12 +78,6 @@ struct Scal {
                                                                                                                    //  index would put them in scratch)
     int phase, nold, niter, evals, ls_iter, max_ls, ls_evals, first, low, insuf, head;
 };
-
-// Vector elements per lane, a compile-time parameter of the state machine: element e = lane + 64 k, k < EPL, so P <= 64 EPL.
-// Three cover the 24- and 52-joint models and the 55-joint one up to 24 shape coefficients (P <= 192): the fit kernel's three
-// inlined copies and the step kernel's narrow form.  Four (P <= 256) cover every model the library fits (the tree kernel:
-// 63 joints, 32 shape coefficients, P = 224): the step kernel's wide form only.
-constexpr int kEpl = 3, kEplWide = 4;
 
 // A step used to walk through global memory: every vector operation a loop of loads and stores, every decision behind the
 // round trip of the one before (9.6 us median, 12.8 us mean per step for one frame: more than the closure's launch).  Now the

@@ -520,7 +520,7 @@ def shape_pass_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, se
 
 
 # ---- development: the device L-BFGS state machine fed a caller's closure results (k2b_debug_lbfgs_step) ------------------------
-# columns of a frame's two scalar state rows, in the order of csrc/k2b_lbfgs_device.h's SD_* / SI_* enumerators
+# columns of a frame's two scalar state rows, in the order of csrc/k2b_lbfgs_plan.h's SD_* / SI_* enumerators
 LBFGS_STATE_DOUBLES = ("loss", "prev_loss", "hdiag", "t", "t_prev", "f_prev", "gtd_prev", "f0", "gtd0", "dnorm", "bt0", "bt1", "bf0",
                        "bf1", "bg0", "bg1", "ro")
 LBFGS_STATE_INTS = ("phase", "nold", "niter", "evals", "ls_iter", "max_ls", "ls_evals", "first", "low", "insuf", "head")

@@ -362,3 +362,60 @@ def test_default_sequence_mode_in_one_call_equals_the_frame_loop():
                                     pose_preserve_weight=cfg.frame.pose_preserve_weight, freeze_betas=cfg.frame.freeze_betas)
     for t in (0, 1, T - 1):
         assert torch.equal(api[t].params.body_pose, ref["body_pose"][t:t + 1]) and torch.equal(api[t].params.betas, ref["betas"][t:t + 1])
+
+
+def _refused_calls():
+    """(id, entry, what is wrong with the call, exception class of the status, substring of the library's message).  One frame, three
+    targets; ``cfg`` marks a non-zero translation prior weight, ``surface`` a target that is an extra joint."""
+    bad, unsup = ValueError, NotImplementedError
+    rows = []
+    for entry, who, it in (("world", "k2b_fit_world_lbfgs", "max_iter"), ("sequence", "k2b_fit_sequence_lbfgs", "first_iters"),
+                           ("sequences", "k2b_fit_sequences_lbfgs", "first_iters"), ("shape", "k2b_shape_pass_lbfgs", "max_iter")):
+        rows += [(entry, {it: 0}, bad, f"{who}: max_iter=0"), (entry, {it: 10001}, bad, f"{who}: max_iter=10001"),
+                 (entry, {"history_size": 101}, unsup, f"{who}: history_size=101 (at most 100)"),
+                 (entry, {"lr": 0.0}, bad, f"{who}: lr must be positive"), (entry, {"lr": -1e-2}, bad, f"{who}: lr must be positive")]
+    for entry, who in (("sequence", "k2b_fit_sequence_lbfgs"), ("sequences", "k2b_fit_sequences_lbfgs")):
+        rows += [(entry, {"followup_iters": 0}, bad, f"{who}: followup_iters=0"),
+                 (entry, {"followup_iters": 10001}, bad, f"{who}: followup_iters=10001"),
+                 (entry, {"null": True}, bad, f"{who}: NULL parameter / target buffer")]
+    rows += [("sequence", {"cfg": True}, unsup, "k2b_fit_sequence_lbfgs: no translation prior in a chain"),
+             ("sequences", {"cfg": True}, bad, "k2b_fit_sequences_lbfgs: transl_prior_weight must be 0 in a chain"),
+             ("world", {"null": True}, bad, "k2b_fit_world_lbfgs: NULL parameter buffer"),
+             ("shape", {"null": True}, bad, "k2b_shape_pass_lbfgs: NULL buffer"),
+             ("sequences", {"surface": True}, unsup,
+              "k2b_fit_sequences_lbfgs: one launch needs the 24-joint model, the prior over the whole pose and kinematic targets")]
+    return rows
+
+
+def test_device_lbfgs_entries_refuse_bad_calls_with_their_status_and_message():
+    """The argument checks of the four L-BFGS entries, call by call: the status class the binding raises and the text the library
+    recorded (``k2b_last_error``).  Nothing is launched by a refused call."""
+    m, pr = H.native_model(), H.native_prior()
+    assert m.num_output_joints > m.num_joints              # the model has extra joints: a surface target exists
+    j3d, (go, bp, be, tr) = _problem(1)
+    j3d = j3d[:, :3].contiguous()
+    off = torch.tensor([0, 1], dtype=torch.int32, device="cuda")
+
+    def call(entry, max_iter=5, first_iters=5, followup_iters=3, history_size=100, lr=1e-2, null=False, cfg=False, surface=False):
+        c = native.default_fit_config()
+        c.transl_prior_weight = 1.0 if cfg else 0.0
+        idx = [0, 1, m.num_joints] if surface else [0, 1, 2]
+        g = None if null else go
+        if entry == "world":
+            return native.fit_world_lbfgs(m, pr, c, idx, j3d, None, g, bp, be, tr, max_iter=max_iter, lr=lr, history_size=history_size)
+        if entry == "sequence":
+            return native.fit_sequence_lbfgs(m, pr, c, first_iters, followup_iters, idx, j3d, None, g, bp, be, tr, lr=lr,
+                                             history_size=history_size)
+        if entry == "sequences":
+            return native.fit_sequences_lbfgs(m, pr, c, first_iters, followup_iters, idx, [1], j3d, None, g, bp, be, tr, lr=lr,
+                                              history_size=history_size)
+        return native.shape_pass_lbfgs(m, pr, c, off, idx, j3d, None, g, bp, j3d[:, 0].contiguous(), 0, be, max_iter=max_iter, lr=lr,
+                                       history_size=history_size)
+
+    for entry, wrong, exc, text in _refused_calls():
+        with pytest.raises(exc) as info:
+            call(entry, **wrong)
+        assert text in str(info.value), (entry, wrong, str(info.value))
+    for entry in ("world", "sequence", "sequences", "shape"):                  # the same calls with nothing wrong go through
+        call(entry)
+    torch.cuda.synchronize()

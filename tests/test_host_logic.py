@@ -166,8 +166,8 @@ def test_debug_lbfgs_step_refuses_bad_calls_on_the_host_before_any_launch():
                             ((1, 70, 0), NotImplementedError, "history=0"), ((-1, 70, 3), ValueError, "num_frames=-1")):
         with pytest.raises(exc, match=text):
             native.lbfgs_debug_layout(*args)
-    # the binding names the state rows' columns after the enumerators of csrc/k2b_lbfgs_device.h, in their order
-    dev = (REPO / "keypoints2body_amd" / "csrc" / "k2b_lbfgs_device.h").read_text()
+    # the binding names the state rows' columns after the enumerators of csrc/k2b_lbfgs_plan.h, in their order
+    dev = (REPO / "keypoints2body_amd" / "csrc" / "k2b_lbfgs_plan.h").read_text()
     sd = re.search(r"enum \{ (SD_LOSS.*?) \};", dev, flags=re.S).group(1)
     si = re.search(r"enum \{ (SI_PHASE.*?) \};", dev, flags=re.S).group(1)
     names = lambda text, prefix: tuple(n[len(prefix):].lower() for n in re.findall(rf"\b{prefix}[A-Z0-9_]+", text))
