@@ -447,6 +447,30 @@ int k2b_angular_error_deg(int64_t n, const float *pred_rotvec, const float *gt_r
                           float *err_deg_out, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * k2b_point_error (ABI 1.6) — the positional metrics of a fit: MPJPE (align_mode 0, or 1 after a translation), PA-MPJPE
+ * (align_mode 3) and PVE (the same over vertices).  For each frame b of num_frames, two point sets x = pred[b], y = gt[b]:
+ *     err[b] = sum_i w_i |a(x_i) - y_i| / sum_i w_i         (a weighted mean of Euclidean distances, not an RMS)
+ *   pred, gt dev [B][N][3]; weights dev [N] shared by all frames, or [B][N] with weights_per_frame != 0, non-negative;
+ *   NULL = ones.
+ *   align_mode 0: a(x) = x.   1: a(x) = x + (ybar - xbar), the weighted centroids.
+ *              2: a(x) = R x + t, the rotation R in SO(3) and t that minimise sum w |R x + t - y|^2 (Kabsch).
+ *              3: a(x) = s R x + t (Umeyama); R is always a proper rotation, so a mirrored set is not aligned by a reflection.
+ *   err_out dev [B];  per_point_out dev [B][N] or NULL: the unweighted distances |a(x_i) - y_i|;
+ *   transform_out dev [B][13] or NULL: s, R row-major, t (modes 0 and 1: s = 1, R = I and the t that was used).
+ * Corner cases: all weighted points of x coincide (or N == 1): R = I, s = 1, t = ybar - xbar.  A frame whose weights sum to 0:
+ * err 0, distances 0, the identity transform.  A non-finite input makes that frame's outputs non-finite and no other frame's.
+ * Centroids, covariance, decomposition (Horn's quaternion form, a fixed number of Jacobi sweeps) and residuals are float64, the
+ * results rounded to float32 once.  Every sum has one fixed order: a frame's outputs are bit-identical from run to run and do
+ * not depend on num_frames or on the frame's position.  1 <= N <= 2^20; up to 256 points four frames share a workgroup, beyond
+ * that a frame has its own, and at most 2^24 - 1 workgroups fit the launch: otherwise K2B_ERR_UNSUPPORTED.  N < 1, B < 0, an
+ * align_mode outside 0..3, a NULL pred / gt / err_out: K2B_ERR_INVALID_ARGUMENT before any HIP call.  num_frames == 0 is a
+ * no-op.  Stream-ordered, one launch, no allocation, no synchronisation.
+ * ------------------------------------------------------------------------------- */
+int k2b_point_error(int32_t num_frames, int32_t num_points, const float *pred, const float *gt,
+                    const float *weights, int32_t weights_per_frame, int32_t align_mode,
+                    float *err_out, float *per_point_out, float *transform_out, void *stream) K2B_SINCE(1, 6);
+
+/* ---------------------------------------------------------------------------------
  * IK-GAT rotation regressor — inference of the reference's learned estimator
  * (core/estimators/ikgat/: gan_regressor.py:39-126, inference.py:39-43 and 83-120,
  * utils.py:13-52) in eval mode.  Per frame: joint positions minus joint 0 (plus the 6-D form

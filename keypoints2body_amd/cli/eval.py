@@ -3,7 +3,8 @@
     python -m keypoints2body_amd.cli.eval --amass-root DIR [--batch-sequences N] [...]
 
 Fits every ``*.npz`` sequence under ``--amass-root`` in world mode with the AMASS joint layout and reports the dataset MPJAE
-over ``global_orient + body_pose``, with the reference's flags, per-sequence failure accounting and final line.  Where the
+over ``global_orient + body_pose``, with the reference's flags, per-sequence failure accounting and final line.  With
+``--position-metrics`` it also reports MPJPE and PA-MPJPE of the fitted joints against the input joints.  Where the
 reference fits one sequence per call, this front end hands ``--batch-sequences`` sequences at a time to
 ``optimize_params_sequences`` (one launch for all their chains in the default warm-start world mode); the results equal the
 per-sequence calls bit for bit.  Loading, the MPJAE kernel and saving are ``keypoints2body_amd.evaluation``.  There is no
@@ -57,6 +58,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--prior-dir", type=Path, default=None, help="directory of gmm_08.pkl (default ./data/models/)")
     p.add_argument("--mean-file", type=Path, default=None,
                    help="mean pose / shape (.h5 or .npz; default ./data/models/neutral_smpl_mean_params.h5)")
+    p.add_argument("--position-metrics", action="store_true",
+                   help="also report MPJPE and PA-MPJPE (mm) of the fitted joints against the input joints")
     return p.parse_args(argv)
 
 
@@ -88,10 +91,12 @@ def _assets(args, device):
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    """Run the evaluation; prints the dataset MPJAE line and returns its value."""
+    """Run the evaluation; prints the dataset MPJAE line (after the two positional lines of ``--position-metrics``) and returns
+    the MPJAE."""
     import torch
     from .. import evaluation
     from ..api.sequence import optimize_params_sequences
+    from ..core.constants import category_indices
     args = parse_args(argv)
     configure_logging(args.log_level)
     if args.skip_start_frames < 0:
@@ -105,6 +110,9 @@ def main(argv: Optional[Sequence[str]] = None) -> float:
     model, prior, mean = _assets(args, device)
 
     totals = {"sum": 0.0, "count": 0, "ok": 0, "failed": 0}
+    # --position-metrics: the fit residual in positional terms, over the joints the fit matched (the AMASS correspondence)
+    position = {"none": [0.0, 0], "procrustes": [0.0, 0]}
+    model_rows, target_rows = category_indices("AMASS")
 
     def failed(path, exc):
         totals["failed"] += 1
@@ -112,7 +120,17 @@ def main(argv: Optional[Sequence[str]] = None) -> float:
         if args.fail_fast:
             raise exc
 
-    def score(path, gt_pose, pred_pose):
+    def score_positions(fit_joints, joints):
+        """Sequence MPJPE / PA-MPJPE in mm over the frames after --skip-start-frames; adds them to the dataset sums."""
+        fit = fit_joints[args.skip_start_frames:, model_rows]
+        tgt = torch.as_tensor(joints[args.skip_start_frames:, target_rows])
+        seq = {align: evaluation.evaluate_position_pair(fit, tgt, align=align, device=device) for align in position}
+        for align, (_, err_sum, frames) in seq.items():       # both values exist before either joins the dataset sums
+            position[align][0] += err_sum
+            position[align][1] += frames
+        return 1000.0 * seq["none"][0], 1000.0 * seq["procrustes"][0]
+
+    def score(path, gt_pose, pred_pose, fit_joints=None, joints=None):
         if args.skip_start_frames > 0:
             if pred_pose.shape[0] <= args.skip_start_frames:
                 raise ValueError(f"Sequence too short after skipping {args.skip_start_frames} frame(s): "
@@ -121,13 +139,18 @@ def main(argv: Optional[Sequence[str]] = None) -> float:
         else:
             pred_eval, gt_eval = pred_pose, gt_pose
         seq_mpjae, angle_sum, angle_count = evaluation.evaluate_pose_pair(pred_eval, gt_eval, device=device)
+        seq_mpjpe, seq_pa = score_positions(fit_joints, joints) if args.position_metrics else (None, None)
         totals["sum"] += angle_sum
         totals["count"] += angle_count
         totals["ok"] += 1
         if args.save_pred_dir is not None:
             evaluation.save_prediction_pose(pred_pose, path, args.amass_root, args.save_pred_dir)
-        logger.info("%s: MPJAE %.3f deg (dataset %.3f deg, %d ok, %d failed)", path.name, seq_mpjae,
-                    totals["sum"] / totals["count"], totals["ok"], totals["failed"])
+        if not args.position_metrics:
+            logger.info("%s: MPJAE %.3f deg (dataset %.3f deg, %d ok, %d failed)", path.name, seq_mpjae,
+                        totals["sum"] / totals["count"], totals["ok"], totals["failed"])
+            return
+        logger.info("%s: MPJAE %.3f deg, MPJPE %.3f mm, PA-MPJPE %.3f mm (dataset %.3f deg, %d ok, %d failed)", path.name,
+                    seq_mpjae, seq_mpjpe, seq_pa, totals["sum"] / totals["count"], totals["ok"], totals["failed"])
 
     cfg = sequence_config(args)
     for start in range(0, len(files), args.batch_sequences):
@@ -156,10 +179,10 @@ def main(argv: Optional[Sequence[str]] = None) -> float:
                 if batch is None:
                     one = optimize_params_sequences([joints], body_model="smpl", joint_layout="AMASS", model=model,
                                                     config=cfg, device=device, pose_prior=prior, mean_params=mean)
-                    pred = one.pose(0)
+                    pred, fit_joints = one.pose(0), one.joints_of(0)
                 else:
-                    pred = batch.pose(i)
-                score(path, gt_pose, np.asarray(pred.detach().cpu().numpy(), dtype=np.float32))
+                    pred, fit_joints = batch.pose(i), batch.joints_of(i)
+                score(path, gt_pose, np.asarray(pred.detach().cpu().numpy(), dtype=np.float32), fit_joints, joints)
             except Exception as exc:
                 failed(path, exc)
         logger.info("%d / %d sequences done", min(start + args.batch_sequences, len(files)), len(files))
@@ -169,6 +192,11 @@ def main(argv: Optional[Sequence[str]] = None) -> float:
     dataset_mpjae = totals["sum"] / totals["count"]
     logger.info("Finished evaluation: success=%d failed=%d dataset_MPJAE=%.6f deg", totals["ok"], totals["failed"],
                 dataset_mpjae)
+    if args.position_metrics:
+        mpjpe, pa_mpjpe = (1000.0 * acc[0] / acc[1] for acc in position.values())
+        logger.info("dataset_MPJPE=%.6f mm dataset_PA-MPJPE=%.6f mm over %d frames", mpjpe, pa_mpjpe, position["none"][1])
+        print(f"Dataset MPJPE(fit residual, {len(model_rows)} joints): {mpjpe:.6f} mm")
+        print(f"Dataset PA-MPJPE(fit residual, {len(model_rows)} joints): {pa_mpjpe:.6f} mm")
     print(f"Dataset MPJAE(global_orient + body_pose): {dataset_mpjae:.6f} deg")
     return dataset_mpjae
 

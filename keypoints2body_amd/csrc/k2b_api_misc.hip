@@ -1,6 +1,6 @@
 // k2b_api_misc.hip — the entries of the C ABI (include/k2b.h) that are one launch or none: version, the calling thread's
-// error message, config defaults, the LBS forward, the vertex / surface terms, the Adam step, the angular error and the
-// IK-GAT regressor.
+// error message, config defaults, the LBS forward, the vertex / surface terms, the Adam step, the angular and
+// positional errors and the IK-GAT regressor.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -55,7 +55,7 @@ int device_cus() {
 
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 5u; }
+uint32_t k2b_version(void) { return (1u << 16) | 6u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
@@ -225,6 +225,29 @@ int k2b_angular_error_deg(int64_t n, const float* pred_rotvec, const float* gt_r
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(K2B_ERR_NO_DEVICE, "k2b_angular_error_deg: no HIP device visible (this engine has no CPU path)");
     HIP_TRY(k2b::launch_angular_error(pred_rotvec, gt_rotvec, err_deg_out, (long long)n, (hipStream_t)stream_v));
+    return K2B_OK;
+}
+
+int k2b_point_error(int32_t B, int32_t N, const float* pred, const float* gt, const float* weights, int32_t weights_per_frame,
+                    int32_t align_mode, float* err_out, float* per_point_out, float* transform_out, void* stream_v) {
+    if (N < 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_point_error: num_points=%d must be >= 1", N);
+    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_point_error: num_frames=%d must be >= 0", B);
+    if (align_mode < 0 || align_mode > 3)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_point_error: align_mode=%d, expected 0 (none), 1 (translation), 2 (rigid) or 3 (similarity)", align_mode);
+    if (B == 0) return K2B_OK;
+    if (!pred || !gt || !err_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_point_error: NULL buffer (pred, gt and err_out are required)");
+    if (N > k2b::kPointErrorMaxPoints)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_point_error: num_points=%d, at most %d", N, k2b::kPointErrorMaxPoints);
+    if (k2b::point_error_workgroups(B, N) > k2b::kPointErrorMaxWorkgroups)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_point_error: num_frames=%d with num_points=%d exceeds one launch (%lld workgroups, at most %lld)", B, N,
+                    k2b::point_error_workgroups(B, N), k2b::kPointErrorMaxWorkgroups);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(K2B_ERR_NO_DEVICE, "k2b_point_error: no HIP device visible (this engine has no CPU path)");
+    k2b::PointErrorArgs a{};
+    a.pred = pred; a.gt = gt; a.weights = weights; a.weights_per_frame = weights_per_frame ? 1 : 0; a.align_mode = align_mode;
+    a.num_frames = B; a.num_points = N; a.err = err_out; a.per_point = per_point_out; a.transform = transform_out;
+    HIP_TRY(k2b::launch_point_error(a, (hipStream_t)stream_v));
     return K2B_OK;
 }
 

@@ -322,6 +322,28 @@ hipError_t launch_lbfgs_frame_prep(float* go, const float* sgo, float* bp, const
 // Geodesic angle (degrees) between n pairs of axis-angle rotations (evaluation metric, k2b_metrics.hip).
 hipError_t launch_angular_error(const float* pred, const float* gt, float* out, long long n, hipStream_t stream);
 
+// Positional error of B frames of N points after an alignment (MPJPE / PA-MPJPE / PVE, k2b_metrics.hip): one wave per frame
+// up to kPointErrorWavePoints points (four frames per workgroup), one workgroup per frame beyond.
+constexpr int kPointErrorWavePoints = 256;
+constexpr int kPointErrorMaxPoints = 1 << 20;
+struct PointErrorArgs {
+    const float* pred;       // [B][N][3]
+    const float* gt;         // [B][N][3]
+    const float* weights;    // [N], [B][N] (weights_per_frame) or NULL (ones)
+    int weights_per_frame;
+    int align_mode;          // 0 none, 1 translation, 2 rigid, 3 similarity
+    int num_frames, num_points;
+    float* err;              // [B]
+    float* per_point;        // [B][N] or NULL
+    float* transform;        // [B][13] or NULL: s, R row-major, t
+};
+// workgroups of the launch (256 threads each); the HIP runtime takes at most 2^32 - 1 threads per grid dimension
+inline long long point_error_workgroups(int num_frames, int num_points) {
+    return num_points <= kPointErrorWavePoints ? ((long long)num_frames + 3) / 4 : (long long)num_frames;
+}
+constexpr long long kPointErrorMaxWorkgroups = 0xffffffffll / 256;
+hipError_t launch_point_error(const PointErrorArgs& a, hipStream_t stream);
+
 // ---- IK-GAT regressor inference (k2b_ikgat.hip): B frames of J joint positions (+ input quaternions when in == 9) -> J
 // quaternions per frame.  Batched: ceil(B / F) workgroups of F frames; chain: one workgroup walks the B frames in order,
 // frame t + 1 reading frame t's outputs as its input quaternions.

@@ -1,4 +1,4 @@
-"""Pose-error evaluation (MPJAE) on the GPU: the consumer side of the fitting path.
+"""Pose-error (MPJAE) and positional-error evaluation on the GPU: the consumer side of the fitting path.
 
 Mirrors the library part of the reference's ``keypoints2body/cli/eval.py`` (the argument parser and the
 progress-bar loop around it are CLI and out of scope):
@@ -8,6 +8,9 @@ progress-bar loop around it are CLI and out of scope):
 * ``compute_angular_error_deg`` (``:131-140``) and ``evaluate_pose_pair`` (``:143-160``): the rotations go to
   the device once and ``k2b_angular_error_deg`` (csrc/k2b_metrics.hip) evaluates every pair in one launch; the
   sum is taken in float64 on the device, as the reference sums in float64 on the host.
+
+Beyond the reference: the positional metrics MPJPE / PA-MPJPE / PVE (``compute_position_error``, ``procrustes_align``,
+``evaluate_position_pair``) on ``k2b_point_error``, one launch per call.
 
 Like the rest of the package there is no CPU path: without a HIP device these functions raise.
 """
@@ -75,6 +78,65 @@ def evaluate_pose_pair(pred_pose, gt_pose, device=None) -> Tuple[float, float, i
     total = float(ang.double().sum())
     count = int(ang.numel())
     return total / count, total, count
+
+
+_POSITION_ALIGN = {"none": "none", "root": "none", "translation": "translation", "rigid": "rigid", "procrustes": "similarity"}
+
+
+def _point_device(pred, device):
+    return native.require_device(device if device is not None else (pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda else None))
+
+
+def compute_position_error(pred, gt, *, align: str = "none", root: int = 0, weights=None, device=None) -> torch.Tensor:
+    """Per-frame positional error between point sets ``(..., N, 3)``: the (weighted) mean distance of corresponding points,
+    as a device tensor of shape ``(...)``.  With joints this is MPJPE, with vertices PVE.  ``align``: ``"none"``, ``"root"``
+    (point ``root`` of each set moved to the origin first), ``"translation"`` (centroids matched), ``"rigid"`` (Kabsch) or
+    ``"procrustes"`` (similarity, Umeyama: PA-MPJPE).  One launch of ``k2b_point_error`` (csrc/k2b_metrics.hip), float64
+    inside.  A frame whose weights sum to zero has error 0."""
+    if align not in _POSITION_ALIGN:
+        raise ValueError(f"align must be one of {sorted(_POSITION_ALIGN)}, got {align!r}")
+    dev = _point_device(pred, device)
+    p, g = _device_f32(pred, dev), _device_f32(gt, dev)
+    if align == "root":
+        if tuple(p.shape) != tuple(g.shape) or p.dim() < 2:
+            raise ValueError(f"expected two (...,N,3) tensors of equal shape, got {tuple(p.shape)} and {tuple(g.shape)}")
+        p, g = (p - p[..., root:root + 1, :]).contiguous(), (g - g[..., root:root + 1, :]).contiguous()
+    w = None if weights is None else _device_f32(weights, dev)
+    return native.point_error(p, g, weights=w, align=_POSITION_ALIGN[align])
+
+
+def procrustes_align(pred, gt, *, scale: bool = True, weights=None):
+    """Aligns ``pred (..., N, 3)`` to ``gt`` by the least-squares similarity (``scale``) or rigid transform:
+    ``(aligned, s, R, t)`` with ``aligned = s R x + t`` formed in torch from the kernel's transform, ``s (...)``,
+    ``R (..., 3, 3)`` a proper rotation and ``t (..., 3)``, all on the device."""
+    dev = _point_device(pred, None)
+    p, g = _device_f32(pred, dev), _device_f32(gt, dev)
+    w = None if weights is None else _device_f32(weights, dev)
+    _, tf = native.point_error(p, g, weights=w, align="similarity" if scale else "rigid", transform=True)
+    s, R, t = tf[..., 0], tf[..., 1:10].reshape(tf.shape[:-1] + (3, 3)), tf[..., 10:13]
+    aligned = s[..., None, None] * (p @ R.transpose(-1, -2)) + t[..., None, :]
+    return aligned, s, R, t
+
+
+def evaluate_position_pair(pred_points, gt_points, *, align: str, weights=None, device=None) -> Tuple[float, float, int]:
+    """Mean positional error of predicted vs ground-truth points ``(T, N, 3)``: ``(mean, sum, count)`` over the common frames
+    and the common points, frames whose weights sum to zero left out; the sum is taken in float64 on the device.  ``align`` as
+    ``compute_position_error``; ``weights (N,)`` or ``(T, N)``."""
+    n = min(gt_points.shape[0], pred_points.shape[0])
+    k = min(gt_points.shape[1], pred_points.shape[1])
+    dev = native.require_device(device)
+    pred = _device_f32(pred_points, dev)[:n, :k].contiguous()
+    gt = _device_f32(gt_points, dev)[:n, :k].contiguous()
+    w = None
+    if weights is not None:
+        w = _device_f32(weights, dev)
+        w = (w[:n, :k] if w.dim() == 2 else w[:k]).contiguous()
+    err = compute_position_error(pred, gt, align=align, weights=w, device=dev)
+    if w is not None:
+        err = err[w.double().sum(-1) > 0] if w.dim() == 2 else (err if float(w.double().sum()) > 0 else err[:0])
+    total = float(err.double().sum())
+    count = int(err.numel())
+    return (total / count if count else float("nan")), total, count
 
 
 def save_prediction_pose(pred_pose: np.ndarray, src_path: Path, dataset_root: Path, save_root: Path) -> None:

@@ -99,6 +99,7 @@ _PROTOTYPES = (
     ("k2b_lbs_backward", C.c_int, (_vp, _i32) + (_vp,) * 10 + _STREAM),
     ("k2b_debug_lbfgs_state_layout", C.c_int, (_i32, _i32, _i32) + (C.POINTER(_i64),) * 3 + (C.POINTER(_i32),) * 2),
     ("k2b_debug_lbfgs_step", C.c_int, (_i32, _i32, _i32) + (_vp,) * 6 + (_i32, _i32, _f64, _f64, _f64, _vp, _i64, _i32, _i32) + _STREAM),
+    ("k2b_point_error", C.c_int, (_i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp) + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -602,6 +603,38 @@ def angular_error_deg(pred_rotvec: torch.Tensor, gt_rotvec: torch.Tensor) -> tor
     _launch("k2b_angular_error_deg", dev, n, _dev(pred_rotvec, "pred_rotvec", dev), _dev(gt_rotvec, "gt_rotvec", dev),
             _ptr(out) if n else None)
     return out
+
+
+POINT_ALIGN_MODES = {"none": 0, "translation": 1, "rigid": 2, "similarity": 3}
+
+
+def point_error(pred: torch.Tensor, gt: torch.Tensor, *, weights: Optional[torch.Tensor] = None, align: str = "none",
+                per_point: bool = False, transform: bool = False):
+    """Weighted mean distance between two point sets per frame after an alignment, (..., N, 3) x (..., N, 3) -> (...)
+    (``k2b_point_error``; launched on the current stream of the tensors' device).  ``align``: ``"none"``, ``"translation"``,
+    ``"rigid"`` (Kabsch) or ``"similarity"`` (Umeyama, PA-MPJPE).  ``weights``: ``(N,)`` shared by all frames or ``(..., N)``
+    per frame, non-negative.  With ``per_point`` / ``transform`` the result is a tuple ``(err, [distances (..., N)],
+    [transforms (..., 13): s, R row-major, t])``."""
+    dev = require_device(pred.device if isinstance(pred, torch.Tensor) else None)
+    if align not in POINT_ALIGN_MODES:
+        raise ValueError(f"align must be one of {sorted(POINT_ALIGN_MODES)}, got {align!r}")
+    if tuple(pred.shape) != tuple(gt.shape) or pred.dim() < 2 or pred.shape[-1] != 3 or pred.shape[-2] < 1:
+        raise ValueError(f"expected two (...,N,3) tensors of equal shape with N >= 1, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    lead, N = tuple(pred.shape[:-2]), int(pred.shape[-2])
+    B = int(np.prod(lead, dtype=np.int64))
+    per_frame = 0
+    if weights is not None:
+        if tuple(weights.shape) == lead + (N,) and lead:
+            per_frame = 1
+        elif tuple(weights.shape) != (N,):
+            raise ValueError(f"weights has shape {tuple(weights.shape)}, expected {(N,)} or {lead + (N,)}")
+    err = torch.empty(lead, dtype=torch.float32, device=dev)
+    dist = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if per_point else None
+    tf = torch.empty(lead + (13,), dtype=torch.float32, device=dev) if transform else None
+    _launch("k2b_point_error", dev, B, N, _dev(pred, "pred", dev), _dev(gt, "gt", dev), _dev(weights, "weights", dev), per_frame,
+            POINT_ALIGN_MODES[align], _ptr(err) if B else None, _ptr(dist) if B else None, _ptr(tf) if B else None)
+    extra = tuple(t for t in (dist, tf) if t is not None)
+    return (err,) + extra if extra else err
 
 
 def _term_call(name, model: NativeModel, idx: np.ndarray, targets, conf, conf_shape, flags, sigma, joint_loss_weight, *params):
