@@ -25,7 +25,20 @@
  *     stream on the FIRST use of a selection per model (its vertex table is gathered and cached);
  *   - buffers are caller-owned; inputs are never written; handles may be shared by
  *     threads as long as concurrent calls use different streams AND different
- *     workspaces (one workspace per handle: serialise calls on one handle).
+ *     workspaces (one workspace per handle: serialise calls on one handle);
+ *   - frames are independent, non-finite inputs included: in every entry with a frame or
+ *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
+ *     k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
+ *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term) each output of a frame (in the chain
+ *     entries and the shape pass: of a sequence; inside a chain a frame also never depends on
+ *     a LATER frame) depends only on that frame's own inputs, bit for bit, even when another
+ *     frame's inputs are NaN or +-Inf (a missing keypoint written as NaN, say).  A frame whose
+ *     loss depends on a non-finite input reports a non-finite loss_out; its fitted parameters
+ *     are then unspecified (under L-BFGS the optimiser stops at its finite start), and so are
+ *     the frames behind it in the same sequence of an L-BFGS chain, which start from them; in
+ *     an Adam chain those frames report a non-finite loss too.  The stand-alone terms, k2b_lbs and k2b_lbs_backward return
+ *     non-finite values wherever float64 arithmetic on the same frame does, and possibly in
+ *     more elements of that same frame.  (tests/test_gpu_isolation.py)
  */
 #ifndef K2B_H
 #define K2B_H

@@ -15,6 +15,9 @@ Conditions on the inputs (asserted, so that a badly chosen case cannot loosen it
 gradient by more than an eighth of 2e-5 (ROUNDING_LIMIT below).  ``tests/test_fit_gradient_conditions.py`` checks both for all
 cases without a GPU.
 
+Root rotations of several turns (``turn_case``, TURNS = 6.5 .. 5000 rad) have a gate of their own, ``turn_gate``: the group gate per
+frame, widened by what two ulp of the float32 angle do to the float64 gradient.
+
 Groups: global_orient, body_pose, betas, transl; SMPL-H and SMPL-X split the pose into body | (face) | hands and SMPL-X the shape
 coefficients into betas | expression."""
 import copy
@@ -43,6 +46,12 @@ TRANSL_SCALE, TARGET_OFFSET = 0.2, 0.12
 MODEL_SEED = 3
 SMPLX_BETAS = {20: 10, 32: 22}                    # shape coefficients -> betas (the rest: 10 expression coefficients)
 LADDER = (0.0, 1e-6, 1e-3, 1.0, 2.0, 3.0, 3.1415, 3.3)
+# Rotation vectors of several turns (legal input; optimisers produce them), on the root only: it is outside the pose prior, so
+# every group keeps the scale of the joint term.  999 / 1001 straddle the branch of ``sincos_small`` (csrc/k2b_device.h) that hands
+# angles above 1e3 rad to the library functions.  ``turn_case``, ``turn_gate``.
+TURNS = (6.5, 20.0, 100.0, 999.0, 1001.0, 5000.0)
+TURN_SHARP = 20.0          # up to this angle a turned frame is held as sharply as every other frame
+TURN_ULPS = 2.0            # a float32 kernel forms the angle with a sum of squares and a square root: two roundings
 GMOF_SIGMA = 0.05
 GMOF_RESIDUALS = (0.01, 0.03, 0.05, 0.1, 0.3, 1.0)       # metres: below, at and far above sigma
 CONF_PATTERN = (0.0, 0.5, 1.0, 2.5, 1.5)
@@ -299,6 +308,18 @@ def conf_case(kind: str, per_frame: bool, removed: bool = False) -> Case:
                    j3d=np.ascontiguousarray(j3d[:, keep]), conf=np.ascontiguousarray(conf[..., keep]))
 
 
+@functools.lru_cache(maxsize=None)
+def turn_case(kind: str) -> Case:
+    """Frame f: the root turned by TURNS[f] rad about a seeded axis, everything else as ``base``."""
+    n = len(TURNS)
+    b = base(kind, B=n, seed=37)
+    axes = synthetic.normalish(81, (n, 3), 37)
+    axes = axes / np.sqrt((axes * axes).sum(axis=1, keepdims=True))
+    go = (axes * np.asarray(TURNS)[:, None]).astype(np.float32)
+    j3d = (joints64(kind, go, b.pose, b.shape, b.tr) + TARGET_OFFSET * synthetic.normalish(74, (n, layout(kind).J, 3), 37)).astype(np.float32)
+    return replace(b, name=f"{kind}/turns", j3d=j3d, go=go)
+
+
 def member_case(kind: str, mask: int, freeze: int) -> Case:
     b = base(kind, B=3, seed=23)
     return replace(b, name=f"{kind}/mask{mask}{'/frozen' if freeze else ''}", mask=mask, freeze=freeze)
@@ -424,6 +445,69 @@ def reference(case: Case) -> Reference:
         assert v <= E32_LIMIT, f"{case.name}: float32 autograd is off by {v:.2e} in {k}: the case is badly conditioned (limit {E32_LIMIT:.0e})"
     assert r.e32_loss <= E32_LIMIT, (case.name, r.e32_loss)
     return r
+
+
+# ---- several turns -----------------------------------------------------------------------------------------------------------
+def turn_rescaled(go: np.ndarray, sign: float) -> np.ndarray:
+    """The root vectors in float64, rescaled so that every angle moves by `sign` * TURN_ULPS ulp of the float32 angle."""
+    go = np.asarray(go, dtype=np.float64)
+    angle = np.sqrt((go * go).sum(axis=1))
+    return go * ((angle + sign * TURN_ULPS * np.spacing(angle.astype(np.float32)).astype(np.float64)) / angle)[:, None]
+
+
+@dataclass(frozen=True, eq=False)
+class TurnReference:
+    loss64: np.ndarray
+    g64: np.ndarray
+    e32: dict               # group -> [B]: the float32 oracle's error per frame
+    e32_loss: np.ndarray    # [B]
+    widen: dict             # group -> [B]: d_f, what TURN_ULPS ulp of the float32 angle do to the float64 gradient, either way
+    widen_loss: np.ndarray  # [B]
+
+
+@functools.lru_cache(maxsize=None)
+def turn_reference(kind: str) -> TurnReference:
+    """From the oracle alone.  Conditions, asserted: up to TURN_SHARP rad the float32 oracle stays within E32_LIMIT per frame
+    (``reference``'s condition), and one float32 rounding of the targets moves no group by more than ROUNDING_LIMIT.  Unlike
+    the positions of the LBS forward, where two ulp of a 20 rad angle stay below the gate, the gradient's d_f does not: a group's
+    gradient is a sum of partly cancelling torques while a change of the root angle moves every joint coherently, so two ulp of
+    6.5 rad (1e-6 rad) already move the root group by 1e-4 of its largest entry and the others by up to 4e-5 (20 rad: 6e-4
+    and 7e-5; the float32 oracle itself is off by up to 1e-4 there).  d_f is therefore not capped; it comes from float64 alone."""
+    case, lay = turn_case(kind), layout(kind)
+    loss64, g64 = oracle_eval(case, True)
+    loss32, g32 = oracle_eval(case, False)
+    rel = lambda l: np.abs(l - loss64) / np.abs(loss64)
+    moved = [oracle_eval(replace(case, go=turn_rescaled(case.go, sign)), True) for sign in (1.0, -1.0)]
+    widen = {k: np.maximum(*(group_errors(g, g64, lay)[k] for _, g in moved)) for k, _, _ in lay.groups}
+    ref = TurnReference(loss64, g64, group_errors(g32, g64, lay), rel(loss32), widen, np.maximum(*(rel(l) for l, _ in moved)))
+    sharp = np.asarray(TURNS) <= TURN_SHARP
+    for k, v in rounding_sensitivity(case, g64).items():
+        assert v <= ROUNDING_LIMIT, f"{case.name}: one float32 rounding of the targets moves {k} by {v:.2e}"
+    for k in ref.e32:
+        assert (ref.e32[k][sharp] <= E32_LIMIT).all(), (case.name, k, ref.e32[k])
+    assert (ref.e32_loss[sharp] <= E32_LIMIT).all(), (case.name, ref.e32_loss)
+    return ref
+
+
+def turn_gate(kind: str, loss: np.ndarray, grad: np.ndarray, what: str = ""):
+    """The group gate of ``gate`` per frame, widened by d_f: ``max|g - g64| <= (max(2e-5, 4 e32_kf) + d_kf) max|g64|`` over group k of
+    frame f, the loss within ``max(2e-6, 4 e32_loss_f) + d_loss_f`` of itself; e32 per frame, so that the large angles do not loosen
+    the small ones.  Up to TURN_SHARP rad the gate stays within a few 1e-4 of the group's largest entry (``turn_reference``);
+    above it d_f dominates - the float32 angle itself is uncertain by an ulp or two, which at 5000 rad is a milliradian - and
+    the test catches a wrong quadrant, a broken reduction or a broken library branch there, not an ulp.
+    Prints the measured figures per angle first."""
+    case, lay, ref = turn_case(kind), layout(kind), turn_reference(kind)
+    err = group_errors(grad, ref.g64, lay)
+    tol = {k: np.maximum(GRAD_GATE, ORDER_FACTOR * ref.e32[k]) + ref.widen[k] for k in err}
+    e_loss = np.abs(loss - ref.loss64) / np.abs(ref.loss64)
+    tol_loss = np.maximum(LOSS_GATE, ORDER_FACTOR * ref.e32_loss) + ref.widen_loss
+    for f, a in enumerate(TURNS):
+        print(f"turn gate {lay.kernel} {case.name}{what} {a:g} rad: loss={e_loss[f]:.2e}/{ref.e32_loss[f]:.2e}/{tol_loss[f]:.2e} " +
+              " ".join(f"{k}={v[f]:.2e}/{ref.e32[k][f]:.2e}/{tol[k][f]:.2e}" for k, v in err.items()) + "  (error/e32/tol)")
+    assert np.isfinite(grad).all() and np.isfinite(loss).all(), case.name
+    for k, v in err.items():
+        assert (v <= tol[k]).all(), f"{case.name}{what}: {k} off by {v} of the group's largest entry per frame, gate {tol[k]}"
+    assert (e_loss <= tol_loss).all(), f"{case.name}{what}: loss off by {e_loss}, gate {tol_loss}"
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------------

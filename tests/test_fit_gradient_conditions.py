@@ -46,6 +46,20 @@ def test_ladder_holds_every_angle_on_both_kernels():
         assert np.isclose(angles[0], F.LADDER[0]) and not full[1].any()
 
 
+@pytest.mark.parametrize("kind", F.BOTH)
+def test_turn_case_meets_its_conditions(kind):
+    """The root turned by 6.5 .. 5000 rad: up to 20 rad the float32 oracle stays within E32_LIMIT per frame (asserted by
+    ``turn_reference``, which also says why d_f is not capped by the gate here); above it d_f dominates."""
+    c = F.turn_case(kind)
+    np.testing.assert_allclose(np.linalg.norm(c.go.astype(np.float64), axis=1), F.TURNS, rtol=1e-6)
+    ref = F.turn_reference(kind)
+    for f, a in enumerate(F.TURNS):
+        print(f"{c.name} {a:g} rad: e32 loss {ref.e32_loss[f]:.2e} groups {max(v[f] for v in ref.e32.values()):.2e}; "
+              f"d_f loss {ref.widen_loss[f]:.2e} groups {max(v[f] for v in ref.widen.values()):.2e}")
+    assert np.isfinite(ref.g64).all() and all(np.isfinite(v).all() for v in ref.widen.values())
+    assert max(v[-1] for v in ref.widen.values()) > F.GRAD_GATE             # at 5000 rad the widening is what gates
+
+
 def test_gmof_case_spans_sigma_and_has_a_target_on_its_joint():
     for kind in F.BOTH:
         c = F.gmof_case(kind, "joint")

@@ -78,6 +78,21 @@ def test_rotation_angle_ladder(kind):
     _in_every_shape(F.ladder_case(kind))
 
 
+@pytest.mark.parametrize("kind", F.BOTH)
+def test_root_rotations_of_several_turns(kind):
+    """6.5 .. 5000 rad on the root (999 / 1001 straddle the branch of ``sincos_small`` to the library functions), one frame per
+    angle, in every launch shape.  Up to 20 rad the frames are held to the unchanged group gate; above it the gate is dominated
+    by what an ulp or two of the float32 angle do to the float64 gradient (``fit_gradient_common.turn_gate``), and the test
+    catches a wrong quadrant, a broken reduction or a broken library branch, not an ulp."""
+    case = F.turn_case(kind)
+    shapes = FUSED_SHAPES if F.layout(kind).kernel == "fused" else TREE_SHAPES
+    first = F.device_eval(case, shapes[0])
+    for s in shapes[1:]:
+        loss, grad = F.device_eval(case, s)
+        assert np.array_equal(loss, first[0]) and np.array_equal(grad, first[1]), f"{case.name}: shape {s} differs from shape {shapes[0]}"
+    F.turn_gate(kind, *first)
+
+
 # ---- 3. GMoF outside its quadratic range -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("term", ("joint", "all"))
 @pytest.mark.parametrize("kind", F.BOTH)

@@ -54,6 +54,23 @@ def test_forward_matches_the_float64_oracle(J, NB, regime):
     _check_forward(L.native_model(J, NB), J, NB, regime)
 
 
+@pytest.mark.parametrize("J, NB", L.TURN_LAYOUTS)
+def test_forward_with_rotations_of_several_turns(J, NB):
+    """Regime "turns": 6.5 .. 5000 rad on the root, on joint 3, and 999 / 1001 rad on two consecutive joints of a chain (the pair
+    straddles the branch of ``sincos_small`` to the library functions).  The gate of every frame is the unchanged one plus d_f,
+    what two ulp of the float32 angle do to the float64 result: up to 20 rad that is below the gate, so those frames are held as
+    sharply as every other; above it d_f dominates, and the test catches a wrong quadrant, a broken reduction or a broken library
+    branch there, not an ulp.  Prints the worst error per angle."""
+    ref = L.reference(J, NB, "turns")
+    L.check_inputs(ref, "turns")
+    m = L.native_model(J, NB)
+    j, v = _lbs(m, ref.params)
+    print(f"turns {J}/{NB} worst error / gate per angle: {L.turn_summary(ref, j, v)}")
+    L.forward_gate(ref, j, v)
+    j2, _ = _lbs(m, ref.params, want_vertices=False)
+    L.forward_gate(ref, j2, None, " joints only")
+
+
 # ---- 2. the tile kernel as twin of the stream kernels ---------------------------------------------------------------------------
 @pytest.mark.parametrize("J, NB", L.STREAM_LAYOUTS)
 def test_tile_twin_of_every_stream_layout(J, NB, monkeypatch):

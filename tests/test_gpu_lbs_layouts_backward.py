@@ -45,6 +45,16 @@ def test_backward_matches_float64_autograd(J, NB, which):
     C.gate(f"{J}/{NB} V={V} B={B} {which}", got, g64, g32)
 
 
+def test_backward_with_rotations_of_several_turns():
+    """The frames of the forward's "turns" regime (6.5 .. 5000 rad on the root, on joint 3, 999 / 1001 rad on a chain) through
+    ``k2b_lbs_backward``, per frame under ``lbs_layouts_common.turn_backward_gate``."""
+    J, NB = L.TURN_BACKWARD_LAYOUT
+    p, (gj, gv), _, _, _ = L.turn_backward_reference(J, NB)
+    out = L.native_model(J, NB).lbs_backward(*map(H.cuda, p), H.cuda(gj), H.cuda(gv))
+    torch.cuda.synchronize()
+    L.turn_backward_gate(J, NB, dict(zip(C.GROUPS, out)))
+
+
 @pytest.mark.parametrize("J, NB", L.VERTEX_TERM_LAYOUTS)
 def test_vertex_term_matches_float64_autograd(J, NB):
     """20 / 16: the ``<24, 16>`` instantiation with fewer joints than its capacity; 24 / 17 and 56 / 32: ``<64, 32>``."""

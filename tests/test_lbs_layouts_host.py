@@ -103,6 +103,55 @@ def test_forward_inputs_are_well_conditioned(J, NB, regime):
         assert np.isfinite(ref.scale).all() and (ref.tol >= L.FORWARD_GATE).all()
 
 
+def test_turn_frames_are_where_the_docstring_says():
+    assert L.TURNS == (6.5, 20.0, 100.0, 999.0, 1001.0, 5000.0) and set(L.TURN_LAYOUTS) <= set(L.LAYOUTS) and L.TURN_BACKWARD_LAYOUT in L.BACKWARD_LAYOUTS
+    for J, NB in L.TURN_LAYOUTS:
+        go, pose, shape, tr = L.params(J, NB, "turns")
+        benign = L.params(J, NB, "benign")
+        full = np.concatenate([go, pose], axis=1).reshape(L.FRAMES, J, 3).astype(np.float64)
+        same = np.concatenate([benign[0], benign[1]], axis=1).reshape(L.FRAMES, J, 3)
+        angle = np.sqrt((full * full).sum(axis=2))
+        frames = L.turn_frames()
+        assert sorted(frames) == list(range(4, L.TURN_FRAMES)) and L.TURN_FRAMES <= L.FRAMES
+        for f in range(L.FRAMES):
+            turned = dict(frames.get(f, ()))
+            for joint in range(J):
+                if joint in turned:
+                    np.testing.assert_allclose(angle[f, joint], turned[joint], rtol=1e-6)
+                else:
+                    assert np.array_equal(full[f, joint].astype(np.float32), same[f, joint])
+        assert np.array_equal(shape, benign[2]) and np.array_equal(tr, benign[3])
+        parents, _ = L.tree(J)
+        assert parents[L.TURN_CHAIN[1]] == L.TURN_CHAIN[0] and dict(frames[L.TURN_FRAMES - 1]) == {L.TURN_CHAIN[0]: 999.0, L.TURN_CHAIN[1]: 1001.0}
+        assert [frames[4 + i] for i in range(6)] == [((0, a),) for a in L.TURNS]
+        assert [frames[10 + i] for i in range(6)] == [((L.TURN_JOINT, a),) for a in L.TURNS]
+
+
+@pytest.mark.parametrize("J, NB", L.TURN_LAYOUTS)
+def test_turn_inputs_meet_their_conditions(J, NB):
+    """Up to 20 rad: e32 <= 1.25e-6 (the benign limit) and d_f at most the unchanged gate, so those frames are held as sharply as
+    every other frame; above it d_f dominates (the float32 oracle alone is off by micrometres at 100 rad and more beyond)."""
+    ref = L.reference(J, NB, "turns")
+    L.check_inputs(ref, "turns")
+    angle = L.turn_angle()
+    for a in sorted(set(angle[angle > 0])):
+        rows = angle == a
+        print(f"{ref.name} {a:g} rad: e32 {ref.e32[rows].max():.2e} d_f {ref.widen[rows].max():.2e} gate {ref.tol[rows].min():.2e}")
+    assert np.isfinite(ref.widen).all() and (ref.widen[angle == 0] == 0).all()
+    assert ref.widen[angle == 5000.0].max() > 10 * L.FORWARD_GATE               # there the widening is what gates
+
+
+def test_backward_turn_inputs_meet_their_conditions():
+    J, NB = L.TURN_BACKWARD_LAYOUT
+    p, _, g64, e32, widen = L.turn_backward_reference(J, NB)                    # (asserts the conditions up to 20 rad)
+    assert all(a.shape[0] == L.TURN_FRAMES and a.dtype == np.float32 for a in p)
+    angle = L.turn_angle(L.TURN_FRAMES)
+    for a in sorted(set(angle)):
+        rows = angle == a
+        print(f"backward turns {J}/{NB} {a:g} rad: e32 {e32[rows].max():.2e} d_f {max(v[rows].max() for v in widen.values()):.2e}")
+    assert all(np.isfinite(v.numpy()).all() for v in g64.values()) and all(np.isfinite(v).all() for v in widen.values())
+
+
 @pytest.mark.parametrize("J, NB, V", L.PRODUCT_CASES)
 def test_product_size_inputs_are_well_conditioned(J, NB, V):
     ref = L.reference(J, NB, "benign", V=V, B=3)
