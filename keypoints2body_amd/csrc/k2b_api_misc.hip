@@ -23,6 +23,29 @@ int64_t ikgat_num_weights(int J, int IN, int H, int L) {
     return h * IN + h + (int64_t)J * h + h * IN + h + (int64_t)L * (h * h + 5 * h) + h2 * h + 3 * h2 + 6 * h2 + 6;
 }
 
+// One skin pass of k2b_lbs (k2b_lbs_plan.h, LbsPass): the fields StreamArgs and TileArgs share, then each one's own, launched by
+// the model's route.
+template <class Args>
+Args skin_args(const k2b::PoseArgs& pa, const VertexSet& vs, const k2b::LbsPass& p, float* out, float* dump) {
+    Args a{};
+    a.xh = pa.xh; a.xl = pa.xl; a.a2 = pa.a2;
+    a.num_frames = pa.num_frames; a.num_out = vs.num; a.out = out; a.out_stride = p.stride; a.out_row0 = p.row0;
+    a.dump = dump;
+    a.joints_out = p.joint_copies ? pa.joints_out : nullptr; a.joints_stride = pa.num_out_joints; a.joints_row0 = pa.num_joints;
+    return a;
+}
+hipError_t launch_skin(const k2b_model* m, const k2b::PoseArgs& pa, const VertexSet& vs, const k2b::LbsPass& p, float* out, hipStream_t stream) {
+    if (m->lbs.streams()) {
+        k2b::StreamArgs sa = skin_args<k2b::StreamArgs>(pa, vs, p, out, m->dump.get());
+        sa.pd = vs.spd.get(); sa.w = vs.sw.get(); sa.f32_tiles = pa.frames_padded / 32; sa.nv16 = vs.nv16;
+        return k2b::launch_skin_stream(m->lbs.route, sa, device_cus(), stream);
+    }
+    k2b::TileArgs ta = skin_args<k2b::TileArgs>(pa, vs, p, out, m->dump.get());
+    ta.pdh = vs.pdh.get(); ta.pdl = vs.pdl.get(); ta.w2 = vs.w2.get();
+    ta.groups_a = m->lbs.groups_a; ta.k_steps_x = m->lbs.k_steps_x; ta.f_tiles = pa.frames_padded / 32; ta.v_tiles = vs.v_tiles;
+    return k2b::launch_skin_tiles(ta, device_cus(), stream);
+}
+
 }  // namespace
 
 namespace k2b {
@@ -93,58 +116,38 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
     if (B == 0) return K2B_OK;
     if (!go || !bp || !be) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: NULL parameter buffer");
     if (!joints_out && !vertices_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs: no output requested");
+    if (m->lbs.route == k2b::LbsRoute::unsupported)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs: %d joints; the vertex kernel is built for 17-24 (SMPL) and 49-56 (SMPL-H / SMPL-X) joints", m->J);
     hipStream_t stream = (hipStream_t)stream_v;
-    const int bpad = k2b::lbs_frames_padded(B);
+    const int L = m->lmk.L, bpad = k2b::lbs_frames_padded(B);
+    const k2b::LbsForwardPlan plan = k2b::lbs_forward_plan(joints_out != nullptr, vertices_out != nullptr, m->J, m->V, m->E, L, m->joints_in_mesh);
     {
         std::lock_guard<std::mutex> lk(m->mu);
         if (const int rc = reserve_lbs_workspace(m, bpad); rc != K2B_OK) return rc;
     }
     k2b::PoseArgs pa{};
     pa.j_basis_lane = m->j_basis_lane.get(); pa.parents = m->parents.get();
-    const int L = m->lmk.L, ostride = m->J + m->E + L;                  // rows of joints_out: J kinematic, E extra vertices, L landmarks
-    pa.num_joints = m->J; pa.num_betas = m->NB; pa.num_out_joints = ostride;
-    pa.num_frames = B; pa.frames_padded = bpad; pa.k_steps_x = m->k_steps_x;
+    pa.num_joints = m->J; pa.num_betas = m->NB; pa.num_out_joints = m->J + m->E + L;   // rows of joints_out: J kinematic, E extra vertices, L landmarks
+    pa.num_frames = B; pa.frames_padded = bpad; pa.k_steps_x = m->lbs.k_steps_x;
     pa.go = go; pa.bp = bp; pa.be = be; pa.tr = tr;
-    if (m->groups_a != 3 && m->groups_a != 7)
-        return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs: %d joints; the vertex kernel is built for 17-24 (SMPL) and 49-56 (SMPL-H / SMPL-X) joints", m->J);
     pa.xh = m->wsXh.get(); pa.xl = m->wsXl.get(); pa.a2 = m->wsA2.get(); pa.joints_out = joints_out;
-    pa.a2_stream_order = m->streams() ? 1 : 0;
-    HIP_TRY(k2b::launch_pose_setup(pa, stream));
-    auto skin = [&](const VertexSet& vs, float* out, int stride, int row0, float* joint_copies) -> hipError_t {
-        if (m->streams()) {
-            k2b::StreamArgs sa{};
-            sa.xh = pa.xh; sa.xl = pa.xl; sa.a2 = pa.a2; sa.pd = vs.spd.get(); sa.w = vs.sw.get();
-            sa.f32_tiles = bpad / 32; sa.nv16 = vs.nv16;
-            sa.num_frames = B; sa.num_out = vs.num; sa.out = out; sa.out_stride = stride; sa.out_row0 = row0;
-            sa.dump = m->dump.get();
-            sa.joints_out = joint_copies; sa.joints_stride = ostride; sa.joints_row0 = m->J;
-            return m->stream ? k2b::launch_skin_stream(sa, device_cus(), stream)
-                 : m->stream_x ? k2b::launch_skin_stream_x(sa, device_cus(), stream) : k2b::launch_skin_stream_xw(sa, device_cus(), stream);
+    pa.a2_stream_order = m->lbs.streams() ? 1 : 0;
+    const VertexSet* const sets[] = {&m->mesh, &m->extra, &m->lmk.verts};                 // by LbsPass::Set
+    float* const bufs[] = {vertices_out, joints_out, m->lmk.ws.get()};                    // by LbsPass::Buf
+    for (int i = 0; i < plan.num_passes; ++i) {
+        const k2b::LbsPass& p = plan.pass[i];
+        float* const buf = bufs[p.buf];
+        switch (p.kind) {
+            case k2b::LbsPass::pose_setup: HIP_TRY(k2b::launch_pose_setup(pa, m->lbs.pose_capacity, stream)); break;
+            case k2b::LbsPass::skin: HIP_TRY(launch_skin(m, pa, *sets[p.set], p, buf, stream)); break;
+            case k2b::LbsPass::gather:       // only when an output joint's vertex cannot ride in the W image
+                HIP_TRY(k2b::launch_gather_joints(buf, m->extra_ids.get(), joints_out, B, p.stride, m->J, m->E, pa.num_out_joints, stream));
+                break;
+            case k2b::LbsPass::landmarks:    // a stream-ordered pass over this call's vertices, or over the 3L skinned alone (ids: their sequence)
+                HIP_TRY(k2b::launch_landmarks(buf, p.stride, (p.set == k2b::LbsPass::mesh ? m->lmk.ids : m->lmk.seq).get(), m->lmk.w.get(), joints_out,
+                                              pa.num_out_joints, m->J + m->E, B, L, stream));
+                break;
         }
-        k2b::TileArgs ta{};
-        ta.xh = pa.xh; ta.xl = pa.xl; ta.a2 = pa.a2; ta.pdh = vs.pdh.get(); ta.pdl = vs.pdl.get(); ta.w2 = vs.w2.get();
-        ta.groups_a = m->groups_a; ta.k_steps_x = m->k_steps_x; ta.f_tiles = bpad / 32; ta.v_tiles = vs.v_tiles;
-        ta.num_frames = B; ta.num_out = vs.num; ta.out = out; ta.out_stride = stride; ta.out_row0 = row0;
-        ta.dump = m->dump.get();
-        ta.joints_out = joint_copies; ta.joints_stride = ostride; ta.joints_row0 = m->J;
-        return k2b::launch_skin_tiles(ta, device_cus(), stream);
-    };
-    if (vertices_out) {
-        // the mesh launch also writes the vertex-selected joints (their vertices are tagged in the W image)
-        const bool copies = joints_out && m->E > 0 && m->joints_in_mesh;
-        HIP_TRY(skin(m->mesh, vertices_out, m->V, 0, copies ? joints_out : nullptr));
-        if (joints_out && m->E > 0 && !copies)
-            HIP_TRY(k2b::launch_gather_joints(vertices_out, m->extra_ids.get(), joints_out, B, m->V, m->J, m->E, ostride, stream));
-        // landmarks: a stream-ordered pass over this call's vertices
-        if (joints_out && L > 0)
-            HIP_TRY(k2b::launch_landmarks(vertices_out, m->V, m->lmk.ids.get(), m->lmk.w.get(), joints_out, ostride, m->J + m->E, B, L, stream));
-        return K2B_OK;
-    }
-    if (joints_out && m->E > 0) HIP_TRY(skin(m->extra, joints_out, ostride, m->J, nullptr));
-    if (joints_out && L > 0) {
-        // landmarks without the mesh: the 3L vertices skinned alone into the model's workspace (sized above), then combined
-        HIP_TRY(skin(m->lmk.verts, m->lmk.ws.get(), 3 * L, 0, nullptr));
-        HIP_TRY(k2b::launch_landmarks(m->lmk.ws.get(), 3 * L, m->lmk.seq.get(), m->lmk.w.get(), joints_out, ostride, m->J + m->E, B, L, stream));
     }
     return K2B_OK;
 }

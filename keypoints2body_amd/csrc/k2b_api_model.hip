@@ -20,7 +20,7 @@ namespace {
 // route (k2b_model_tables.h, vertex_set_images) go up; a stream model has none of the tile kernel's (SMPL-X: 64 MB less per GPU)
 int build_vertex_set(k2b_model* m, VertexSet& vs, const std::vector<int>& ids, const std::vector<int>& tag,
                      const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights, int V) {
-    const k2b::tables::VertexSetShape shape{m->J, m->NB, m->P, m->k_steps_x, m->stream ? 3 : m->streams() ? 5 : 0};
+    const k2b::tables::VertexSetShape shape{m->J, m->NB, m->P, m->lbs.k_steps_x, m->lbs.w_frags};
     const k2b::tables::VertexSetImages im = k2b::tables::vertex_set_images(shape, ids, tag, v_template, shapedirs, posedirs, lbs_weights, V);
     vs.num = (int)ids.size();
     vs.v_tiles = im.v_tiles;
@@ -69,19 +69,11 @@ int set_landmarks_locked(k2b_model* m, int32_t L, const int32_t* vertex_ids, con
 // ---- the steps of k2b_model_create, in its order -------------------------------------------------------------------------------
 // LBS operands: the route (stream kernels or the tile kernel), then the B side of the two GEMMs for the mesh and the extra joints
 int create_lbs_operands(k2b_model* m, const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights) {
-    const int V = m->V, J = m->J, NB = m->NB, E = m->E;
-    int KX = ((m->P + NB + 2 + 31) / 32) * 2;      // even: the kernels stage 32-deep slices
-    m->groups_a = k2b::tile_groups_a(J);
-    // 49-56 joints with fewer features than SMPL-X (SMPL-H: 477 -> 15 k-steps): one all-zero k-step more buys the stream kernel
-    if (K2B_LBS_STREAM && m->groups_a == 7 && KX < 2 * k2b::kStreamXKSteps) KX = 2 * k2b::kStreamXKSteps;
-    m->k_steps_x = KX;
+    const int V = m->V, E = m->E;
     // development switch K2B_LBS_TILE (non-zero): this model is skinned by the tile kernel whatever the stream kernels would
     // take - their run-time twin.  Per model, fixed here; nothing else reads it.
     const char* tile_env = getenv("K2B_LBS_TILE");
-    const bool streams = K2B_LBS_STREAM && !(tile_env && atoi(tile_env) != 0);
-    m->stream = streams && m->groups_a == 3 && KX == 2 * k2b::kStreamKSteps;
-    m->stream_x = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXKSteps;
-    m->stream_xw = streams && m->groups_a == 7 && KX == 2 * k2b::kStreamXWKSteps;      // 513-544 features: 55 joints from 25 shape coefficients on, 56 from 16
+    m->lbs = k2b::lbs_route(m->J, m->NB, K2B_LBS_STREAM != 0, tile_env && atoi(tile_env) != 0);
     HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
     std::vector<int> all(V), tag(V, 0);
     std::iota(all.begin(), all.end(), 0);
@@ -270,19 +262,19 @@ int surface_table(k2b_model* m, const std::vector<int>& sel, const std::vector<i
 
 // grow-only per-model workspace of the per-frame LBS operands (caller holds m->mu)
 int reserve_lbs_workspace(k2b_model* m, int bpad) {
+    const k2b::LbsWorkspace n = k2b::lbs_workspace(m->lbs, bpad, m->lmk.L);
     if (m->lmk.L > 0 && bpad > m->lmk.ws_bpad) {             // the landmark vertices of joints-only calls
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(m->lmk.ws.reset());
         m->lmk.ws_bpad = 0;
-        HIP_TRY(m->lmk.ws.alloc((size_t)bpad * 3 * m->lmk.L * 3));
+        HIP_TRY(m->lmk.ws.alloc(n.landmark_floats));
         m->lmk.ws_bpad = bpad;
     }
     if (bpad <= m->ws_bpad) return K2B_OK;
     HIP_TRY(hipDeviceSynchronize());
     for (auto* w : {&m->wsXh, &m->wsXl, &m->wsA2}) HIP_TRY(w->reset());
     m->ws_bpad = 0;
-    const size_t nx = (size_t)m->k_steps_x * bpad * 16;
-    const size_t na2 = (size_t)(bpad / 16) * 12 * k2b::tile_ngp(m->groups_a) * 128;
+    const size_t nx = n.x_halfs, na2 = n.a2_halfs;
     HIP_TRY(m->wsA2.alloc(na2));
     HIP_TRY(hipMemset(m->wsA2.get(), 0, na2 * sizeof(k2b::k2b_half)));    // PAD / ZERO groups and padding frames stay zero
     HIP_TRY(m->wsXh.alloc(nx));

@@ -120,19 +120,14 @@ struct __attribute__((visibility("hidden"))) k2b_model {
     k2b::Tree kin;                                           // the kinematic tree (k2b_tree.h): DFS order, depth of every joint
     VertexSet mesh, extra;                                   // the whole mesh and the E extra-joint vertices
     bool joints_in_mesh = false;                             // every extra joint's vertex is tagged in mesh.w2 (no gather launch)
-    bool stream = false;                                     // 17-24 joints and 7 pose k-steps: the stream kernel skins this model
-    bool stream_x = false;                                   // 49-56 joints and 16 pose k-steps (SMPL-X): k2b_lbs_stream_x_kernel
-    bool stream_xw = false;                                  // 49-56 joints and 17 pose k-steps (513-544 features: 55 joints with 25-32 shape coefficients, 56 with 16-32): k2b_lbs_stream_xw_kernel
-    bool streams() const { return stream || stream_x || stream_xw; }   // one of the stream kernels (none: the tile kernel)
+    k2b::LbsRouteRecord lbs;                                 // which kernel skins this model, GA, k-steps, W fragments, pose capacity (k2b_lbs_plan.h, lbs_route)
     // tables of the tree fit kernel (any J <= 64), lane order = DFS pre-order (lane of joint j: kin.pos[j])
     DevBuf<float> tt_dt, tt_dd;
     DevBuf<int> tt_anc;
     std::vector<int> h_tt_tab;                               // host: the [64][8] lane table with empty prior columns
     std::map<int, DevBuf<int>> tt_tabs;                      // the lane table per prior width, built on first use, never written after its upload (guarded by mu)
-    int groups_a = 0;                                        // GA = ceil(J / 8)
     DevBuf<k2b::k2b_half> wsA2;                              // per-frame A operand of the tile kernel
     DevBuf<float> dump;                                      // 64 x 3 floats: store target of lanes outside the batch
-    int k_steps_x = 0;
     // LBS per-frame operand workspace (grow-only)
     DevBuf<k2b::k2b_half> wsXh, wsXl;
     int ws_bpad = 0;

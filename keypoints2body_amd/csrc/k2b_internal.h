@@ -8,6 +8,7 @@
 #include "k2b_device.h"
 #include "k2b_launch_plan.h"   // (and k2b_layout.h: kFitJoints, kPrior*, the fit kernel's LDS layout)
 #include "k2b_lbfgs_plan.h"    // kLbfgsMaxHistory, lbfgs_state_bytes / lbfgs_state_rows, the schedule and the workspace maps
+#include "k2b_lbs_plan.h"      // LbsRoute, the stream kernels' k-step counts, lbs_frames_padded, the sizes and passes of the LBS pair
 
 namespace k2b {
 
@@ -155,8 +156,7 @@ struct PoseArgs {
     float* joints_out;         // [B][num_out_joints][3] (first J rows written) or null
     int xcd_frames;            // set by the launcher: 0 = workgroup b takes frame b; else XCD label b % 8 takes the frames [x, x + 1) * xcd_frames
 };
-hipError_t launch_pose_setup(const PoseArgs& a, hipStream_t stream);
-int lbs_frames_padded(int num_frames);
+hipError_t launch_pose_setup(const PoseArgs& a, int pose_capacity, hipStream_t stream);   // (LbsRouteRecord::pose_capacity)
 
 // ---- tile kernel (k2b_lbs_tile_kernel): 128 frames x 128 vertices per workgroup, persistent ------------------
 // Operands of the transform GEMM T = A . W^T in k-GROUPS of 8 joints over 16-row tiles (256 B = [16 rows][8 halfs]):
@@ -190,17 +190,17 @@ hipError_t launch_skin_tiles(const TileArgs& a, int num_cus, hipStream_t stream)
 // ---- stream kernels (k2b_lbs_stream.hip): the same tile, Pd global -> registers -------------------------------------------------
 // One kernel body (stream_body<S>) behind three entry points, one description S each; the descriptions hold what differs (pose
 // k-steps, X resident or in a ring, fragment counts and products, the counted-wait tables) and live in k2b_lbs_stream.hip.
-//   k2b_lbs_stream_kernel     17-24 joints, 7 pose k-steps (SMPL)                                      launch_skin_stream
-//   k2b_lbs_stream_x_kernel   49-56 joints, 16 pose k-steps (<= 512 features: SMPL-H, SMPL-X up to 24 shape coefficients) launch_skin_stream_x
-//   k2b_lbs_stream_xw_kernel  49-56 joints, 17 pose k-steps (513-544 features: SMPL-X with 25-32, 56 joints with 16-32)   launch_skin_stream_xw
-// Every other model with 17-24 or 49-56 joints, and any model created under K2B_LBS_TILE=1, runs the tile kernel.
+//   k2b_lbs_stream_kernel     17-24 joints, 7 pose k-steps (SMPL)                                      LbsRoute::stream
+//   k2b_lbs_stream_x_kernel   49-56 joints, 16 pose k-steps (<= 512 features: SMPL-H, SMPL-X up to 24 shape coefficients) LbsRoute::stream_x
+//   k2b_lbs_stream_xw_kernel  49-56 joints, 17 pose k-steps (513-544 features: SMPL-X with 25-32, 56 joints with 16-32)   LbsRoute::stream_xw
+// Every other model with 17-24 or 49-56 joints, and any model created under K2B_LBS_TILE=1, runs the tile kernel (the rule and
+// the k-step counts kStream*KSteps: k2b_lbs_plan.h, lbs_route).
 // Operands (1 KiB pieces = 64 lanes x 8 halfs in v_mfma_f32_16x16x32_f16 operand order: lane = row + 16 k-group), SMPL:
 //   X   as for the tile kernel
 //   A   [16-frame tile][entry 12][fragment 2]: fragment 0 = k-groups hi_0 hi_1 hi_2 PAD, fragment 1 = lo_0 lo_1 lo_2 ZERO
 //       (the pose set-up writes this group order with PoseArgs::a2_stream_order)
 //   Pd  [k-step 7][16-vertex tile][coordinate 3][hi | lo]
 //   W   [16-vertex tile][3]: [hi | ONES], [hi | tag], [lo | 0]   (tag: 1 + output joint of the vertex, first half of the group)
-constexpr int kStreamKSteps = 7;
 struct StreamArgs {
     const k2b_half *xh, *xl, *a2, *pd, *w;
     int f32_tiles;               // 32-frame tiles (frames padded / 32)
@@ -213,16 +213,12 @@ struct StreamArgs {
     int joints_stride, joints_row0;
     int num_wgs;
 };
-hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stream);
+hipError_t launch_skin_stream(LbsRoute route, const StreamArgs& a, int num_cus, hipStream_t stream);   // one of the three stream routes
 // SMPL-X: the same operands with
 //   A   [16-frame tile][entry 12][fragment 4]: hi_0-3 | hi_4-6 PAD | lo_0-3 | lo_4-6 ZERO   (a2_stream_order with GA = 7)
 //   Pd  [k-step 16][16-vertex tile][coordinate 3][hi | lo]
 //   W   [16-vertex tile][5]: hi_0-3, [hi_4-6 | ONES], lo_0-3, [lo_4-6 | 0], [hi_4-6 | tag]
-constexpr int kStreamXKSteps = 16;
-hipError_t launch_skin_stream_x(const StreamArgs& a, int num_cus, hipStream_t stream);
 // 49-56 joints with 513-544 features (SMPL-X with 25-32 shape coefficients; 56 joints from 16 on): SMPL-X's operands, Pd [k-step 17]
-constexpr int kStreamXWKSteps = 17;
-hipError_t launch_skin_stream_xw(const StreamArgs& a, int num_cus, hipStream_t stream);
 hipError_t launch_gather_joints(const float* verts, const int* ids, float* joints, int num_frames, int V, int J, int E,
                                 int out_stride, hipStream_t stream);   // out_stride: J + E (+ L: landmark rows behind)
 

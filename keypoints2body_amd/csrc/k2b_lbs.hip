@@ -58,9 +58,7 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
 // ---------------------------------------------------------------------------------------------
 // Pose set-up: one 64-lane workgroup per frame, lane j = joint j.
 // ---------------------------------------------------------------------------------------------
-constexpr int kMaxXSteps = 34;       // 16-deep k-steps of the feature vector this kernel can stage (SMPL: 14, SMPL-X: 32, or 34 with 25-32
-                                     // shape coefficients: 9 x 54 + 32 + 2 = 520 features)
-
+// (kMaxXSteps, the 16-deep k-steps of the feature vector this kernel can stage: k2b_lbs_plan.h)
 // NBC = capacity of the shape loop (10 / 16 / 20 / 32: the unrolled J(beta) loads and products are a third of this
 // kernel's instructions at 32), GA = ceil(J / 8) (compile-time divisors in the A2 store loop)
 template <int NBC, int GA>
@@ -245,7 +243,6 @@ constexpr int kFragHalfs = 512;      // one piece = 64 lanes x 8 halfs = 1 KiB
 // v_posed (which die tile by tile), so the three coordinates of a (frame, vertex) pair meet in registers and leave as ONE
 // 12-byte store - no LDS parking, no spills.  Bytes into LDS per 32 x 32 sub-tile: 41 KiB (128 x 64 kernel: 60 KiB).
 // ---------------------------------------------------------------------------------------------
-constexpr int kTileSlotBytes = 64 * 1024;
 #ifndef K2B_TILE_AHEAD
 #define K2B_TILE_AHEAD(NKT) ((NKT) <= 3)
 #endif
@@ -615,22 +612,23 @@ __global__ void k2b_gather_joints_kernel(const float* __restrict__ verts, const 
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
-int lbs_frames_padded(int num_frames) { return (num_frames + 31) / 32 * 32; }
-
-hipError_t launch_pose_setup(const PoseArgs& a_in, hipStream_t stream) {
+// the pose grid, both persistent grids and the tile kernel's LDS bytes: k2b_lbs_plan.h
+hipError_t launch_pose_setup(const PoseArgs& a_in, int pose_capacity, hipStream_t stream) {
     if (a_in.num_frames <= 0) return hipSuccess;
-    if (a_in.k_steps_x > kMaxXSteps || a_in.num_joints > kMaxJoints || a_in.num_betas > kMaxShape) return hipErrorInvalidValue;
-    const int GA = tile_groups_a(a_in.num_joints);
+    if (a_in.k_steps_x > kMaxXSteps || a_in.num_joints > kMaxJoints || a_in.num_betas > pose_capacity) return hipErrorInvalidValue;
     PoseArgs a = a_in;
 #ifndef K2B_POSE_XCD
 #define K2B_POSE_XCD 1
 #endif
-    a.xcd_frames = (K2B_POSE_XCD && a.num_frames > 256) ? (a.num_frames + 255) / 256 * 32 : 0;
-    const dim3 grid(a.xcd_frames ? 8 * a.xcd_frames : a.num_frames), block(64);
-#define K2B_POSE(NBC_, GA_) hipLaunchKernelGGL((k2b_pose_setup_kernel<NBC_, GA_>), grid, block, 0, stream, a)
-    if (GA == 3) { if (a.num_betas <= 10) K2B_POSE(10, 3); else if (a.num_betas <= 16) K2B_POSE(16, 3); else K2B_POSE(32, 3); }
-    else if (GA == 7) { if (a.num_betas <= 10) K2B_POSE(10, 7); else if (a.num_betas <= 20) K2B_POSE(20, 7); else K2B_POSE(32, 7); }
-    else return hipErrorInvalidValue;                      // 17..24 joints (SMPL) or 49..56 (SMPL-H / SMPL-X)
+    const LbsPoseGrid g = lbs_pose_grid(a.num_frames, K2B_POSE_XCD);
+    a.xcd_frames = g.xcd_frames;
+#define K2B_POSE(NBC_, GA_) \
+    case NBC_ * 8 + GA_: hipLaunchKernelGGL((k2b_pose_setup_kernel<NBC_, GA_>), dim3(g.grid), dim3(64), 0, stream, a); break
+    switch (pose_capacity * 8 + tile_groups_a(a.num_joints)) {
+        K2B_POSE(10, 3); K2B_POSE(16, 3); K2B_POSE(32, 3);
+        K2B_POSE(10, 7); K2B_POSE(20, 7); K2B_POSE(32, 7);
+        default: return hipErrorInvalidValue;              // 17..24 joints (SMPL) or 49..56 (SMPL-H / SMPL-X)
+    }
 #undef K2B_POSE
     return hipGetLastError();
 }
@@ -638,10 +636,9 @@ hipError_t launch_pose_setup(const PoseArgs& a_in, hipStream_t stream) {
 hipError_t launch_skin_tiles(const TileArgs& a_in, int num_cus, hipStream_t stream) {
     if (a_in.num_frames <= 0 || a_in.num_out <= 0) return hipSuccess;
     TileArgs a = a_in;
-    const int vgroups = (a.v_tiles + 3) / 4, fgroups = (a.f_tiles + 3) / 4;
-    const int wgs = a.num_wgs = persistent_grid(num_cus, (long long)vgroups * fgroups);
+    const int wgs = a.num_wgs = lbs_tile_grid(num_cus, a.v_tiles, a.f_tiles);
     const int GA = a.groups_a;
-    const size_t lds = (size_t)2 * kTileSlotBytes + (size_t)8 * tile_ngp(GA) * 256;
+    const size_t lds = lbs_tile_lds_bytes(GA);
     if (a.k_steps_x & 1) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
 #define K2B_TILE(GA_, EPS_)                                                                                          \

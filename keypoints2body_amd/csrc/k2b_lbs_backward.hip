@@ -37,9 +37,9 @@ constexpr int kBwdFrames = 16;                    // frames of a tile: the M of 
 constexpr int kBwdChunk = 64;                     // vertices per chunk
 constexpr int kBwdCols = 3 * kBwdChunk;
 constexpr int kBwdRow = kBwdCols + 4;             // LDS row stride of the [frame][3 vertex + c] tiles (4 x odd: conflict-free A reads)
-constexpr int kBwdMaxGroups = 16;                 // slabs per frame at most
-constexpr int kBwdMinChunksPerGroup = 4;
 constexpr int kBwdThreads = 256;
+// groups, workspace and LDS bytes of a call are sized for this tile by lbs_backward_plan (k2b_lbs_plan.h)
+static_assert(kBwdFrames == kBwdPlanFrames && kBwdChunk == kBwdPlanChunk && kBwdRow == kBwdPlanRow, "k2b_lbs_plan.h plans for another tile");
 
 struct BwdArgs {
     // model (device): smplx tensors as uploaded by k2b_model_create
@@ -464,25 +464,16 @@ __global__ __launch_bounds__(64) void k2b_lbs_backward_tail_kernel(const BwdArgs
     }
 }
 
-size_t dense_lds_bytes(int J, int KP, int MT) {
-    return ((size_t)kBwdFrames * (KP + 4) + (size_t)kBwdFrames * J * 12 + 3 * (size_t)kBwdFrames * kBwdRow + (size_t)kBwdChunk * (16 * MT + 1) +
-            kBwdCols) * sizeof(float);
-}
-
-hipError_t launch_dense(const BwdArgs& a, hipStream_t stream) {
-    const dim3 grid(a.G, (a.B + kBwdFrames - 1) / kBwdFrames);
-    if (a.J <= 24) {
-        static std::atomic<unsigned long long> done{0};
-        const size_t lds = dense_lds_bytes(a.J, a.KP, 2);
-        if (const hipError_t e = ensure_dynamic_lds(k2b_lbs_backward_dense_kernel<2, 4>, done, lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k2b_lbs_backward_dense_kernel<2, 4>), grid, dim3(kBwdThreads), lds, stream, a);
-    } else {
-        static std::atomic<unsigned long long> done{0};
-        const size_t lds = dense_lds_bytes(a.J, a.KP, 4);
-        if (const hipError_t e = ensure_dynamic_lds(k2b_lbs_backward_dense_kernel<4, 9>, done, lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k2b_lbs_backward_dense_kernel<4, 9>), grid, dim3(kBwdThreads), lds, stream, a);
-    }
+// the instantiation and its LDS bytes come with the plan (k2b_lbs_plan.h)
+template <int MT, int TPW>
+hipError_t launch_dense_as(const BwdArgs& a, const LbsBackwardPlan& p, hipStream_t stream) {
+    static std::atomic<unsigned long long> done{0};
+    if (const hipError_t e = ensure_dynamic_lds(k2b_lbs_backward_dense_kernel<MT, TPW>, done, p.dense_lds_bytes); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k2b_lbs_backward_dense_kernel<MT, TPW>), dim3(p.G, p.frame_tiles), dim3(kBwdThreads), p.dense_lds_bytes, stream, a);
     return hipGetLastError();
+}
+hipError_t launch_dense(const BwdArgs& a, const LbsBackwardPlan& p, hipStream_t stream) {
+    return p.dense_mt == 2 ? launch_dense_as<2, 4>(a, p, stream) : launch_dense_as<4, 9>(a, p, stream);
 }
 
 }  // namespace
@@ -522,10 +513,10 @@ extern "C" int k2b_lbs_backward(const k2b_model* model_c, int32_t B, const float
     if (B == 0) return K2B_OK;
     if (!go || !bp || !be) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs_backward: NULL parameter buffer");
     if (!grad_joints && !grad_vertices) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_lbs_backward: no cotangent given");
-    if (m->groups_a != 3 && m->groups_a != 7)
+    if (m->lbs.route == k2b::LbsRoute::unsupported)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs_backward: %d joints; k2b_lbs and its backward are built for 17-24 (SMPL) and 49-56 (SMPL-H / SMPL-X) joints", m->J);
     if (m->NB < 1 || m->NB > k2b::kMaxShape) return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs_backward: %d shape coefficients, at most %d", m->NB, k2b::kMaxShape);
-    if ((B + k2b::kBwdFrames - 1) / k2b::kBwdFrames > 65535) return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs_backward: %d frames exceed one launch", B);
+    if (k2b::lbs_backward_frame_tiles(B) > k2b::kBwdMaxFrameTiles) return fail(K2B_ERR_UNSUPPORTED, "k2b_lbs_backward: %d frames exceed one launch", B);
     if (!g_go && !g_bp && !g_be && !g_tr) return K2B_OK;
     hipStream_t stream = (hipStream_t)stream_v;
     {
@@ -533,35 +524,30 @@ extern "C" int k2b_lbs_backward(const k2b_model* model_c, int32_t B, const float
         if (const int rc = lbs_backward_tables(m); rc != K2B_OK) return rc;
     }
     const k2b_model::LbsBackward& t = m->bwd;
+    // the vertex set: every vertex, or (no vertex cotangent) the vertices the surface rows name
+    const bool dense = grad_vertices != nullptr;
+    const k2b::LbsBackwardPlan p = k2b::lbs_backward_plan(m->J, m->NB, m->V, t.U, B, dense);
     k2b::BwdArgs a{};
     a.v_template = m->v_template.get(); a.shapedirs = m->shapedirs.get(); a.posedirs = m->posedirs.get(); a.lbs_weights = m->lbs_weights.get();
     a.j_template = m->j_template.get(); a.j_dirs = m->j_dirs.get(); a.parents = m->parents.get();
     a.V = m->V; a.J = m->J; a.NB = m->NB;
-    a.PF = 9 * (m->J - 1); a.PF16 = (a.PF + 15) / 16 * 16; a.KP = a.PF16 + (m->NB <= 16 ? 16 : 32);
-    a.QN = (m->J + 1) * 12; a.SL = a.QN + a.KP;
+    a.PF = p.PF; a.PF16 = p.PF16; a.KP = p.KP; a.QN = p.QN; a.SL = p.SL;
     a.ostride = m->J + m->E + m->lmk.L;
-    // the vertex set: every vertex, or (no vertex cotangent) the vertices the surface rows name
-    const bool dense = grad_vertices != nullptr;
-    a.NV = dense ? m->V : t.U;
+    a.NV = p.NV; a.nchunks = p.nchunks; a.chunks_per_group = p.chunks_per_group; a.G = p.G;   // G 0: a joints-only call on a model without surface rows
     a.vlist = dense ? nullptr : t.ints.get();
     a.item_row = t.ints.get() + t.o_rows;
     a.item_pos = t.ints.get() + (dense ? t.o_pos_dense : t.o_pos_compact);
     a.chunk_off = t.ints.get() + (dense ? t.o_off_dense : t.o_off_compact);
     a.item_w = t.w.get();
-    a.nchunks = (a.NV + k2b::kBwdChunk - 1) / k2b::kBwdChunk;
-    a.chunks_per_group = std::max(k2b::kBwdMinChunksPerGroup, (a.nchunks + k2b::kBwdMaxGroups - 1) / k2b::kBwdMaxGroups);
-    a.G = (a.nchunks + a.chunks_per_group - 1) / a.chunks_per_group;      // 0: a joints-only call on a model without surface rows
     a.B = B; a.go = go; a.bp = bp; a.be = be; a.grad_joints = grad_joints; a.grad_vertices = grad_vertices;
     a.g_go = g_go; a.g_bp = g_bp; a.g_be = g_be; a.g_tr = g_tr;
-    const int bpad = (B + k2b::kBwdFrames - 1) / k2b::kBwdFrames * k2b::kBwdFrames;
-    const size_t nX = a.G ? (size_t)bpad * a.KP : 0, nT = a.G ? (size_t)bpad * a.J * 12 : 0, nS = (size_t)B * a.G * a.SL;
     StreamWorkspace ws(stream);
-    if (a.G) {
-        HIP_TRY(ws.alloc((nX + nT + nS) * sizeof(float)));
-        a.X = reinterpret_cast<float*>(ws.get()); a.T = a.X + nX; a.slab = a.T + nT;
-        hipLaunchKernelGGL(k2b::k2b_lbs_backward_prep_kernel, dim3(bpad), dim3(64), 0, stream, a);
+    if (p.G) {
+        HIP_TRY(ws.alloc(p.workspace_floats() * sizeof(float)));
+        a.X = reinterpret_cast<float*>(ws.get()); a.T = a.X + p.x_floats; a.slab = a.T + p.t_floats;
+        hipLaunchKernelGGL(k2b::k2b_lbs_backward_prep_kernel, dim3(p.frames_padded), dim3(64), 0, stream, a);
         HIP_TRY_MSG(hipGetLastError(), "k2b_lbs_backward: prep launch failed");
-        HIP_TRY_MSG(k2b::launch_dense(a, stream), "k2b_lbs_backward: dense launch failed");
+        HIP_TRY_MSG(k2b::launch_dense(a, p, stream), "k2b_lbs_backward: dense launch failed");
     }
     hipLaunchKernelGGL(k2b::k2b_lbs_backward_tail_kernel, dim3(B), dim3(64), 0, stream, a);
     HIP_TRY_MSG(hipGetLastError(), "k2b_lbs_backward: tail launch failed");

@@ -490,7 +490,7 @@ hipError_t launch_stream(void (*kernel)(const StreamArgs), const StreamArgs& a_i
     if (a_in.num_frames <= 0 || a_in.num_out <= 0) return hipSuccess;
     StreamArgs a = a_in;
     if ((a.nv16 & 7) || a.f32_tiles <= 0) return hipErrorInvalidValue;
-    a.num_wgs = persistent_grid(num_cus, (long long)(a.nv16 >> 3) * ((a.f32_tiles + 3) >> 2));
+    a.num_wgs = lbs_stream_grid(num_cus, a.nv16, a.f32_tiles);
     static std::atomic<unsigned long long> lds_set{0};
     const hipError_t e = ensure_dynamic_lds(kernel, lds_set, stream_lds_bytes<S>());
     if (e != hipSuccess) return e;
@@ -504,14 +504,13 @@ __global__ __launch_bounds__(512) void k2b_lbs_stream_kernel(const StreamArgs a)
 __global__ __launch_bounds__(512) void k2b_lbs_stream_x_kernel(const StreamArgs a) { stream_body<SmplX>(a); }
 __global__ __launch_bounds__(512) void k2b_lbs_stream_xw_kernel(const StreamArgs a) { stream_body<SmplXWide>(a); }
 
-hipError_t launch_skin_stream(const StreamArgs& a, int num_cus, hipStream_t stream) {
-    return launch_stream<Smpl>(k2b_lbs_stream_kernel, a, num_cus, stream);
-}
-hipError_t launch_skin_stream_x(const StreamArgs& a, int num_cus, hipStream_t stream) {
-    return launch_stream<SmplX>(k2b_lbs_stream_x_kernel, a, num_cus, stream);
-}
-hipError_t launch_skin_stream_xw(const StreamArgs& a, int num_cus, hipStream_t stream) {
-    return launch_stream<SmplXWide>(k2b_lbs_stream_xw_kernel, a, num_cus, stream);
+hipError_t launch_skin_stream(LbsRoute route, const StreamArgs& a, int num_cus, hipStream_t stream) {
+    switch (route) {
+        case LbsRoute::stream: return launch_stream<Smpl>(k2b_lbs_stream_kernel, a, num_cus, stream);
+        case LbsRoute::stream_x: return launch_stream<SmplX>(k2b_lbs_stream_x_kernel, a, num_cus, stream);
+        case LbsRoute::stream_xw: return launch_stream<SmplXWide>(k2b_lbs_stream_xw_kernel, a, num_cus, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace k2b

@@ -97,13 +97,11 @@ def forward_cases():
 # ---- the host's rule ------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def route_constants_in_source() -> dict:
-    """kStreamKSteps, kStreamXKSteps, kStreamXWKSteps (32-deep k-steps of the three stream kernels, ``k2b_internal.h``) and
-    kMaxXSteps (16-deep k-steps the pose set-up can stage, ``k2b_lbs.hip``)."""
-    internal, lbs = (CSRC / "k2b_internal.h").read_text(), (CSRC / "k2b_lbs.hip").read_text()
-    out = {name: int(re.search(rf"constexpr int {name} = (\d+);", internal).group(1))
-           for name in ("kStreamKSteps", "kStreamXKSteps", "kStreamXWKSteps")}
-    out["kMaxXSteps"] = int(re.search(r"constexpr int kMaxXSteps = (\d+);", lbs).group(1))
-    return out
+    """kStreamKSteps, kStreamXKSteps, kStreamXWKSteps (32-deep k-steps of the three stream kernels) and kMaxXSteps (16-deep
+    k-steps the pose set-up can stage), all in ``k2b_lbs_plan.h``."""
+    plan = (CSRC / "k2b_lbs_plan.h").read_text()
+    return {name: int(re.search(rf"constexpr int {name} = (\d+);", plan).group(1))
+            for name in ("kStreamKSteps", "kStreamXKSteps", "kStreamXWKSteps", "kMaxXSteps")}
 
 
 def expected_route(J: int, NB: int, constants=None):
