@@ -163,6 +163,23 @@ typedef struct k2b_fit_config {
      * (0 = all; SMPL-X: 10, the expression stays free as in world_space.py:137-151,215-229). */
     int32_t prior_pose_dims;
     int32_t num_betas_prior;
+    /* K2B_SINCE(1, 7).  Joint term in image space: 0 = off (the 3D term above, the default); 1 = perspective reprojection
+     * (k2b_fit_world only).  The target buffer keeps its [B][K][3] layout; row k holds (u - cx, v - cy, ignored): pixel
+     * coordinates WITH THE PRINCIPAL POINT ALREADY SUBTRACTED by the caller (in float64, before the rounding to float32:
+     * raw pixel coordinates of a few hundred lose more in that rounding than the gradient tests allow).  For
+     * every targeted joint, with (X, Y, Z) = p_k + transl (transl = the camera translation, as in the camera-space fitter):
+     *     e_x = fx X / Z - u',   e_y = fy Y / Z - v'
+     *     loss term = w_j^2 sum_k c_k^2 (gmof(e_x, sigma) + gmof(e_y, sigma)),   sigma in pixels
+     * and every other term, optimize_mask, freeze_betas, the confidences and the loss convention as for the 3D term.
+     * Z is divided by as it stands (no clamp): a joint behind the camera (Z < 0) is legal and finite; a targeted joint of
+     * non-zero confidence at Z = 0 makes THAT frame's loss and gradient non-finite and no other frame's (Conventions); a joint
+     * without a target, or with confidence 0, contributes exactly nothing whatever its depth.
+     * Kinematic targets only (a surface target: K2B_ERR_UNSUPPORTED), Adam and independent frames only (every other fit
+     * entry refuses projection != 0 with K2B_ERR_UNSUPPORTED, as does a model created under K2B_FIT_SCAN64=1).
+     * The term has NO counterpart in the reference (api/frame.py:71-75 raises for joints2d): it is defined here and held to
+     * a float64 oracle of this formula, not to reference outputs. */
+    int32_t projection;
+    float focal[2];             /* fx, fy in pixels: finite and > 0; read only when projection != 0 */
 } k2b_fit_config;
 
 void k2b_fit_config_default(k2b_fit_config *cfg);

@@ -1,0 +1,193 @@
+"""Image-space two-stage fitter on the HIP engine: SMPL / SMPL-H / SMPL-X fitted to 2D keypoints under a pinhole camera.
+
+The reference has no such path (``keypoints2body/api/frame.py:71-75`` raises for ``joints2d``), so this fitter is DEFINED here
+and pinned to a float64 oracle of its own formulas (``tests/reproj_common.py``), not to reference outputs.  It is modelled on
+``CameraSpaceFitter``: two launches of the fused fit kernels for a batch of independent frames, with the joint term in its
+projected form (``k2b_fit_config.projection = 1``, ``include/k2b.h``):
+
+    e = (fx X / Z - (u - cx), fy Y / Z - (v - cy)),   (X, Y, Z) = joint + camera translation,
+    loss = w_j^2 sum_k c_k^2 (gmof(e_x, sigma) + gmof(e_y, sigma)) + the priors of the 3D fit,      sigma in pixels.
+
+The principal point never reaches the kernel: it is subtracted from the keypoints here, in float64, before they are rounded
+to float32 (a pixel coordinate is a few hundred times its residual; DESIGN.md 4.4d has the figures).
+
+* initial translation, by similar triangles over the four torso joints (``TORSO_JOINTS``) of the start pose, one joints-only
+  forward as in ``guess_init_3d``: ``t_z`` = (mean 3D length of the torso's four edges) / (mean length of the same edges between
+  the detections, in normalised image coordinates ``(u' / fx, v' / fy)``), and ``t_xy`` puts the torso's centroid on the detected
+  centroid at that depth;
+* stage 1: ``[global_orient, camera translation]`` (``optimize_mask = 9``) against the torso joints with a plain squared pixel
+  error (GMoF with sigma -> inf, weight 1), every pose / shape prior off.  On 24-joint models the depth prior
+  ``depth_weight^2 |t - t0|^2`` pulls toward the initial translation; the tree kernel of SMPL-H / SMPL-X has no translation
+  prior (its entry refuses one), so those models run stage 1 WITHOUT it;
+* stage 2: all targets, all priors, ``sigma`` (default 100 px) and ``joint_loss_weight`` (default 1: pixel residuals are two
+  orders above metric ones); betas are optimised iff ``seq_ind == 0 or not freeze_betas``, as the camera fitter does;
+* result: ``transl`` = the camera translation, model-space joints / vertices from the usual final forward (no translation
+  applied), ``loss`` = stage 2's loss re-evaluated at the result without the preserve term (one evaluate-only launch).
+
+Adam only: the device L-BFGS entries refuse the projected term (``K2B_ERR_UNSUPPORTED``), so ``use_lbfgs=True`` raises.
+Kinematic targets only (model index below the joint count): surface targets keep their 3D term.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ... import native
+from ...models.body_model import check_target_indices
+from ...models.smpl_data import BodyModelFitResult, SMPLData
+from ...prior import MaxMixturePrior
+from ..constants import JOINT_MAP, TORSO_JOINTS
+from .common import FitterBase
+from .world_space import WorldSpaceFitter
+
+_TORSO_IDX = [JOINT_MAP[name] for name in TORSO_JOINTS]     # RHip, LHip, RShoulder, LShoulder: the same in every SMPL-family tree
+_TORSO_EDGES = ((0, 1), (2, 3), (0, 2), (1, 3))             # hips, shoulders, right side, left side
+_SQUARED_ERROR_SIGMA = 1.0e8                                # gmof(e, sigma) -> e^2 in fp32
+
+
+def centred_keypoints(keypoints2d, principal_point) -> np.ndarray:
+    """(B, K, 2) pixel coordinates -> float32 target rows (B, K, 3) = (u - cx, v - cy, 0); the subtraction in float64."""
+    kp = keypoints2d.detach().cpu().numpy() if isinstance(keypoints2d, torch.Tensor) else np.asarray(keypoints2d)
+    if kp.ndim != 3 or kp.shape[2] != 2:
+        raise ValueError(f"keypoints2d must be (B,K,2), got {tuple(kp.shape)}")
+    pp = np.asarray(principal_point, dtype=np.float64).reshape(-1)
+    if pp.shape != (2,) or not np.isfinite(pp).all():
+        raise ValueError("principal_point must be two finite numbers (cx, cy)")
+    out = np.zeros(kp.shape[:2] + (3,), dtype=np.float32)
+    out[..., :2] = kp.astype(np.float64) - pp
+    return out
+
+
+def focal_pair(focal) -> tuple:
+    f = np.asarray(focal, dtype=np.float64).reshape(-1)
+    if f.shape == (1,):
+        f = np.repeat(f, 2)
+    if f.shape != (2,) or not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError("focal must be a positive finite number or a pair (fx, fy)")
+    return float(f[0]), float(f[1])
+
+
+def guess_init_2d(model_joints: torch.Tensor, torso_uv: torch.Tensor, focal: tuple, torso_index: torch.Tensor) -> torch.Tensor:
+    """Initial camera translation (B, 3) by similar triangles: `model_joints` (B, J, 3) of the start pose without translation,
+    `torso_uv` (B, 4, >=2) the centred detections of ``TORSO_JOINTS`` in that order."""
+    p = model_joints.index_select(1, torso_index)
+    n = torso_uv[..., :2] / torch.tensor(focal, dtype=torso_uv.dtype, device=torso_uv.device)           # normalised image coordinates
+    a, b = [e[0] for e in _TORSO_EDGES], [e[1] for e in _TORSO_EDGES]
+    len3 = (p[:, a] - p[:, b]).norm(dim=-1).mean(dim=1)
+    len2 = (n[:, a] - n[:, b]).norm(dim=-1).mean(dim=1)
+    depth = len3 / len2
+    c3, c2 = p.mean(dim=1), n.mean(dim=1)
+    return torch.stack([c2[:, 0] * depth - c3[:, 0], c2[:, 1] * depth - c3[:, 1], depth - c3[:, 2]], dim=1)
+
+
+class ImageSpaceFitter(FitterBase):
+    """Per-frame optimizer against 2D keypoints under a pinhole camera, executed on one MI355X."""
+
+    # SMPL-H / SMPL-X in kernel layout, and the data class of a result: the world fitter's, which read ``self.smpl`` alone
+    _pack = WorldSpaceFitter._pack
+    _packed_config = WorldSpaceFitter._packed_config
+    result_params = WorldSpaceFitter.result_params
+
+    def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=False, joints_category="AMASS", device=None,
+                 pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None):
+        if use_lbfgs:
+            raise NotImplementedError("ImageSpaceFitter runs Adam only: the device L-BFGS entries (k2b_fit_world_lbfgs and the "
+                                      "sequence entries) refuse the projected joint term; pass use_lbfgs=False")
+        super().__init__(smpl_model, step_size, use_lbfgs, joints_category, device, pose_prior_num_gaussians, pose_prior)
+        if self.smpl.num_joints not in (24, 52, 55):
+            raise NotImplementedError(f"a body model with {self.smpl.num_joints} joints: the fit kernels are built for 24, 52 and 55")
+        self.num_iters = num_iters
+
+    def stage_configs(self, focal, seq_ind=0, sigma=100.0, joint_loss_weight=1.0, pose_preserve_weight=5.0, freeze_betas=True,
+                      depth_weight=100.0):
+        """Kernel configurations of the two stages, ``(cfg1, cfg2, fit_betas)`` (module docstring)."""
+        fx, fy = focal_pair(focal)
+        tree = self.smpl.num_joints != 24 or self.smpl.packed          # (no translation prior in the tree kernel)
+        cfg1 = native.default_fit_config()
+        cfg1.num_iters, cfg1.step_size = int(self.num_iters), float(self.step_size)
+        cfg1.sigma, cfg1.joint_loss_weight = _SQUARED_ERROR_SIGMA, 1.0
+        cfg1.pose_prior_weight = cfg1.angle_prior_weight = cfg1.shape_prior_weight = cfg1.pose_preserve_weight = 0.0
+        cfg1.optimize_mask, cfg1.transl_prior_weight = 9, 0.0 if tree else float(depth_weight)
+        cfg2 = native.default_fit_config()
+        cfg2.num_iters, cfg2.step_size = int(self.num_iters), float(self.step_size)
+        cfg2.sigma, cfg2.joint_loss_weight = float(sigma), float(joint_loss_weight)
+        cfg2.pose_preserve_weight = float(pose_preserve_weight) if seq_ind > 0 else 0.0
+        fit_betas = seq_ind == 0 or not freeze_betas
+        cfg2.optimize_mask = 15 if fit_betas else 11
+        for cfg in (cfg1, cfg2):
+            cfg.projection, cfg.focal[0], cfg.focal[1] = 1, fx, fy
+            self._packed_config(cfg)
+        return cfg1, cfg2, fit_betas
+
+    def _start_rows(self, init_params):
+        go = self._dev(init_params.global_orient, 3)
+        if self.smpl.packed:
+            bp, be = self._pack(init_params, go.shape[0])
+        else:
+            bp = self._dev(init_params.body_pose, 3 * (self.smpl.num_joints - 1))
+            be = self._dev(init_params.betas, self.smpl.num_betas)
+        return go, bp, be
+
+    def fit_batch(self, init_params: SMPLData, keypoints2d, focal, principal_point=(0.0, 0.0), conf=None, seq_ind: int = 0,
+                  target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
+                  pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
+                  init_cam_t=None, per_frame_conf: bool = False, want_vertices: bool = True, run_forward: bool = True):
+        """Both stages for B independent frames: ``(params dict of (B, .) tensors - ``transl`` = the camera translation -,
+        joints, vertices, per-frame loss)``.  `keypoints2d` (B, K, 2) in pixels, in the order of this fitter's joint category
+        or of `target_model_indices`; `focal` a number or ``(fx, fy)``; `conf` (K,) or, with `per_frame_conf`, (B, K)."""
+        fx, fy = focal_pair(focal)
+        targets = torch.from_numpy(centred_keypoints(keypoints2d, principal_point))
+        B = targets.shape[0]
+        go, bp, be = self._start_rows(init_params)
+        if not (go.shape[0] == bp.shape[0] == be.shape[0] == B):
+            raise ValueError("init_params and keypoints2d disagree on the number of frames")
+        model_idx, rows = self._target_selection(target_model_indices, targets.shape[1])
+        if len(model_idx) != (targets.shape[1] if rows is None else len(rows)):
+            raise ValueError("target_model_indices must have one entry per keypoint")
+        check_target_indices(self.smpl, model_idx)
+        if any(int(j) >= self.smpl.num_joints for j in model_idx):
+            raise NotImplementedError("projected surface targets (vertex-selected joints, landmarks) are not built: kinematic joints only")
+        targets = (targets if rows is None else targets[:, rows]).to(self.device).contiguous()
+        cf = self._confidence(conf, per_frame_conf, rows)
+
+        # stage 1's targets: the four torso joints among the detections
+        missing = [TORSO_JOINTS[i] for i, j in enumerate(_TORSO_IDX) if j not in model_idx]
+        if missing:
+            raise ValueError(f"the torso joints {missing} are not among the targets: the initial translation and stage 1 need all four")
+        torso_cols = torch.tensor([model_idx.index(j) for j in _TORSO_IDX], dtype=torch.int64, device=self.device)
+        torso_tgt = targets.index_select(1, torso_cols).contiguous()
+        if init_cam_t is None:
+            joints0 = self.smpl.native.lbs(go, bp, be, None, want_vertices=False)[0]
+            cam_t0 = guess_init_2d(joints0, torso_tgt, (fx, fy), torch.tensor(_TORSO_IDX, dtype=torch.int64, device=self.device))
+        else:
+            cam_t0 = self._dev(init_cam_t, 3)
+        cam_t0 = cam_t0.detach().contiguous()
+
+        cfg1, cfg2, _ = self.stage_configs((fx, fy), seq_ind, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight)
+        prior_target = cam_t0 if cfg1.transl_prior_weight != 0.0 else None
+        cfg2.conf_per_frame = int(cf is not None and cf.dim() == 2)
+        fit = lambda cfg, idx, tgt, c, p, centre=None: native.fit_world(
+            self.smpl.native, self.pose_prior.native, cfg, idx, tgt, c, p["global_orient"], p["body_pose"], p["betas"], p["transl"],
+            transl_prior_target=centre)
+        s1 = fit(cfg1, _TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0), prior_target)
+        s2 = fit(cfg2, model_idx, targets, cf, s1)
+        out = {k: s2[k] for k in native.PARAM_KEYS}
+        # the loss at the result: stage 2's terms without the preserve term, one evaluate-only launch
+        cfg2.num_iters, cfg2.step_size, cfg2.pose_preserve_weight = 1, 0.0, 0.0
+        out["loss"] = fit(cfg2, model_idx, targets, cf, out)["loss"]
+        self.last_init_cam_t = cam_t0
+        return self._result(out, run_forward, want_vertices)
+
+    def final_forward(self, out, want_vertices=True):
+        """Model-space joints / vertices: the camera translation is part of the parameters, not applied to the mesh."""
+        return self.smpl.native.lbs(out["global_orient"], out["body_pose"], out["betas"], None, want_vertices=want_vertices)
+
+    def fit_frame(self, init_params: SMPLData, keypoints2d, focal, principal_point=(0.0, 0.0), conf=None, seq_ind: int = 0,
+                  target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
+                  pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
+                  init_cam_t=None) -> BodyModelFitResult:
+        out, joints, verts, loss = self.fit_batch(init_params, keypoints2d, focal, principal_point, conf, seq_ind, target_model_indices,
+                                                  sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight, init_cam_t)
+        return BodyModelFitResult(params=self.result_params(out, init_params), vertices=verts, joints=joints, loss=loss.sum())

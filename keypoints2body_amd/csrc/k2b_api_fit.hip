@@ -64,6 +64,23 @@ int check_surface_targets(const Targets& t, const FitCall& c, int J) {
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence: vertex-selected joints are not built into the chain (fit frame by frame)");
     return K2B_OK;
 }
+// k2b_fit_config::projection: its values, and what the projected joint term is not built into
+int check_projection(const k2b_fit_config* cfg, const FitCall& c) {
+    if (cfg->projection == 0) return K2B_OK;
+    if (cfg->projection != 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: projection=%d must be 0 or 1", cfg->projection);
+    for (int i = 0; i < 2; ++i)
+        if (!(cfg->focal[i] > 0.0f) || !(cfg->focal[i] <= 3.402823466e38f))      // (NaN fails the first comparison)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: focal[%d]=%g must be finite and positive", i, (double)cfg->focal[i]);
+    if (c.chain.len > 1 || c.lbfgs.mode != k2b::LbMode::none)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the projected joint term is built for independent frames under Adam only");
+    return K2B_OK;
+}
+int check_projected_targets(const k2b_fit_config* cfg, const Targets& t) {
+    if (cfg->projection != 0 && !t.vsel.empty())
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: surface targets (vertex-selected joints, landmarks) keep the 3D term: "
+                    "no projection for model indices beyond the kinematic joints");
+    return K2B_OK;
+}
 int check_debug_shape(const k2b_fit_config* cfg) {
     if (cfg->debug_launch_shape < k2b::ForceShape::automatic || cfg->debug_launch_shape > k2b::ForceShape::wide)
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: debug_launch_shape=%d must be 0..4", cfg->debug_launch_shape);
@@ -94,6 +111,7 @@ void fill_call_fields(Args& a, const k2b_fit_config* cfg, const FitCall& c, cons
     a.chain_len = c.chain.len > 1 ? c.chain.len : 1;
     a.chain_iters = c.chain.iters;
     a.chain_meta = c.chain.len > 1 ? c.chain.meta : nullptr;
+    a.projection = cfg->projection; a.focal_x = cfg->focal[0]; a.focal_y = cfg->focal[1];
 }
 
 // ---- surface targets: the Adam loop as pairs of launches ---------------------------------------------------------------------
@@ -203,6 +221,7 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     k2b::FitTreeArgs a{};
     Targets t;
     if (const int rc = classify_targets(model, c, model->kin.pos.data(), &t); rc != K2B_OK) return rc;
+    if (const int rc = check_projected_targets(cfg, t); rc != K2B_OK) return rc;
     memcpy(a.lane_target, t.lane_target, sizeof a.lane_target);
     for (int i = 0; i < 4; ++i) {
         const int ai = cfg->angle_prior_index[i];
@@ -243,6 +262,10 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
     k2b::FitArgs a{};
     Targets t;
     if (const int rc = classify_targets(model, c, nullptr, &t); rc != K2B_OK) return rc;
+    if (const int rc = check_projected_targets(cfg, t); rc != K2B_OK) return rc;
+    if (cfg->projection != 0 && model->fit_scan64)
+        return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the projected joint term is built for the fp32 scans only (this model has no scan "
+                    "plan, or was created under K2B_FIT_SCAN64)");
     if (const int rc = check_surface_targets(t, c, model->J); rc != K2B_OK) return rc;
     for (int i = 0; i < 4; ++i) {
         const int ai = cfg->angle_prior_index[i];
@@ -313,6 +336,7 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence: followup_iters=%d", c.chain.iters);
     if (c.chain.len > 1 && (c.preserve || c.tr_prior || c.grad_out || cfg->transl_prior_weight != 0.0f))
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence: no explicit preserve pose, translation prior or gradient output in a chain");
+    if (const int rc = check_projection(cfg, c); rc != K2B_OK) return rc;
     const FusedEligibility el = fused_eligibility(model, prior, cfg);
     if (!el.fused) return fit_tree(model, const_cast<k2b_prior*>(prior), cfg, el.prior_dims, c);
     return fit_fused(model, prior, cfg, c);
@@ -401,6 +425,7 @@ int k2b_fit_sequence(const k2b_model* model, const k2b_prior* prior, const k2b_f
                      const float* j3d, const float* conf, const float* go_in, const float* bp_in, const float* be_in,
                      const float* tr_in, float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out,
                      void* stream) {
+    if (const int rc = refuse_projection("k2b_fit_sequence", cfg); rc != K2B_OK) return rc;
     if (frames_per_sequence < 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence: frames_per_sequence=%d", frames_per_sequence);
     if ((int64_t)num_sequences * frames_per_sequence > (int64_t)1 << 30)
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence: %d x %d frames", num_sequences, frames_per_sequence);
@@ -429,6 +454,7 @@ int k2b_fit_sequences(const k2b_model* model, const k2b_prior* prior, const k2b_
     RaggedSlots r;
     if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
     if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (const int rc = refuse_projection(who, cfg); rc != K2B_OK) return rc;
     if (followup_iters < 1 || followup_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
     if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_iters=%d", who, cfg->num_iters);
     if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);

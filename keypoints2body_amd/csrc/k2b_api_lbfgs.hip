@@ -125,6 +125,7 @@ struct LbfgsDims { int D, NB, P, history, H; };      // history: the caller's (0
 int lbfgs_preamble(const char* who, const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int max_iter,
                    const int* followup, int history_size, double lr, LbfgsDims* d) {
     if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (const int rc = refuse_projection(who, cfg); rc != K2B_OK) return rc;
     if (max_iter < 1 || max_iter > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: max_iter=%d", who, max_iter);
     if (history_size <= 0) history_size = k2b::kLbfgsMaxHistory;
     if (history_size > k2b::kLbfgsMaxHistory)

@@ -78,7 +78,7 @@ int device_cus() {
 
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 6u; }
+uint32_t k2b_version(void) { return (1u << 16) | 7u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
@@ -106,6 +106,8 @@ void k2b_fit_config_default(k2b_fit_config* c) {
     c->debug_launch_shape = 0;
     c->prior_pose_dims = 0;
     c->num_betas_prior = 0;
+    c->projection = 0;
+    c->focal[0] = c->focal[1] = 0.0f;
 }
 
 int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* bp, const float* be, const float* tr,

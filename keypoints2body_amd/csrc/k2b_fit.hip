@@ -66,6 +66,12 @@
 #define K2B_FSTAMP_ROW_PRINT ((void)0)
 #endif
 
+// A/B switch of the projected joint term (tools/build_fit_variant.sh name "-DK2B_PROJ_FAST_RCP=1"): 1 / Z by v_rcp_f32 instead of
+// the IEEE division.  The shipped library is built with 0: the variant passes the gradient gate and is no faster.
+#ifndef K2B_PROJ_FAST_RCP
+#define K2B_PROJ_FAST_RCP 0
+#endif
+
 namespace k2b {
 
 namespace {
@@ -203,8 +209,14 @@ __device__ __forceinline__ float frame_loss(float lanes, float c_y, float best, 
 // SCAN64: how the tree pass forms its subtree sums (k2b_lanes.h) - false: fp32 chain / end scans on the lanes of the model's scan
 // plan; true: fp64 prefix differences on lanes in DFS order (models without a plan).  A template parameter, not a branch in the
 // tree pass: a run-time-false block there costs the 16-wave shape spilled registers (profiles/HISTORY.md).
-template <int NBT, int MODE, bool SCAN64>
+// NBTF = NBT, or NBT | kProjForm for the joint term's projected form (block e of the tree pass: the perspective reprojection
+// residual of k2b_fit_config::projection; fp32 scans only).  The form rides in the first argument, not in a fourth one, so that
+// the 3D instantiations keep their symbol names: their code objects can be compared with those of any earlier build.
+template <int NBTF, int MODE, bool SCAN64>
 __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel(const FitArgs a) {
+    constexpr int NBT = NBTF & (kProjForm - 1);
+    constexpr bool PROJ = (NBTF & kProjForm) != 0;
+    static_assert(!(PROJ && SCAN64), "the projected form is built for the fp32 scans");
     constexpr bool SPLIT = Shape<MODE>::SPLIT, PAIR = Shape<MODE>::PAIR;
     constexpr int NROW = Shape<MODE>::NROW, CPW = Shape<MODE>::CPW;
     constexpr bool WIDE16 = Shape<MODE>::NWAVES == 16;       // four waves per SIMD: 128 registers per lane
@@ -493,6 +505,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     }
 
     const float s2 = a.sigma * a.sigma;
+    const float fx = PROJ ? a.focal_x : 0.f, fy = PROJ ? a.focal_y : 0.f;      // (read by the projected joint term only)
     const float wpp2 = a.pose_prior_w * a.pose_prior_w;
     const float wa2 = a.angle_w * a.angle_w;
     const float ws2 = a.shape_w * a.shape_w;
@@ -653,7 +666,26 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         // (no branch on "this lane has a target": wconf = 0 there, so its loss and gradient vanish)
         Vec3 gj;
         float part = 0.f;                  // per-lane partial of the joint loss
-        {
+        if constexpr (PROJ) {
+            // perspective form (k2b.h, k2b_fit_config::projection): e = (fx X / Z - u', fy Y / Z - v') with (X, Y, Z) = p + t and
+            // the target row (u', v', ignored) in centred pixels; g = J^T d with d = d gmof / d e as below.  Z is divided by as it
+            // stands (no clamp), so a lane that contributes nothing is SELECTED out, not multiplied by wconf = 0: beyond the tree
+            // the point is t itself, and 0 . inf at Z = 0 would poison the scans.  1 / Z is the IEEE division, not fast_rcp: the
+            // pixel coordinate is a few hundred times its residual, so an ulp of it is that much larger in the gradient (one
+            // division per pass).  Chosen by measurement, DESIGN.md 4.4d: with v_rcp_f32 (K2B_PROJ_FAST_RCP) the gradient gate still
+            // holds but the launch is no faster - 1.03 against 1.02 x the 3D one at 4096 frames, 0.99 against 0.98 at 1024.  The fused
+            // operations are pinned, as in adam_update.
+            const bool on = wconf != 0.f;
+            const float X = pj.x + tr.x, Y = pj.y + tr.y, iz = K2B_PROJ_FAST_RCP ? fast_rcp(pj.z + tr.z) : 1.0f / (pj.z + tr.z);
+            const float ex = __builtin_fmaf(fx * X, iz, -tgt.x), ey = __builtin_fmaf(fy * Y, iz, -tgt.y);
+            const float x2 = ex * ex, y2 = ey * ey;
+            const float dx = s2 + x2, dy = s2 + y2;
+            if (last) part = on ? wconf * ((s2 * x2) / dx + (s2 * y2) / dy) : 0.f;
+            const float k2 = 2.f * wconf * (s2 * s2);
+            const float gx = fx * (k2 * ex * fast_rcp(dx * dx)) * iz, gy = fy * (k2 * ey * fast_rcp(dy * dy)) * iz;
+            const float gz = -__builtin_fmaf(X, gx, Y * gy) * iz;
+            gj = {on ? gx : 0.f, on ? gy : 0.f, on ? gz : 0.f};
+        } else {
             const float ex = pj.x + tr.x - tgt.x, ey = pj.y + tr.y - tgt.y, ez = pj.z + tr.z - tgt.z;
             const float x2 = ex * ex, y2 = ey * ey, z2 = ez * ez;
             const float dx = s2 + x2, dy = s2 + y2, dz = s2 + z2;
@@ -1421,6 +1453,13 @@ static FitArgs frame_range(const FitArgs& a, int f0, int n) {
 template <int MODE>
 static void launch_shape(const FitLaunch& l, const FitArgs& a, hipStream_t stream) {
     const dim3 grid(l.grid), block(l.block_threads);
+    if constexpr (MODE != MODE_SPLIT_LBFGS) {
+        if (a.projection) {
+            if (l.NBT == 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10 | kProjForm, MODE, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k2b_fit_world_kernel<16 | kProjForm, MODE, false>), grid, block, 0, stream, a);
+            return;
+        }
+    }
     if (l.NBT == 10) {
         if (l.scan64) hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE, true>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((k2b_fit_world_kernel<10, MODE, false>), grid, block, 0, stream, a);
@@ -1435,6 +1474,8 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
     const FitPlan plan = plan_fit_world(a_in.num_frames, a_in.num_cus, a_in.num_betas, a_in.scan64 != 0, a_in.force_shape, a_in.lb_mode,
                                         a_in.chain_len);
     if (!plan.ok) return hipErrorInvalidValue;       // lb_mode and the batch disagree: the caller asks lbfgs_scheme_for first
+    // the projected term is instantiated for fp32 scans, independent frames and Adam only (the entries refuse the rest by name)
+    if (a_in.projection && (a_in.scan64 || a_in.lb_mode != LbMode::none || a_in.chain_len > 1)) return hipErrorInvalidValue;
     for (int i = 0; i < plan.num_launches; ++i) {
         const FitLaunch& l = plan.launch[i];
         FitArgs a = frame_range(a_in, l.first_frame, l.num_frames);

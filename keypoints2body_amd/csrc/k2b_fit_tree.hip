@@ -42,8 +42,14 @@ __device__ __forceinline__ float shfl(float v, int src) { return __shfl(v, src, 
 
 __device__ __forceinline__ double shfl64(double v, int src) { return bperm64(src << 2, v); }
 
-template <int NS, bool CHAIN>            // NS: capacity for shape coefficients (betas | expression): 16, 20 or 32; CHAIN: warm-start chains
+// NSF = NS, the capacity for shape coefficients (betas | expression): 16, 20 or 32, or NS | kProjForm for the joint term's projected
+// form (k2b_fit_config::projection; as in k2b_fit.hip the form rides in the first argument, so that the 3D instantiations keep
+// their symbol names); CHAIN: warm-start chains (3D form only)
+template <int NSF, bool CHAIN>
 __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs a) {
+    constexpr int NS = NSF & (kProjForm - 1);
+    constexpr bool PROJ = (NSF & kProjForm) != 0;
+    static_assert(!(PROJ && CHAIN), "the projected form is built for independent frames");
     extern __shared__ __attribute__((aligned(16))) float tlds[];
     // [8][16][64] half8 A fragments (128 KiB) | [M][64] h | [M][64] b | [M][64] mu | [TW][64] theta_v fp32 |
     // [TW][hi 64 | lo 64] theta_v f16 | [TW][M][64] y' | [TW][M] q | [M] constants | [M] 1 / scale
@@ -197,6 +203,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
         wconf = (a.joint_w * a.joint_w) * (cf * cf);
     }
     const float s2 = a.sigma * a.sigma;
+    const float fx = PROJ ? a.focal_x : 0.f, fy = PROJ ? a.focal_y : 0.f;      // (read by the projected joint term only)
 
     // ---- parameters and Adam state -----------------------------------------------------------------------------------------
     const int D = 3 * (J - 1);
@@ -345,7 +352,21 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
         const float t0 = read_lane(tr, 0), t1 = read_lane(tr, 1), t2 = read_lane(tr, 2);
         float lj = 0.f;
         Vec3 g = {0.f, 0.f, 0.f};
-        if (tk >= 0) {
+        if constexpr (PROJ) {
+            // perspective form (k2b.h, k2b_fit_config::projection): e = (fx X / Z - u', fy Y / Z - v'), (X, Y, Z) = p + t, the target
+            // row (u', v', ignored) in centred pixels; g = J^T d.  Z is divided by as it stands, so a target of confidence 0 is
+            // left out by the branch, not by its weight (0 . inf at Z = 0).  1 / Z is the IEEE division (k2b_fit.hip has the reason).
+            if (tk >= 0 && wconf != 0.f) {
+                const float X = pg.x + t0, Y = pg.y + t1, iz = 1.0f / (pg.z + t2);
+                const float ex = __builtin_fmaf(fx * X, iz, -ty0), ey = __builtin_fmaf(fy * Y, iz, -ty1);
+                const float x2 = ex * ex, y2 = ey * ey;
+                const float qx = s2 + x2, qy = s2 + y2;
+                if (it == nit - 1) lj = wconf * ((s2 * x2) / qx + (s2 * y2) / qy);
+                const float k2 = 2.f * wconf * (s2 * s2);
+                const float gx = fx * (k2 * ex * fast_rcp(qx * qx)) * iz, gy = fy * (k2 * ey * fast_rcp(qy * qy)) * iz;
+                g = {gx, gy, -__builtin_fmaf(X, gx, Y * gy) * iz};
+            }
+        } else if (tk >= 0) {
             const float ex = pg.x + t0 - ty0, ey = pg.y + t1 - ty1, ez = pg.z + t2 - ty2;
             const float x2 = ex * ex, y2 = ey * ey, z2 = ez * ez;
             const float qx = s2 + x2, qy = s2 + y2, qz = s2 + z2;
@@ -491,15 +512,16 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     }
 }
 
-template <int NS, bool CHAIN>
+template <int NSF, bool CHAIN>
 hipError_t launch_tree(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
     static std::atomic<unsigned long long> lds_set{0};
-    if (const hipError_t e = ensure_dynamic_lds(k2b_fit_tree_kernel<NS, CHAIN>, lds_set, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k2b_fit_tree_kernel<NS, CHAIN>), dim3(p.grid), dim3(p.block_threads), lds, stream, a);
+    if (const hipError_t e = ensure_dynamic_lds(k2b_fit_tree_kernel<NSF, CHAIN>, lds_set, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k2b_fit_tree_kernel<NSF, CHAIN>), dim3(p.grid), dim3(p.block_threads), lds, stream, a);
     return hipGetLastError();
 }
 template <int NS>
 hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
+    if (a.projection) return p.chain ? hipErrorInvalidValue : launch_tree<NS | kProjForm, false>(p, lds, a, stream);   // (the entry refuses chains by name)
     return p.chain ? launch_tree<NS, true>(p, lds, a, stream) : launch_tree<NS, false>(p, lds, a, stream);
 }
 

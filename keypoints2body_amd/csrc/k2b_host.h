@@ -240,6 +240,12 @@ hipError_t start_in_place(int B, int D, int NB, const ConstParams& in, const Par
 struct FusedEligibility { int prior_dims; bool fused; };
 FusedEligibility fused_eligibility(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg);
 bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx);
+// k2b_fit_config::projection is built into k2b_fit_world's Adam loop alone: the chain and L-BFGS entries refuse it by name
+inline int refuse_projection(const char* who, const k2b_fit_config* cfg) {
+    if (cfg && cfg->projection != 0)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term (projection=%d) is built into k2b_fit_world only", who, cfg->projection);
+    return K2B_OK;
+}
 int check_targets(const char* who, const k2b_model* m, int32_t K, const int32_t* idx);
 
 // Ragged sequences of the k2b_fit_sequences* entries: the chain slots in launch order.

@@ -13,6 +13,9 @@
 namespace k2b {
 
 constexpr int kMaxJoints = 64;
+// The fit kernels' joint term has two forms, the 3D residual and the perspective reprojection of k2b_fit_config::projection.  The
+// projected instantiations carry this bit in their first template argument (the shape-coefficient capacity, <= 32).
+constexpr int kProjForm = 256;
 // the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api_prior.hip):
 //   [m][tile 4][ks0 hi, ks1 hi, ks0 lo, ks1 lo][64 lanes][8 halfs]
 constexpr int kPriorFrag32Halfs = kPriorMaxGauss * 4 * 4 * 64 * 8;
@@ -83,6 +86,10 @@ struct FitArgs {
     // {row of the start parameters, first frame row, frame count >= 1, 0} (device).  A workgroup runs as many steps as its
     // longest slot; a slot whose sequence has ended takes the barriers and writes nothing.
     const int* chain_meta;
+    // joint term (k2b_fit_config::projection, focal): 0 = 3D residual, 1 = perspective reprojection of centred pixel targets.  Behind
+    // everything else: the 3D instantiations never read them, and their kernel-argument offsets stay what they were.
+    int projection;
+    float focal_x, focal_y;
 };
 
 hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
@@ -123,6 +130,8 @@ struct FitTreeArgs {
     const int* chain_meta;       // ragged chains: as FitArgs::chain_meta
     int comp_waves;             // set by launch_fit_tree: 4 = the mixture runs on four dedicated component waves (<= 4 frames per CU)
     int debug_shape;             // TreeShape (k2b_launch_plan.h): automatic = chosen by the batch size; plain / comp_waves force one (tests)
+    int projection;              // as FitArgs::projection, focal_x, focal_y (no chains)
+    float focal_x, focal_y;
 };
 hipError_t launch_fit_tree(const FitTreeArgs& a, int num_cus, hipStream_t stream);
 

@@ -47,6 +47,8 @@ class FitConfigC(C.Structure):
         ("debug_launch_shape", C.c_int32),
         ("prior_pose_dims", C.c_int32),
         ("num_betas_prior", C.c_int32),
+        ("projection", C.c_int32),
+        ("focal", C.c_float * 2),
     ]
 
 
