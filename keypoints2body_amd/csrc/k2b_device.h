@@ -62,8 +62,12 @@ __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sq
 // sin and cos of a non-negative angle with ONE shared range reduction (k = round(a 2/pi), two-term
 // Cody-Waite) and the fdlibm float kernels on [-pi/4, pi/4]; ~1-2 ulp.  Rotation angles are O(1);
 // beyond 1e3 rad the two-term reduction loses accuracy and the library functions take over.
+// RARE_BEHIND: the fast path runs unconditionally and the library values are patched in behind it, inside one wave-uniform
+// branch taken only when some lane of the wave is beyond 1e3 rad - every lane ends with the same value as in the other form,
+// and the caller's straight-line code in front of the call is not cut off from the polynomial by a per-lane branch.
+template <bool RARE_BEHIND = false>
 __device__ __forceinline__ void sincos_small(float a, float& s, float& c) {
-    if (a > 1.0e3f) { s = sinf(a); c = cosf(a); return; }
+    if (!RARE_BEHIND && a > 1.0e3f) { s = sinf(a); c = cosf(a); return; }
     const float kf = rintf(a * 0.63661977236758134308f);
     const int k = (int)kf;
     float r = fmaf(kf, -1.57079625129699707031f, a);      // pi/2 high part
@@ -76,6 +80,11 @@ __device__ __forceinline__ void sincos_small(float a, float& s, float& c) {
     const float s0 = (k & 1) ? pc : ps, c0 = (k & 1) ? ps : pc;
     s = (k & 2) ? -s0 : s0;
     c = ((k + 1) & 2) ? -c0 : c0;
+    if (RARE_BEHIND && __builtin_expect(__builtin_amdgcn_ballot_w64(a > 1.0e3f) != 0, 0)) {
+        const float sl = sinf(a), cl = cosf(a);
+        s = a > 1.0e3f ? sl : s;
+        c = a > 1.0e3f ? cl : c;
+    }
 }
 
 // Rodrigues' formula exactly as smplx.lbs.batch_rodrigues evaluates it
@@ -87,13 +96,14 @@ struct Rodrigues {
     float angle, inv_angle, s, c;
 };
 
+template <bool RARE_BEHIND = false>
 __device__ __forceinline__ Rodrigues rodrigues_fwd(Vec3 th) {
     Rodrigues o;
     const float ex = th.x + 1e-8f, ey = th.y + 1e-8f, ez = th.z + 1e-8f;
     o.angle = fast_sqrt(ex * ex + ey * ey + ez * ez);
     o.inv_angle = fast_rcp(o.angle);
     o.u = {th.x * o.inv_angle, th.y * o.inv_angle, th.z * o.inv_angle};
-    sincos_small(o.angle, o.s, o.c);
+    sincos_small<RARE_BEHIND>(o.angle, o.s, o.c);
     const float omc = 1.0f - o.c;
     const float ux = o.u.x, uy = o.u.y, uz = o.u.z;
     // K K = u u^T - (u.u) I restricted to what the matrix product gives

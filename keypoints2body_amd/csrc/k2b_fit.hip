@@ -641,7 +641,9 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             }
             dj = {e[0], e[1], e[2]};
         }
-        const Rodrigues rod = rodrigues_fwd(th);           // (beyond the tree th is zero: thoff)
+        // (beyond the tree th is zero: thoff.  The rare path of sin / cos behind the fast one: J(beta) above and the polynomial
+        //  share a basic block)
+        const Rodrigues rod = rodrigues_fwd<true>(th);
         // ---- pointer-doubling down-sweep: after round r a lane is composed with 2^(r+1) ancestors ----
         Mat3 Rg = rod.R;                   // becomes the global rotation
         Vec3 pj = dj;                      // becomes the posed joint (without transl)
@@ -1220,22 +1222,29 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 swap32(pq0, pq1);                      // pq1: lanes kq < 32 receive the value of lane 32 + kq (frame 1)
                 lossp[0] = add_rounded(lossp[0], hq == 0 ? cqQ * dQ * dQ : 0.f);
                 lossp[1] = add_rounded(lossp[1], hq == 0 ? pq1 : 0.f);
+                // (the lanes' sums do not wait for the trees: in front of the barrier)
+                lossp[0] = wave_sum_fast(lossp[0]);
+                lossp[1] = wave_sum_fast(lossp[1]);
             }
+            const float inv_bc2 = fast_rcp(co.y);      // (nor does the Adam coefficient's reciprocal)
             K2B_FSTAMP(6);
             __syncthreads();
             K2B_FSTAMP(7);
             // ---- joint gradient from the tree waves, Adam ------------------------------------------------------------------------
-            const float inv_bc2 = fast_rcp(co.y);
+            // (the three gradient reads requested back to back, in front of everything that uses one; a second slot beyond the
+            //  workgroup's frames is a strip inside the slot array that nobody wrote, and its value is dropped)
+            const float* const gs_r0 = slots + slot0 * SLOT + XS;
+            const float gj[2] = {gs_r0[offA], gs_r0[SLOT + offA]};
+            const float gjq = xsQ[XS + offQ];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 if (slot0 + h >= F) continue;
-                const float* gs_r = slots + (slot0 + h) * SLOT + XS;
-                const float g = optA ? gs_r[offA] + gpa[h] : 0.f;
-                if (last) { g0o[h] = g; losso[h] = frame_loss(wave_sum_fast(lossp[h]), wpp2, bestv[h], gs_r[XS - 1]); }
+                const float g = optA ? gj[h] + gpa[h] : 0.f;
+                if (last) { g0o[h] = g; losso[h] = frame_loss(lossp[h], wpp2, bestv[h], gs_r0[h * SLOT + XS - 1]); }
                 adam_update(xa[h], ma[h], va[h], g, co, inv_bc2, om_b1, a.beta2, om_b2, a.eps);
             }
             {
-                const float g = (optQ && rowQ) ? xsQ[XS + offQ] + gpq : 0.f;
+                const float g = (optQ && rowQ) ? gjq + gpq : 0.f;
                 if (last) gqo = g;
                 adam_update(xq, mq, vq, g, co, inv_bc2, om_b1, a.beta2, om_b2, a.eps);
             }
