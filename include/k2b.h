@@ -125,6 +125,15 @@ void k2b_prior_destroy(k2b_prior *prior);
  *   body_fitting_loss_3d                  (core/losses.py:24-38)
  *   torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8)  (world_space.py:249)
  * k2b_fit_config_default() fills the values the reference's world fitter uses.
+ * Adam numbers: step_size >= 0 and 0 <= beta < 1 as in torch.  adam_eps: its float32 rounding must be a normal positive
+ * number (1.17549435e-38 .. 3.4e38); every Adam entry (k2b_fit_world, k2b_fit_sequence, k2b_fit_sequences,
+ * k2b_adam_step) returns K2B_ERR_INVALID_ARGUMENT for a negative value, NaN, 0 or a float32 denormal.  torch accepts 0;
+ * here the update of a parameter with gradient 0 - one outside the optimiser, say - would be 0 * rcp(0) = NaN.  The
+ * L-BFGS entries pass the config through the same checks.  Known deviation from torch: the fit entries form the first
+ * moment as m + (1 - beta1)(g - m) for every beta1; torch's lerp switches to g - (g - m) beta1 from 1 - beta1 = 0.5 on.
+ * For adam_beta1 <= 0.5 the two differ by an ulp of max(|m|, |g|) per step, which can lose a gradient that collapses by
+ * orders of magnitude within one iteration; k2b_adam_step follows torch in both forms.  (tests/test_gpu_adam.py;
+ * DESIGN.md 1.1.)
  * ------------------------------------------------------------------------------- */
 typedef struct k2b_fit_config {
     int32_t num_iters;          /* num_iters_first if seq_ind == 0 else num_iters_followup */
@@ -448,7 +457,9 @@ int k2b_debug_lbfgs_step(int32_t num_frames, int32_t pose_dim, int32_t num_betas
  *   conf dev [E_sel] or NULL.  At most 32 selected joints per call.
  * k2b_adam_step: torch.optim.Adam single-tensor update of n floats for step t = 1, 2, ...
  *   (bias corrections formed in double like the fused kernel's table); m, v are the caller's
- *   state buffers (zero before the first step).
+ *   state buffers (zero before the first step).  eps as k2b_fit_config::adam_eps: a normal positive float32, else
+ *   K2B_ERR_INVALID_ARGUMENT.  The first moment follows both forms of torch's lerp (from 1 - beta1 = 0.5 on:
+ *   g - (g - m) beta1), so beta1 = 0 gives m = g exactly.
  * ------------------------------------------------------------------------------- */
 int k2b_vertex_term(const k2b_model *model, int32_t num_frames, int32_t num_selected,
                     const int32_t *extra_index, const float *targets, const float *conf,

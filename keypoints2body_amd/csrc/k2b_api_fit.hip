@@ -20,6 +20,8 @@ int validate_call(const k2b_model* model, const k2b_fit_config* cfg, const FitCa
     if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: num_iters=%d", cfg->num_iters);
     if (!(cfg->step_size >= 0.0) || !(cfg->adam_beta1 >= 0.0 && cfg->adam_beta1 < 1.0) || !(cfg->adam_beta2 >= 0.0 && cfg->adam_beta2 < 1.0))
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: bad Adam hyper-parameters");
+    if (!adam_eps_ok(cfg->adam_eps))
+        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: adam_eps=%g must round to a normal positive float32", cfg->adam_eps);
     if (c.B == 0) return K2B_OK;             // (nothing to fit: the callers return here)
     if (!c.j3d || !c.in.go || !c.in.bp || !c.in.be || !c.in.tr || !c.out.go || !c.out.bp || !c.out.be || !c.out.tr)
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: NULL parameter / target buffer (init transl is required, world_space.py:118-119)");

@@ -213,6 +213,7 @@ int k2b_surface_term(const k2b_model* model_c, int32_t B, int32_t T, const int32
 int k2b_adam_step(int64_t n, float* params, const float* grad, float* mbuf, float* vbuf, int32_t step, double step_size,
                   double beta1, double beta2, double eps, void* stream_v) {
     if (n < 0 || step < 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_adam_step: n=%lld step=%d", (long long)n, step);
+    if (!k2b::host::adam_eps_ok(eps)) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_adam_step: eps=%g must round to a normal positive float32", eps);
     if (n == 0) return K2B_OK;
     if (!params || !grad || !mbuf || !vbuf) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_adam_step: NULL buffer");
     const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);

@@ -194,6 +194,14 @@ struct __attribute__((visibility("hidden"))) k2b_ikgat {
 namespace k2b {
 namespace host __attribute__((visibility("hidden"))) {
 
+// Adam's eps as the kernels see it: its float32 rounding must be a normal positive number (k2b.h, k2b_fit_config).  With 0, a
+// negative value, NaN or a float32 denormal (flushed to 0) the update of a parameter with gradient 0 - one outside the
+// optimiser, say - is 0 * rcp(0) = NaN.  (NaN fails the first comparison.)
+inline bool adam_eps_ok(double eps) {
+    const float e = (float)eps;
+    return e >= 1.17549435e-38f && e <= 3.402823466e38f;
+}
+
 // ---- k2b_api_model.hip, k2b_api_prior.hip: per-handle tables built on first use ----------------------------------------------
 int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, float2** out);
 int folded_prior(k2b_prior* p, int Dv, const k2b_prior::Folded** out);

@@ -276,14 +276,19 @@ __global__ __launch_bounds__(64) void k2b_vertex_term_kernel(const VertexTermArg
     }
 }
 
-// torch.optim.Adam single-tensor step on a flat parameter block (same arithmetic as the fused kernel's)
+// torch.optim.Adam single-tensor step on a flat parameter block.  The same formulas as the fit kernels' updates, not the same
+// bits: adam_update (k2b_fit.hip) pins its fused operations, this kernel and the two Adam tails leave the contraction to the
+// compiler.  The first moment follows torch's lerp in both of its forms: from a weight 1 - beta1 of 0.5 on it is
+// g - (g - m) (1 - w), which keeps a small g behind a large m (beta1 = 0: m = g exactly) where m + w (g - m) loses it.  The fit
+// kernels keep the one form m + w (g - m) for every beta1.
 __global__ __launch_bounds__(256) void k2b_adam_kernel(float* __restrict__ x, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, long long n, float lr_over_bc1, float sqrt_bc2,
                                                        float one_minus_beta1, float beta2, float one_minus_beta2, float eps) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
-    const float mi = m[i] + one_minus_beta1 * (gi - m[i]);
+    const float dm = gi - m[i];
+    const float mi = one_minus_beta1 < 0.5f ? m[i] + one_minus_beta1 * dm : gi - dm * (1.f - one_minus_beta1);
     const float vi = v[i] * beta2 + one_minus_beta2 * gi * gi;
     const float denom = fast_sqrt(vi) * fast_rcp(sqrt_bc2) + eps;
     m[i] = mi;

@@ -127,7 +127,8 @@ def fit_world_adam(model, prior: GMMPrior, global_orient, body_pose, betas, tran
                    conf=None, *, num_iters: int, lr: float = 1e-2, seq_ind: int = 0,
                    model_idx: Optional[Sequence[int]] = None, target_idx: Optional[Sequence[int]] = None,
                    weights: Optional[FitWeights] = None, freeze_betas: bool = False,
-                   trace_iters: Sequence[int] = (), record_all_losses: bool = False) -> FitOutput:
+                   trace_iters: Sequence[int] = (), record_all_losses: bool = False,
+                   adam_betas: tuple = (0.9, 0.999), adam_eps: float = 1e-8) -> FitOutput:
     """Adam branch of ``WorldSpaceFitter.fit_frame`` for a batch of B frames.
 
     The loss is a sum over frames with no cross-frame term (losses.py:67) and Adam
@@ -155,7 +156,7 @@ def fit_world_adam(model, prior: GMMPrior, global_orient, body_pose, betas, tran
                             prior, conf[target_idx], w, preserve_on=seq_ind > 0)
 
     params = [go, bp, tr] + ([] if freeze_betas else [be])   # world_space.py:215-229
-    opt = torch.optim.Adam(params, lr=lr, betas=(0.9, 0.999))
+    opt = torch.optim.Adam(params, lr=lr, betas=adam_betas, eps=adam_eps)
     trace = FitTrace() if (trace_iters or record_all_losses) else None
     last = None
     for it in range(1, num_iters + 1):
@@ -190,7 +191,8 @@ SMPLH_FIELDS = ("global_orient", "body_pose", "transl", "left_hand_pose", "right
 
 def fit_world_adam_smplx(model, prior: GMMPrior, params: dict, j3d, conf=None, *, num_iters: int, lr: float = 1e-2,
                          seq_ind: int = 0, model_idx: Optional[Sequence[int]] = None, weights: Optional[FitWeights] = None,
-                         freeze_betas: bool = False, trace_iters: Sequence[int] = (), fields: Sequence[str] = ()):
+                         freeze_betas: bool = False, trace_iters: Sequence[int] = (), fields: Sequence[str] = (),
+                         adam_betas: tuple = (0.9, 0.999), adam_eps: float = 1e-8):
     """Adam branch of ``WorldSpaceFitter.fit_frame`` for ``SMPLXData`` inputs (world_space.py:126-151: hands, expression,
     jaw and eyes join the optimiser; 173-192: they are passed to the model; 202-212: the loss sees ``body_pose`` (63-D,
     prior zero-padded to the mixture's 69 dimensions - see ``GMMPrior.per_component``), ``betas`` (not the expression)
@@ -210,7 +212,7 @@ def fit_world_adam_smplx(model, prior: GMMPrior, params: dict, j3d, conf=None, *
         return frame_losses(p["body_pose"], preserve, p["betas"], out.joints[:, idx, :], j3d, prior, conf, w,
                             preserve_on=seq_ind > 0)
 
-    opt = torch.optim.Adam([v for k, v in p.items() if v.requires_grad], lr=lr, betas=(0.9, 0.999))
+    opt = torch.optim.Adam([v for k, v in p.items() if v.requires_grad], lr=lr, betas=adam_betas, eps=adam_eps)
     last, trace = None, {}
     for it in range(1, num_iters + 1):
         opt.zero_grad()
@@ -257,7 +259,8 @@ def camera_stage1_loss(model_joints, cam_t, cam_t_est, j3d, depth_loss_weight=10
 def fit_camera_adam_one(model, prior: GMMPrior, global_orient, body_pose, betas, j3d, conf=None, *, num_iters: int,
                         lr: float = 1e-2, seq_ind: int = 0, freeze_betas: bool = False,
                         weights: Optional[FitWeights] = None, model_idx: Optional[Sequence[int]] = None,
-                        init_cam_t: Optional[torch.Tensor] = None) -> FitOutput:
+                        init_cam_t: Optional[torch.Tensor] = None, adam_betas: tuple = (0.9, 0.999),
+                        adam_eps: float = 1e-8) -> FitOutput:
     """Both Adam stages for ONE frame (all tensors have a leading dimension of 1)."""
     w = weights or FitWeights()
     go = global_orient.clone().detach()
@@ -276,7 +279,7 @@ def fit_camera_adam_one(model, prior: GMMPrior, global_orient, body_pose, betas,
 
     go.requires_grad_(True)
     cam_t.requires_grad_(True)
-    opt = torch.optim.Adam([go, cam_t], lr=lr, betas=(0.9, 0.999))
+    opt = torch.optim.Adam([go, cam_t], lr=lr, betas=adam_betas, eps=adam_eps)
     for _ in range(num_iters):                                   # stage 1: camera_space.py:183-213
         joints = model(global_orient=go, body_pose=bp, betas=be).joints
         loss = camera_stage1_loss(joints[:, idx], cam_t, t0, j3d)
@@ -289,7 +292,7 @@ def fit_camera_adam_one(model, prior: GMMPrior, global_orient, body_pose, betas,
     opt_betas = seq_ind == 0 or not freeze_betas                 # camera_space.py:219-224
     be.requires_grad_(opt_betas)
     params = [bp] + ([be] if opt_betas else []) + [go, cam_t]
-    opt = torch.optim.Adam(params, lr=lr, betas=(0.9, 0.999))
+    opt = torch.optim.Adam(params, lr=lr, betas=adam_betas, eps=adam_eps)
     for _ in range(num_iters):                                   # stage 2: camera_space.py:268-298
         joints = model(global_orient=go, body_pose=bp, betas=be).joints
         loss = frame_losses(bp, preserve, be, joints[:, idx] + cam_t, j3d, prior, conf, w,
