@@ -28,7 +28,7 @@
  *     workspaces (one workspace per handle: serialise calls on one handle);
  *   - frames are independent, non-finite inputs included: in every entry with a frame or
  *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
- *     k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
+ *     k2b_fit_image_sequences, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
  *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term) each output of a frame (in the chain
  *     entries and the shape pass: of a sequence; inside a chain a frame also never depends on
  *     a LATER frame) depends only on that frame's own inputs, bit for bit, even when another
@@ -173,8 +173,8 @@ typedef struct k2b_fit_config {
     int32_t prior_pose_dims;
     int32_t num_betas_prior;
     /* K2B_SINCE(1, 7).  Joint term in image space: 0 = off (the 3D term above, the default); 1 = perspective reprojection
-     * (k2b_fit_world only).  The target buffer keeps its [B][K][3] layout; row k holds (u - cx, v - cy, ignored): pixel
-     * coordinates WITH THE PRINCIPAL POINT ALREADY SUBTRACTED by the caller (in float64, before the rounding to float32:
+     * (k2b_fit_world, and the chains of k2b_fit_image_sequences).  The target buffer keeps its [B][K][3] layout; row k holds
+     * (u - cx, v - cy, ignored): pixel coordinates WITH THE PRINCIPAL POINT ALREADY SUBTRACTED by the caller (in float64, before the rounding to float32:
      * raw pixel coordinates of a few hundred lose more in that rounding than the gradient tests allow).  For
      * every targeted joint, with (X, Y, Z) = p_k + transl (transl = the camera translation, as in the camera-space fitter):
      *     e_x = fx X / Z - u',   e_y = fy Y / Z - v'
@@ -183,8 +183,9 @@ typedef struct k2b_fit_config {
      * Z is divided by as it stands (no clamp): a joint behind the camera (Z < 0) is legal and finite; a targeted joint of
      * non-zero confidence at Z = 0 makes THAT frame's loss and gradient non-finite and no other frame's (Conventions); a joint
      * without a target, or with confidence 0, contributes exactly nothing whatever its depth.
-     * Kinematic targets only (a surface target: K2B_ERR_UNSUPPORTED), Adam and independent frames only (every other fit
-     * entry refuses projection != 0 with K2B_ERR_UNSUPPORTED, as does a model created under K2B_FIT_SCAN64=1).
+     * Kinematic targets only (a surface target: K2B_ERR_UNSUPPORTED), Adam only; independent frames here, warm-start chains
+     * through k2b_fit_image_sequences (every other fit entry refuses projection != 0 with K2B_ERR_UNSUPPORTED, as does a
+     * model created under K2B_FIT_SCAN64=1).
      * The term has NO counterpart in the reference (api/frame.py:71-75 raises for joints2d): it is defined here and held to
      * a float64 oracle of this formula, not to reference outputs. */
     int32_t projection;
@@ -344,6 +345,38 @@ int k2b_fit_sequences(const k2b_model *model, const k2b_prior *prior, const k2b_
  * The arguments are checked as the entries check them. */
 int k2b_sequence_order(int32_t num_sequences, const int32_t *lengths, const int32_t *offsets, int32_t *order_out,
                        int32_t *num_slots);
+
+/* ---------------------------------------------------------------------------------
+ * k2b_fit_image_sequences (ABI 1.8) — warm-start chains over 2D keypoints: k2b_fit_sequences' chain under the projected
+ * joint term of k2b_fit_config::projection, S ragged videos side by side in ONE launch (S = 1: the single video).
+ * Argument conventions as k2b_fit_sequences (packed rows, host lengths / offsets, *_in one row per sequence, loss_out may
+ * be NULL), plus followup_freeze_betas.
+ *   keypoints dev [sum T][K][3]: rows (u - cx, v - cy, ignored), centred pixels as for k2b_fit_world under projection
+ *   conf      dev [K], or [sum T][K] with cfg->conf_per_frame; NULL = ones
+ *   transl_*  the camera translation
+ * cfg->projection must be 1 and cfg->focal finite and positive (else K2B_ERR_INVALID_ARGUMENT: 3D targets have
+ * k2b_fit_sequences).  Step 0 of a sequence is k2b_fit_world under `cfg`: cfg->num_iters iterations, no preserve term.  Step
+ * t > 0 starts from step t - 1's RESULT, preserves that result's body pose with cfg->pose_preserve_weight, runs
+ * followup_iters iterations with a fresh Adam state and, with followup_freeze_betas != 0, holds the shape as
+ * cfg->freeze_betas = 1 would (a video's shape is estimated on its first frame: 24-joint models hold all betas, SMPL-H /
+ * SMPL-X the first num_betas_prior coefficients - the expression stays free); cfg->freeze_betas itself applies to every
+ * step, step 0 included.  A sequence of length 1 is the first-frame fit; a sequence of length 0 writes nothing.  loss_out is
+ * every frame's last-iteration loss before its step, preserve term included.
+ * A sequence's rows are bit-identical to the same sequence fitted alone, and to a host loop of k2b_fit_world calls that
+ * hands each result on (tests/test_gpu_reproj_chain.py).  A non-finite keypoint stays in its own SEQUENCE: the frames before
+ * it are untouched, the frame itself and the frames behind it in that sequence may be non-finite (a warm start inherits).
+ * Refused before anything is launched, outputs untouched: surface targets and a 24-joint model without a scan plan or created
+ * under K2B_FIT_SCAN64=1 (K2B_ERR_UNSUPPORTED); cfg->transl_prior_weight != 0, bad lengths / offsets, bad followup_iters
+ * (K2B_ERR_INVALID_ARGUMENT).  Adam only.
+ * ------------------------------------------------------------------------------- */
+int k2b_fit_image_sequences(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                            int32_t num_sequences, const int32_t *lengths, const int32_t *offsets, int32_t followup_iters,
+                            int32_t followup_freeze_betas, int32_t num_targets, const int32_t *model_joint_index,
+                            const float *keypoints, const float *conf,
+                            const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                            const float *transl_in,
+                            float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                            float *loss_out, void *stream) K2B_SINCE(1, 8);
 
 /* ---------------------------------------------------------------------------------
  * k2b_shape_pass_lbfgs (ABI 1.3) — the shape pre-pass of many sequences together (reference core/shape.py:10-115,

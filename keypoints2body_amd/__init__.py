@@ -5,7 +5,7 @@ Drop-in for the hot path of ``keypoints2body`` (per-frame Adam fitting of SMPL p
 through the C ABI in ``include/k2b.h``.  There is no CPU fallback.
 """
 from .api.frame import optimize_params_frame
-from .api.image import optimize_params_frame_2d
+from .api.image import optimize_params_frame_2d, optimize_params_sequence_2d, optimize_params_sequences_2d
 from .api.sequence import SequenceBatch, optimize_params_sequence, optimize_params_sequences, optimize_shape_sequence
 from .models.smpl_data import (BodyModelFitResult, BodyModelParams, FLAMEData, MANOData, SMPLData, SMPLHData,
                                SMPLXData)
@@ -14,6 +14,6 @@ __version__ = "0.1.0"
 
 __all__ = [
     "__version__", "optimize_params_frame", "optimize_params_frame_2d", "optimize_params_sequence", "optimize_params_sequences", "SequenceBatch",
-    "optimize_shape_sequence",
+    "optimize_shape_sequence", "optimize_params_sequence_2d", "optimize_params_sequences_2d",
     "BodyModelFitResult", "BodyModelParams", "MANOData", "FLAMEData", "SMPLData", "SMPLHData", "SMPLXData",
 ]

@@ -1,4 +1,5 @@
-"""``optimize_params_frame_2d``: fit one frame of 2D keypoints under a pinhole camera, executed on the HIP engine.
+"""``optimize_params_frame_2d`` / ``optimize_params_sequence_2d`` / ``optimize_params_sequences_2d``: fit one frame, one video or
+many videos of 2D keypoints under a pinhole camera, executed on the HIP engine.
 
 The reference has no counterpart (its ``api/frame.py:71-75`` raises for ``input_type="joints2d"``, and so do this package's
 existing entry points: ``common.check_request`` is untouched).  The capability is this function of its own; what it computes is
@@ -10,12 +11,13 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..core.config import FrameOptimizeConfig, ModelType, frame_config_from
+from ..core.config import FrameOptimizeConfig, ModelType, SequenceOptimizeConfig, frame_config_from, sequence_config_from
 from ..core.engine import default_init_params, load_mean_pose_shape, upgrade_smpl_family_init_params
 from ..core.fitters.image_space import ImageSpaceFitter
 from ..core.joints.adapters import resolve_adapter
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams
 from . import common
+from .sequence import SequenceBatch, _batched_results, _stack_starts
 
 
 def _keypoints_and_conf(keypoints2d, conf):
@@ -76,3 +78,126 @@ def optimize_params_frame_2d(keypoints2d, *, focal, principal_point, conf=None, 
     return fitter.fit_frame(init_params, uv[None], focal, principal_point, cf, seq_ind=0, target_model_indices=target_model_indices,
                             sigma=sigma, joint_loss_weight=joint_loss_weight, pose_preserve_weight=frame_cfg.pose_preserve_weight,
                             freeze_betas=frame_cfg.freeze_betas)
+
+
+def _sequence_keypoints(keypoints_seq):
+    """(T,K,2) or (T,K,3) [u, v, confidence] -> float64 (T,K,2), float32 (T,K) per-frame confidences."""
+    kp = keypoints_seq.detach().cpu().numpy() if isinstance(keypoints_seq, torch.Tensor) else np.asarray(keypoints_seq)
+    if kp.ndim != 3 or kp.shape[2] not in (2, 3):
+        raise ValueError(f"Expected a keypoint sequence of shape (T,K,2) or (T,K,3), got {tuple(kp.shape)}")
+    conf = kp[..., 2] if kp.shape[2] == 3 else np.ones(kp.shape[:2])
+    return kp[..., :2].astype(np.float64), conf.astype(np.float32)
+
+
+def _fit_videos(seqs, focal, principal_point, body_model, model, config, init_params, joint_layout, target_model_indices, sigma,
+                joint_loss_weight, device, pose_prior, mean_params, want_vertices=True):
+    """The shared body of the two video entry points: ``(fitter, one start per sequence, params, joints, vertices, loss,
+    lengths)`` with the results packed over all frames."""
+    device = common.resolve_device(device)
+    seq_cfg = sequence_config_from(config) if config is not None else SequenceOptimizeConfig(frame=FrameOptimizeConfig(use_lbfgs=False))
+    frame_cfg = seq_cfg.frame
+    if body_model not in common.SMPL_FAMILY:
+        raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
+    S = len(seqs)
+    if init_params is not None and (not isinstance(init_params, (list, tuple)) or len(init_params) != S):
+        raise ValueError("init_params must be None or a list with one start per sequence")
+    uvs, cfs = zip(*(_sequence_keypoints(k) for k in seqs))
+    if len({u.shape[1] for u in uvs}) != 1:
+        raise ValueError("every sequence must have the same number of keypoints")
+    if seq_cfg.limit_frames is not None and seq_cfg.limit_frames > 0:
+        uvs, cfs = [u[: seq_cfg.limit_frames] for u in uvs], [c[: seq_cfg.limit_frames] for c in cfs]
+    uv, cf = np.concatenate(uvs, axis=0), np.concatenate(cfs, axis=0)
+    lengths = np.asarray([u.shape[0] for u in uvs], dtype=np.int32)
+    if target_model_indices is None:
+        ad = resolve_adapter(uv.shape[1], joint_layout)
+        if ad.rotate_osim_to_smpl or ad.out_layout not in ("SMPL24", "AMASS"):
+            raise ValueError(f"joint_layout={joint_layout!r} is defined for 3D joints only")
+        if ad.mapping is not None:
+            uv, cf = uv[:, list(ad.mapping)], cf[:, list(ad.mapping)]
+        category = ad.out_layout
+    else:
+        category = "GENERIC"
+    model = common.obtain_model(model, body_model, device)
+    fitter = ImageSpaceFitter(model, step_size=frame_cfg.step_size, num_iters=frame_cfg.num_iters, use_lbfgs=frame_cfg.use_lbfgs,
+                              joints_category=category, device=device, pose_prior_num_gaussians=frame_cfg.pose_prior_num_gaussians,
+                              pose_prior=pose_prior, num_iters_followup=frame_cfg.num_iters_followup)
+    if init_params is None:
+        mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(common.DEFAULT_MEAN_FILE, device)
+        base = default_init_params(mean_pose.to(device), mean_shape.to(device), None, model, joints_category=category,
+                                   coordinate_mode="camera")
+        starts = [upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)] * S
+    else:
+        for p in init_params:
+            common.check_param_type(p, body_model, "init_params")
+        starts = [p.to(device) for p in init_params]
+    kw = dict(target_model_indices=target_model_indices, sigma=sigma, joint_loss_weight=joint_loss_weight, want_vertices=want_vertices,
+              pose_preserve_weight=frame_cfg.pose_preserve_weight, freeze_betas=frame_cfg.freeze_betas)
+    if seq_cfg.use_previous_frame_init or len(uv) == 0:
+        out, joints, verts, loss = fitter.fit_sequences(_stack_starts(starts, device), uv, lengths, focal, principal_point, cf, **kw)
+    else:                                       # independent frames: both stages for every frame, each from its sequence's start
+        rows = _stack_starts([starts[s] for s in range(S) for _ in range(int(lengths[s]))], device)
+        out, joints, verts, loss = fitter.fit_batch(rows, uv, focal, principal_point, cf, seq_ind=0, per_frame_conf=True, **kw)
+    return fitter, starts, out, joints, verts, loss, lengths
+
+
+class _FitterResults:
+    """What ``sequence._batched_results`` reads of an estimator."""
+
+    def __init__(self, fitter):
+        self.fitter = fitter
+
+
+def optimize_params_sequence_2d(keypoints_seq, *, focal, principal_point, body_model: ModelType = "smpl", model=None,
+                                config: Optional[SequenceOptimizeConfig | dict] = None, init_params: Optional[BodyModelParams] = None,
+                                joint_layout: Optional[str] = None, target_model_indices=None, sigma: float = 100.0,
+                                joint_loss_weight: float = 1.0, device=None, pose_prior=None,
+                                mean_params: Optional[tuple] = None) -> list[BodyModelFitResult]:
+    """Fit a video of 2D keypoints, ``keypoints_seq`` (T,K,2) pixels or (T,K,3) with a confidence column, as ONE warm-start
+    chain on the device (stage 1 for the first frame, then one ``k2b_fit_image_sequences`` launch for all frames); results in
+    temporal order, frame 0's parameters equal to ``optimize_params_frame_2d`` on that frame.
+
+    ``config`` is a ``SequenceOptimizeConfig`` or dict (without one: Adam, the defaults): ``frame.num_iters`` iterations for
+    stage 1 and for a video's first frame, ``frame.num_iters_followup`` for every later frame, ``frame.step_size``, ``frame.pose_preserve_weight``,
+    ``frame.freeze_betas`` (the frames after the first hold the first frame's shape); ``frame.use_lbfgs=True`` raises, as for the
+    frame entry.  ``use_shape_optimization`` is IGNORED: there is no 2D shape pre-pass, the first frame estimates the shape.
+    With ``use_previous_frame_init=False`` every frame is an independent two-stage fit from its sequence's start
+    (``ImageSpaceFitter.fit_batch``).  ``limit_frames`` applies.  A third keypoint column is a per-frame confidence.  The other
+    arguments are ``optimize_params_frame_2d``'s.  Each result's ``loss`` is the chain's own: the loss of the frame's last iteration
+    before its step, preserve term included (``ImageSpaceFitter.fit_sequences``), not the frame entry's re-evaluated loss."""
+    fitter, starts, out, joints, verts, loss, lengths = _fit_videos(
+        [keypoints_seq], focal, principal_point, body_model, model, config, None if init_params is None else [init_params],
+        joint_layout, target_model_indices, sigma, joint_loss_weight, device, pose_prior, mean_params)
+    return _batched_results(_FitterResults(fitter), out, joints, verts, loss, starts[0], int(lengths[0]))
+
+
+def optimize_params_sequences_2d(keypoints_seqs, *, focal, principal_point, body_model: ModelType = "smpl", model=None,
+                                 config: Optional[SequenceOptimizeConfig | dict] = None, init_params: Optional[list] = None,
+                                 joint_layout: Optional[str] = None, target_model_indices=None, sigma: float = 100.0,
+                                 joint_loss_weight: float = 1.0, device=None, pose_prior=None,
+                                 mean_params: Optional[tuple] = None) -> SequenceBatch:
+    """``optimize_params_sequence_2d`` for many videos of different lengths side by side (one camera): stage 1 for all first
+    frames in one launch, all chains in ONE ``k2b_fit_image_sequences`` launch; a packed ``SequenceBatch`` whose sequence s
+    equals the single call on it bit for bit.  ``init_params``: None or one start (one row) per video; ``config`` and everything
+    else as ``optimize_params_sequence_2d`` (``use_shape_optimization`` ignored, ``use_lbfgs=True`` refused, independent frames with
+    ``use_previous_frame_init=False``, a third keypoint column as per-frame confidence, the chain's own loss)."""
+    if not isinstance(keypoints_seqs, (list, tuple)):
+        raise TypeError("keypoints_seqs must be a list of sequences")
+    if len(keypoints_seqs) == 0:
+        raise ValueError("keypoints_seqs is empty")
+    fitter, starts, out, joints, _, loss, lengths = _fit_videos(
+        list(keypoints_seqs), focal, principal_point, body_model, model, config, init_params, joint_layout, target_model_indices,
+        sigma, joint_loss_weight, device, pose_prior, mean_params, want_vertices=False)
+    from ..native import ragged_offsets
+    offsets = ragged_offsets(lengths)
+    ref = fitter.result_params(out, starts[0])            # reference layout (SMPL-H / SMPL-X: hands and face unpacked)
+    params = {k: getattr(ref, k) for k in ("global_orient", "body_pose", "betas", "transl")}
+
+    def result_fn(s):
+        n, o = int(lengths[s]), int(offsets[s])
+        if n == 0:
+            return []
+        part = {k: v[o:o + n].contiguous() for k, v in out.items()}
+        j, v = fitter.final_forward(part)
+        return _batched_results(_FitterResults(fitter), part, j, v, part["loss"], starts[s], n)
+
+    return SequenceBatch(params=params, joints=joints, loss=loss, lengths=lengths, offsets=offsets, _result_fn=result_fn)

@@ -24,11 +24,17 @@ to float32 (a pixel coordinate is a few hundred times its residual; DESIGN.md 4.
 * result: ``transl`` = the camera translation, model-space joints / vertices from the usual final forward (no translation
   applied), ``loss`` = stage 2's loss re-evaluated at the result without the preserve term (one evaluate-only launch).
 
+Videos (``fit_sequences``): S ragged sequences of keypoints as warm-start chains - stage 1 for the S first frames as one launch,
+then the whole of stage 2 for every frame of every sequence as ONE launch (``k2b_fit_image_sequences``): a sequence's first frame
+is stage 2 as above, every later frame starts from its predecessor's result, preserves that result's body pose and, with
+``freeze_betas``, holds the shape the first frame estimated.
+
 Adam only: the device L-BFGS entries refuse the projected term (``K2B_ERR_UNSUPPORTED``), so ``use_lbfgs=True`` raises.
 Kinematic targets only (model index below the joint count): surface targets keep their 3D term.
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -38,6 +44,7 @@ from ... import native
 from ...models.body_model import check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData
 from ...prior import MaxMixturePrior
+from ..config import FrameOptimizeConfig
 from ..constants import JOINT_MAP, TORSO_JOINTS
 from .common import FitterBase
 from .world_space import WorldSpaceFitter
@@ -91,7 +98,8 @@ class ImageSpaceFitter(FitterBase):
     result_params = WorldSpaceFitter.result_params
 
     def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=False, joints_category="AMASS", device=None,
-                 pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None):
+                 pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None,
+                 num_iters_followup=FrameOptimizeConfig.num_iters_followup):
         if use_lbfgs:
             raise NotImplementedError("ImageSpaceFitter runs Adam only: the device L-BFGS entries (k2b_fit_world_lbfgs and the "
                                       "sequence entries) refuse the projected joint term; pass use_lbfgs=False")
@@ -99,6 +107,7 @@ class ImageSpaceFitter(FitterBase):
         if self.smpl.num_joints not in (24, 52, 55):
             raise NotImplementedError(f"a body model with {self.smpl.num_joints} joints: the fit kernels are built for 24, 52 and 55")
         self.num_iters = num_iters
+        self.num_iters_followup = num_iters_followup      # iterations of a video's frames after its first (fit_sequences)
 
     def stage_configs(self, focal, seq_ind=0, sigma=100.0, joint_loss_weight=1.0, pose_preserve_weight=5.0, freeze_betas=True,
                       depth_weight=100.0):
@@ -130,16 +139,14 @@ class ImageSpaceFitter(FitterBase):
             be = self._dev(init_params.betas, self.smpl.num_betas)
         return go, bp, be
 
-    def fit_batch(self, init_params: SMPLData, keypoints2d, focal, principal_point=(0.0, 0.0), conf=None, seq_ind: int = 0,
-                  target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
-                  pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
-                  init_cam_t=None, per_frame_conf: bool = False, want_vertices: bool = True, run_forward: bool = True):
-        """Both stages for B independent frames: ``(params dict of (B, .) tensors - ``transl`` = the camera translation -,
-        joints, vertices, per-frame loss)``.  `keypoints2d` (B, K, 2) in pixels, in the order of this fitter's joint category
-        or of `target_model_indices`; `focal` a number or ``(fx, fy)``; `conf` (K,) or, with `per_frame_conf`, (B, K)."""
+    def _prepare(self, init_params, keypoints2d, first_rows, focal, principal_point, conf, target_model_indices, per_frame_conf,
+                 init_cam_t):
+        """What both stages read: ``(fx, fy, centred targets, confidences, model joint per target, stage 1's torso targets, start
+        rows, initial camera translation)``.  `first_rows` (None: every frame) names the frames the start rows belong to: a
+        video's first frames, which alone get an initial translation and stage 1."""
         fx, fy = focal_pair(focal)
         targets = torch.from_numpy(centred_keypoints(keypoints2d, principal_point))
-        B = targets.shape[0]
+        B = targets.shape[0] if first_rows is None else len(first_rows)
         go, bp, be = self._start_rows(init_params)
         if not (go.shape[0] == bp.shape[0] == be.shape[0] == B):
             raise ValueError("init_params and keypoints2d disagree on the number of frames")
@@ -157,13 +164,25 @@ class ImageSpaceFitter(FitterBase):
         if missing:
             raise ValueError(f"the torso joints {missing} are not among the targets: the initial translation and stage 1 need all four")
         torso_cols = torch.tensor([model_idx.index(j) for j in _TORSO_IDX], dtype=torch.int64, device=self.device)
-        torso_tgt = targets.index_select(1, torso_cols).contiguous()
+        firsts = targets if first_rows is None else targets.index_select(
+            0, torch.as_tensor(np.asarray(first_rows, dtype=np.int64), device=self.device))
+        torso_tgt = firsts.index_select(1, torso_cols).contiguous()
         if init_cam_t is None:
             joints0 = self.smpl.native.lbs(go, bp, be, None, want_vertices=False)[0]
             cam_t0 = guess_init_2d(joints0, torso_tgt, (fx, fy), torch.tensor(_TORSO_IDX, dtype=torch.int64, device=self.device))
         else:
             cam_t0 = self._dev(init_cam_t, 3)
-        cam_t0 = cam_t0.detach().contiguous()
+        return fx, fy, targets, cf, model_idx, torso_tgt, (go, bp, be), cam_t0.detach().contiguous()
+
+    def fit_batch(self, init_params: SMPLData, keypoints2d, focal, principal_point=(0.0, 0.0), conf=None, seq_ind: int = 0,
+                  target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
+                  pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
+                  init_cam_t=None, per_frame_conf: bool = False, want_vertices: bool = True, run_forward: bool = True):
+        """Both stages for B independent frames: ``(params dict of (B, .) tensors - ``transl`` = the camera translation -,
+        joints, vertices, per-frame loss)``.  `keypoints2d` (B, K, 2) in pixels, in the order of this fitter's joint category
+        or of `target_model_indices`; `focal` a number or ``(fx, fy)``; `conf` (K,) or, with `per_frame_conf`, (B, K)."""
+        fx, fy, targets, cf, model_idx, torso_tgt, (go, bp, be), cam_t0 = self._prepare(
+            init_params, keypoints2d, None, focal, principal_point, conf, target_model_indices, per_frame_conf, init_cam_t)
 
         cfg1, cfg2, _ = self.stage_configs((fx, fy), seq_ind, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight)
         prior_target = cam_t0 if cfg1.transl_prior_weight != 0.0 else None
@@ -179,6 +198,62 @@ class ImageSpaceFitter(FitterBase):
         out["loss"] = fit(cfg2, model_idx, targets, cf, out)["loss"]
         self.last_init_cam_t = cam_t0
         return self._result(out, run_forward, want_vertices)
+
+    def fit_sequences(self, init_params: SMPLData, keypoints2d, lengths, focal, principal_point=(0.0, 0.0), conf=None,
+                      target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
+                      pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
+                      want_vertices: bool = True, run_forward: bool = True):
+        """S videos as warm-start chains: `init_params` one start row per sequence, `keypoints2d` packed (sum T, K, 2) pixels,
+        `lengths` (S,) frames per sequence (0: an empty sequence, whose start row is not read), `conf` None, (K,) or one row per
+        frame (sum T, K).  Three fit launches whatever S and T: the initial translation of the S first frames by ``guess_init_2d``
+        and stage 1 over them exactly as ``fit_batch`` runs it, then ONE ``k2b_fit_image_sequences`` launch under stage 2's
+        configuration of ``stage_configs(seq_ind=0)``: a sequence's first frame gets ``num_iters`` iterations and no preserve
+        term (so it equals ``fit_batch`` on that frame alone), every later frame starts from its predecessor's result, preserves
+        that result's body pose with `pose_preserve_weight`, runs ``num_iters_followup`` iterations with a fresh optimiser and,
+        with `freeze_betas`, holds the shape (SMPL-H / SMPL-X: the betas; the expression stays free).
+
+        Returns ``fit_batch``'s ``(params, joints, vertices, loss)`` over the sum T packed rows.  ``loss`` is the chain's own: a
+        frame's loss at its LAST iteration, before that iteration's step, preserve term included - the convention of the 3D
+        chains - and not ``fit_frame``'s loss re-evaluated at the result without the preserve term."""
+        L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if (L < 0).any():
+            raise ValueError("lengths must not be negative")
+        n = int(keypoints2d.shape[0])
+        if int(L.sum()) != n:
+            raise ValueError(f"lengths sum to {int(L.sum())}, keypoints2d has {n} frames")
+        live = np.flatnonzero(L > 0)
+        offsets = np.concatenate(([0], np.cumsum(L)[:-1])) if L.size else L
+        if conf is not None and torch.as_tensor(conf).dim() == 2 and torch.as_tensor(conf).shape[0] != n:
+            raise ValueError("conf must be (K,) or one row per frame")
+        if live.size == 0:                                            # no frame at all: zero rows of the right widths
+            return self._result(native._fit_outputs(self.smpl.native, (0,)), run_forward, want_vertices)
+        fx, fy, targets, cf, model_idx, torso_tgt, (go, bp, be), cam_t0 = self._prepare(
+            self._rows_of(init_params, live, L.size), keypoints2d, offsets[live], focal, principal_point, conf, target_model_indices,
+            True, None)
+        cfg1, cfg2, _ = self.stage_configs((fx, fy), 0, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight)
+        cfg2.pose_preserve_weight = float(pose_preserve_weight)       # (the chain leaves it out of a sequence's first frame itself)
+        cfg2.conf_per_frame = int(cf is not None and cf.dim() == 2)
+        s1 = native.fit_world(self.smpl.native, self.pose_prior.native, cfg1, _TORSO_IDX, torso_tgt, None, go, bp, be, cam_t0,
+                              transl_prior_target=cam_t0 if cfg1.transl_prior_weight != 0.0 else None)
+        out = native.fit_image_sequences(self.smpl.native, self.pose_prior.native, cfg2, int(self.num_iters_followup), bool(freeze_betas),
+                                         model_idx, L[live], targets, cf, s1["global_orient"], s1["body_pose"], s1["betas"], s1["transl"])
+        self.last_init_cam_t = cam_t0
+        return self._result(out, run_forward, want_vertices)
+
+    @staticmethod
+    def _rows_of(params, rows, count):
+        """The parameter rows `rows` of `params` (every array field; the data class kept)."""
+        sel, fields = torch.as_tensor(rows, dtype=torch.int64), {}
+        for f in dataclasses.fields(params):
+            v = getattr(params, f.name)
+            if f.name == "metadata" or v is None or isinstance(v, (dict, str)):
+                continue
+            t = torch.as_tensor(v, dtype=torch.float32)
+            t = t.unsqueeze(0) if t.dim() <= 1 else t
+            if t.shape[0] != count:
+                raise ValueError(f"init_params.{f.name} has {t.shape[0]} rows for {count} sequences")
+            fields[f.name] = t.index_select(0, sel.to(t.device)).contiguous()
+        return dataclasses.replace(params, **fields)
 
     def final_forward(self, out, want_vertices=True):
         """Model-space joints / vertices: the camera translation is part of the parameters, not applied to the mesh."""

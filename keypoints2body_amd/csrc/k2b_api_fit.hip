@@ -67,13 +67,18 @@ int check_surface_targets(const Targets& t, const FitCall& c, int J) {
     return K2B_OK;
 }
 // k2b_fit_config::projection: its values, and what the projected joint term is not built into
+int check_focal(const char* who, const k2b_fit_config* cfg) {
+    for (int i = 0; i < 2; ++i)
+        if (!(cfg->focal[i] > 0.0f) || !(cfg->focal[i] <= 3.402823466e38f))      // (NaN fails the first comparison)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: focal[%d]=%g must be finite and positive", who, i, (double)cfg->focal[i]);
+    return K2B_OK;
+}
 int check_projection(const k2b_fit_config* cfg, const FitCall& c) {
     if (cfg->projection == 0) return K2B_OK;
     if (cfg->projection != 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: projection=%d must be 0 or 1", cfg->projection);
-    for (int i = 0; i < 2; ++i)
-        if (!(cfg->focal[i] > 0.0f) || !(cfg->focal[i] <= 3.402823466e38f))      // (NaN fails the first comparison)
-            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: focal[%d]=%g must be finite and positive", i, (double)cfg->focal[i]);
-    if (c.chain.len > 1 || c.lbfgs.mode != k2b::LbMode::none)
+    if (const int rc = check_focal("k2b_fit_world", cfg); rc != K2B_OK) return rc;
+    // (a chain under projection is k2b_fit_image_sequences' alone: FitCall::Chain::image)
+    if ((c.chain.len > 1 && !c.chain.image) || c.lbfgs.mode != k2b::LbMode::none)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the projected joint term is built for independent frames under Adam only");
     return K2B_OK;
 }
@@ -114,6 +119,7 @@ void fill_call_fields(Args& a, const k2b_fit_config* cfg, const FitCall& c, cons
     a.chain_iters = c.chain.iters;
     a.chain_meta = c.chain.len > 1 ? c.chain.meta : nullptr;
     a.projection = cfg->projection; a.focal_x = cfg->focal[0]; a.focal_y = cfg->focal[1];
+    a.chain_freeze_shape = c.chain.len > 1 && c.chain.image && c.chain.freeze_shape ? 1 : 0;
 }
 
 // ---- surface targets: the Adam loop as pairs of launches ---------------------------------------------------------------------
@@ -477,6 +483,47 @@ int k2b_fit_sequences(const k2b_model* model, const k2b_prior* prior, const k2b_
     c.out = {go_out, bp_out, be_out, tr_out};
     c.loss_out = loss_out;
     c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.iters = followup_iters; c.chain.meta = meta;
+    return fit_world_impl(model, prior, cfg, c);
+}
+
+// Warm-start chains over 2D keypoints (ABI 1.8): k2b_fit_sequences' chain with the projected joint term, the one entry that
+// lets a chain through check_projection (FitCall::Chain::image).  Every refusal comes before anything is queued.
+int k2b_fit_image_sequences(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                            const int32_t* lengths, const int32_t* offsets, int32_t followup_iters, int32_t followup_freeze_betas,
+                            int32_t K, const int32_t* model_joint_index, const float* keypoints, const float* conf,
+                            const float* go_in, const float* bp_in, const float* be_in, const float* tr_in, float* go_out,
+                            float* bp_out, float* be_out, float* tr_out, float* loss_out, void* stream_v) {
+    const char* who = "k2b_fit_image_sequences";
+    RaggedSlots r;
+    if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
+    if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (cfg->projection != 1)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: projection=%d must be 1 (3D targets: k2b_fit_sequences)", who, cfg->projection);
+    if (const int rc = check_focal(who, cfg); rc != K2B_OK) return rc;
+    if (followup_iters < 1 || followup_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
+    if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_iters=%d", who, cfg->num_iters);
+    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
+    if (const int rc = check_targets(who, model, K, model_joint_index); rc != K2B_OK) return rc;
+    if (!kinematic_only(model, K, model_joint_index))
+        return fail(K2B_ERR_UNSUPPORTED, "%s: surface targets (vertex-selected joints, landmarks) keep the 3D term and are not built "
+                    "into the chain", who);
+    if (fused_eligibility(model, prior, cfg).fused && model->fit_scan64)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term is built for the fp32 scans only (this model has no scan plan, or "
+                    "was created under K2B_FIT_SCAN64)", who);
+    if (r.slots == 0) return K2B_OK;
+    if (!keypoints || !go_in || !bp_in || !be_in || !tr_in || !go_out || !bp_out || !be_out || !tr_out)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    hipStream_t stream = (hipStream_t)stream_v;
+    StreamWorkspace ws(stream);
+    HIP_TRY(ws.alloc(r.meta.size() * sizeof(int)));
+    int* meta = reinterpret_cast<int*>(ws.get());
+    if (const int rc = upload_slots(r.meta, meta, stream); rc != K2B_OK) return rc;
+    FitCall c = fit_call(r.slots, K, model_joint_index, keypoints, conf, stream_v);
+    c.in = {go_in, bp_in, be_in, tr_in};
+    c.out = {go_out, bp_out, be_out, tr_out};
+    c.loss_out = loss_out;
+    c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.iters = followup_iters; c.chain.meta = meta;
+    c.chain.image = true; c.chain.freeze_shape = followup_freeze_betas != 0;
     return fit_world_impl(model, prior, cfg, c);
 }
 

@@ -343,7 +343,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     const int pB = bodyB ? 3 + NC + lane : (goB ? lane - NR : (betaB ? 3 + D + (lane - 8) : 3 + D + NB + (lane - 8 - NB)));
     // optimiser membership of this lane's parameters (k2b_fit_config.optimize_mask)
     const bool optA = (a.opt_mask >> 1) & 1;
-    const bool optB = actB && ((a.opt_mask >> (bodyB ? 1 : (goB ? 0 : (betaB ? 2 : 3)))) & 1);
+    bool optB = actB && ((a.opt_mask >> (bodyB ? 1 : (goB ? 0 : (betaB ? 2 : 3)))) & 1);     // (a projected chain's follow-up steps may drop the shape group)
 
     // rim of the prior: lane (gm = l >> 3, gs = l & 7) works on component gm, columns 8 gs .. 8 gs + 7;
     // lanes gs < 5 finish rim row 64 + gs of that component
@@ -1313,6 +1313,9 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 pr0[0] = x0[0];
                 if (bodyB) { pr1[0] = x1[0]; refB[0] = x1[0]; }
                 m0[0] = v0[0] = m1[0] = v1[0] = 0.f;
+                if constexpr (PROJ) {   // a video's shape is its first frame's: the follow-up steps hold the shape group (FitArgs::chain_freeze_shape)
+                    if (a.chain_freeze_shape) optB = optB && !betaB;
+                }
             }
             if constexpr (MODE == MODE_SPLIT_LBFGS) {
                 if (lb_loop && chain && do_row && f_valid[0] && c_act) {   // the frame's start point into ITS row of the parameter arrays:
@@ -1483,8 +1486,8 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
     const FitPlan plan = plan_fit_world(a_in.num_frames, a_in.num_cus, a_in.num_betas, a_in.scan64 != 0, a_in.force_shape, a_in.lb_mode,
                                         a_in.chain_len);
     if (!plan.ok) return hipErrorInvalidValue;       // lb_mode and the batch disagree: the caller asks lbfgs_scheme_for first
-    // the projected term is instantiated for fp32 scans, independent frames and Adam only (the entries refuse the rest by name)
-    if (a_in.projection && (a_in.scan64 || a_in.lb_mode != LbMode::none || a_in.chain_len > 1)) return hipErrorInvalidValue;
+    // the projected term is instantiated for fp32 scans and Adam only (the entries refuse the rest by name)
+    if (a_in.projection && (a_in.scan64 || a_in.lb_mode != LbMode::none)) return hipErrorInvalidValue;
     for (int i = 0; i < plan.num_launches; ++i) {
         const FitLaunch& l = plan.launch[i];
         FitArgs a = frame_range(a_in, l.first_frame, l.num_frames);

@@ -44,12 +44,11 @@ __device__ __forceinline__ double shfl64(double v, int src) { return bperm64(src
 
 // NSF = NS, the capacity for shape coefficients (betas | expression): 16, 20 or 32, or NS | kProjForm for the joint term's projected
 // form (k2b_fit_config::projection; as in k2b_fit.hip the form rides in the first argument, so that the 3D instantiations keep
-// their symbol names); CHAIN: warm-start chains (3D form only)
+// their symbol names); CHAIN: warm-start chains (the projected ones also read FitTreeArgs::chain_freeze_shape)
 template <int NSF, bool CHAIN>
 __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs a) {
     constexpr int NS = NSF & (kProjForm - 1);
     constexpr bool PROJ = (NSF & kProjForm) != 0;
-    static_assert(!(PROJ && CHAIN), "the projected form is built for independent frames");
     extern __shared__ __attribute__((aligned(16))) float tlds[];
     // [8][16][64] half8 A fragments (128 KiB) | [M][64] h | [M][64] b | [M][64] mu | [TW][64] theta_v fp32 |
     // [TW][hi 64 | lo 64] theta_v f16 | [TW][M][64] y' | [TW][M] q | [M] constants | [M] 1 / scale
@@ -217,7 +216,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     float mth[3] = {0.f, 0.f, 0.f}, vth[3] = {0.f, 0.f, 0.f}, msh = 0.f, vsh = 0.f, mtr = 0.f, vtr = 0.f;
     // which parameters the optimiser owns
     const bool opt_th = isJ && (joint == 0 ? (a.opt_mask & 1) : (a.opt_mask & 2));
-    const bool opt_sh = lane < NB && (a.opt_mask & 4) && !(a.freeze_betas && lane < a.num_betas_prior);
+    bool opt_sh = lane < NB && (a.opt_mask & 4) && !(a.freeze_betas && lane < a.num_betas_prior);
     const bool opt_tr = lane < 3 && (a.opt_mask & 8);
     // prior-layout constants (lane i = prior dimension i)
     const bool isP = lane < Dv;
@@ -256,6 +255,9 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
 #pragma unroll
         for (int c = 0; c < 3; ++c) mth[c] = vth[c] = 0.f;
         msh = vsh = mtr = vtr = 0.f;
+        if constexpr (PROJ) {                    // a video's shape is its first frame's: the follow-up steps hold it (the expression stays free)
+            if (a.chain_freeze_shape) opt_sh = opt_sh && lane >= a.num_betas_prior;
+        }
     }
     const bool use_gmm = wpp > 0.f;              // (uniform over the launch: the barriers below are taken by every wave or by none)
     const int cn = lane & 15, cg = lane >> 4;    // MFMA lane: column (frame slot of the workgroup) and k / row group
@@ -521,7 +523,7 @@ hipError_t launch_tree(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, h
 }
 template <int NS>
 hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
-    if (a.projection) return p.chain ? hipErrorInvalidValue : launch_tree<NS | kProjForm, false>(p, lds, a, stream);   // (the entry refuses chains by name)
+    if (a.projection) return p.chain ? launch_tree<NS | kProjForm, true>(p, lds, a, stream) : launch_tree<NS | kProjForm, false>(p, lds, a, stream);
     return p.chain ? launch_tree<NS, true>(p, lds, a, stream) : launch_tree<NS, false>(p, lds, a, stream);
 }
 

@@ -226,7 +226,9 @@ struct FitCall {
     float *loss_out = nullptr, *grad_out = nullptr;
     hipStream_t stream = nullptr;
     // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta)
-    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; } chain;
+    // image: set by k2b_fit_image_sequences alone - the chain runs under the projected joint term (every other entry's chain is
+    // refused there); freeze_shape: its steps > 0 hold the shape (FitArgs::chain_freeze_shape)
+    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool image = false, freeze_shape = false; } chain;
     // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
     struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
 };
@@ -248,7 +250,8 @@ hipError_t start_in_place(int B, int D, int NB, const ConstParams& in, const Par
 struct FusedEligibility { int prior_dims; bool fused; };
 FusedEligibility fused_eligibility(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg);
 bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx);
-// k2b_fit_config::projection is built into k2b_fit_world's Adam loop alone: the chain and L-BFGS entries refuse it by name
+// k2b_fit_config::projection is built into k2b_fit_world's Adam loop and k2b_fit_image_sequences' chain: the other chain entries
+// and the L-BFGS entries refuse it by name
 inline int refuse_projection(const char* who, const k2b_fit_config* cfg) {
     if (cfg && cfg->projection != 0)
         return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term (projection=%d) is built into k2b_fit_world only", who, cfg->projection);

@@ -90,6 +90,9 @@ struct FitArgs {
     // everything else: the 3D instantiations never read them, and their kernel-argument offsets stay what they were.
     int projection;
     float focal_x, focal_y;
+    // projected chains (k2b_fit_image_sequences): 1 = the steps > 0 of a chain hold the shape group as freeze_betas does (a video's
+    // shape is estimated on its first frame).  Last, and read by the projected instantiations only: every other argument keeps its offset.
+    int chain_freeze_shape;
 };
 
 hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
@@ -130,8 +133,9 @@ struct FitTreeArgs {
     const int* chain_meta;       // ragged chains: as FitArgs::chain_meta
     int comp_waves;             // set by launch_fit_tree: 4 = the mixture runs on four dedicated component waves (<= 4 frames per CU)
     int debug_shape;             // TreeShape (k2b_launch_plan.h): automatic = chosen by the batch size; plain / comp_waves force one (tests)
-    int projection;              // as FitArgs::projection, focal_x, focal_y (no chains)
+    int projection;              // as FitArgs::projection, focal_x, focal_y
     float focal_x, focal_y;
+    int chain_freeze_shape;      // as FitArgs::chain_freeze_shape: steps > 0 freeze the first num_betas_prior coefficients (the expression stays free)
 };
 hipError_t launch_fit_tree(const FitTreeArgs& a, int num_cus, hipStream_t stream);
 

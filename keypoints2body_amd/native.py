@@ -102,6 +102,7 @@ _PROTOTYPES = (
     ("k2b_debug_lbfgs_state_layout", C.c_int, (_i32, _i32, _i32) + (C.POINTER(_i64),) * 3 + (C.POINTER(_i32),) * 2),
     ("k2b_debug_lbfgs_step", C.c_int, (_i32, _i32, _i32) + (_vp,) * 6 + (_i32, _i32, _f64, _f64, _f64, _vp, _i64, _i32, _i32) + _STREAM),
     ("k2b_point_error", C.c_int, (_i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp) + _STREAM),
+    ("k2b_fit_image_sequences", C.c_int, _FIT_HEAD + (_i32, _vp, _vp, _i32, _i32) + _FIT_IN + _FIT_OUT + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -471,6 +472,17 @@ def fit_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, follo
     tensors in the caller's order.  Sequence s equals ``fit_sequence`` on it alone, bit for bit."""
     return _fit_sequences_call("k2b_fit_sequences", model, prior, cfg, (int(followup_iters),), model_joint_index, lengths,
                                offsets, j3d, conf, global_orient, body_pose, betas, transl)
+
+
+def fit_image_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int, followup_freeze_betas: bool,
+                        model_joint_index: Sequence[int], lengths, keypoints: torch.Tensor, conf: Optional[torch.Tensor],
+                        global_orient: torch.Tensor, body_pose: torch.Tensor, betas: torch.Tensor, transl: torch.Tensor, offsets=None):
+    """Warm-start chains over 2D keypoints (``k2b_fit_image_sequences``, ONE launch): ``fit_sequences`` under the projected joint
+    term.  ``cfg.projection`` must be 1; ``keypoints`` packed (sum T, K, 3) rows ``(u - cx, v - cy, ignored)``; ``transl`` is the
+    camera translation; with `followup_freeze_betas` the frames after a sequence's first hold its shape.  Returns the dict of
+    ``fit_sequences``."""
+    return _fit_sequences_call("k2b_fit_image_sequences", model, prior, cfg, (int(followup_iters), int(bool(followup_freeze_betas))),
+                               model_joint_index, lengths, offsets, keypoints, conf, global_orient, body_pose, betas, transl)
 
 
 def fit_sequences_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, first_iters: int, followup_iters: int,
