@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from ..core.config import BodyModelConfig, FrameOptimizeConfig
+from ..core.engine import default_init_params, load_mean_pose_shape, upgrade_smpl_family_init_params
 from ..core.joints.adapters import adapt_layout_and_conf
 from ..models.body_model import as_body_model
 from ..models.smpl_data import FLAMEData, MANOData, SMPLData, SMPLHData, SMPLXData
@@ -70,6 +71,16 @@ def obtain_model(model, body_model: str, device):
     if model is None:
         model = load_body_model(BodyModelConfig(model_type=body_model), device)
     return as_body_model(model, device=device)
+
+
+def default_start(model, body_model: str, category: str, coordinate_mode: str, first_frame, mean_params, device, betas=None):
+    """The start of a fit without given parameters: the mean pose and shape (`mean_params`, or the reference's file) - `betas`
+    in place of the mean shape after a shape pre-pass -, aligned to `first_frame` (1, K, 3; None in 2D) as the reference's
+    ``default_init_params`` does, in the data class of `body_model`."""
+    mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(DEFAULT_MEAN_FILE, device)
+    base = default_init_params(mean_pose.to(device), (mean_shape if betas is None else betas).to(device), first_frame, model,
+                               joints_category=category, coordinate_mode=coordinate_mode)
+    return upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)
 
 
 def check_param_type(params, body_model: str, name: str) -> None:

@@ -7,8 +7,7 @@ from typing import Optional
 import torch
 
 from ..core.config import FrameOptimizeConfig, ModelType, frame_config_from
-from ..core.engine import (OptimizeEngine, default_init_params, load_mean_pose_shape,
-                           upgrade_smpl_family_init_params)
+from ..core.engine import OptimizeEngine, default_init_params
 from ..core.joints.adapters import normalize_frame_observations
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams, SMPLData, SMPLHData, SMPLXData
 from . import common
@@ -61,12 +60,8 @@ def optimize_params_frame(joints, *, prev_params: Optional[BodyModelParams] = No
                             pose_prior=pose_prior)
 
     if prev_params is None:
-        mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(
-            common.DEFAULT_MEAN_FILE, device)
-        base = default_init_params(mean_pose.to(device), mean_shape.to(device), j3d, model,
-                                   joints_category=frame_cfg.joints_category,
-                                   coordinate_mode=frame_cfg.coordinate_mode)
-        init_params = upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)
+        init_params = common.default_start(model, body_model, frame_cfg.joints_category, frame_cfg.coordinate_mode, j3d,
+                                           mean_params, device)
     else:
         common.check_param_type(prev_params, body_model, "prev_params")
         init_params = prev_params.to(device)

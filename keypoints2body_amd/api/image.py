@@ -12,12 +12,11 @@ import numpy as np
 import torch
 
 from ..core.config import FrameOptimizeConfig, ModelType, SequenceOptimizeConfig, frame_config_from, sequence_config_from
-from ..core.engine import default_init_params, load_mean_pose_shape, upgrade_smpl_family_init_params
 from ..core.fitters.image_space import ImageSpaceFitter
 from ..core.joints.adapters import resolve_adapter
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams
 from . import common
-from .sequence import SequenceBatch, _batched_results, _stack_starts
+from .sequence import SequenceBatch, _batched_results, _packed_batch, _stack_starts
 
 
 def _keypoints_and_conf(keypoints2d, conf):
@@ -31,6 +30,33 @@ def _keypoints_and_conf(keypoints2d, conf):
     if conf.shape != (kp.shape[0],):
         raise ValueError(f"conf must be ({kp.shape[0]},), got {tuple(conf.shape)}")
     return kp[:, :2].astype(np.float64), conf.astype(np.float32)
+
+
+def _fitter_and_starts(uv, cf, frame_cfg, body_model, model, init_params, count, joint_layout, target_model_indices, device,
+                       pose_prior, mean_params):
+    """Keypoint layout -> ``(ImageSpaceFitter, `count` starts, keypoints and confidences in the fitter's joint order)``: `uv`
+    (..., K, 2) and `cf` (..., K) in the order `joint_layout` names (or that of `target_model_indices`), `init_params` None
+    (the mean pose and shape for every start) or a list of `count` given starts."""
+    if target_model_indices is None:
+        ad = resolve_adapter(uv.shape[-2], joint_layout)
+        if ad.rotate_osim_to_smpl or ad.out_layout not in ("SMPL24", "AMASS"):
+            raise ValueError(f"joint_layout={joint_layout!r} is defined for 3D joints only")
+        if ad.mapping is not None:
+            uv, cf = uv[..., list(ad.mapping), :], cf[..., list(ad.mapping)]
+        category = ad.out_layout
+    else:
+        category = "GENERIC"
+    model = common.obtain_model(model, body_model, device)
+    fitter = ImageSpaceFitter(model, step_size=frame_cfg.step_size, num_iters=frame_cfg.num_iters, use_lbfgs=frame_cfg.use_lbfgs,
+                              joints_category=category, device=device, pose_prior_num_gaussians=frame_cfg.pose_prior_num_gaussians,
+                              pose_prior=pose_prior, num_iters_followup=frame_cfg.num_iters_followup)
+    if init_params is None:
+        starts = [common.default_start(model, body_model, category, "camera", None, mean_params, device)] * count
+    else:
+        for p in init_params:
+            common.check_param_type(p, body_model, "init_params")
+        starts = [p.to(device) for p in init_params]
+    return fitter, starts, uv, cf
 
 
 def optimize_params_frame_2d(keypoints2d, *, focal, principal_point, conf=None, body_model: ModelType = "smpl", model=None,
@@ -54,27 +80,8 @@ def optimize_params_frame_2d(keypoints2d, *, focal, principal_point, conf=None, 
     if body_model not in common.SMPL_FAMILY:
         raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
     uv, cf = _keypoints_and_conf(keypoints2d, conf)
-    if target_model_indices is None:
-        ad = resolve_adapter(uv.shape[0], joint_layout)
-        if ad.rotate_osim_to_smpl or ad.out_layout not in ("SMPL24", "AMASS"):
-            raise ValueError(f"joint_layout={joint_layout!r} is defined for 3D joints only")
-        if ad.mapping is not None:
-            uv, cf = uv[list(ad.mapping)], cf[list(ad.mapping)]
-        category = ad.out_layout
-    else:
-        category = "GENERIC"
-    model = common.obtain_model(model, body_model, device)
-    fitter = ImageSpaceFitter(model, step_size=frame_cfg.step_size, num_iters=frame_cfg.num_iters, use_lbfgs=frame_cfg.use_lbfgs,
-                              joints_category=category, device=device, pose_prior_num_gaussians=frame_cfg.pose_prior_num_gaussians,
-                              pose_prior=pose_prior)
-    if init_params is None:
-        mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(common.DEFAULT_MEAN_FILE, device)
-        base = default_init_params(mean_pose.to(device), mean_shape.to(device), None, model, joints_category=category,
-                                   coordinate_mode="camera")
-        init_params = upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)
-    else:
-        common.check_param_type(init_params, body_model, "init_params")
-        init_params = init_params.to(device)
+    fitter, (init_params,), uv, cf = _fitter_and_starts(uv, cf, frame_cfg, body_model, model, None if init_params is None else [init_params],
+                                                        1, joint_layout, target_model_indices, device, pose_prior, mean_params)
     return fitter.fit_frame(init_params, uv[None], focal, principal_point, cf, seq_ind=0, target_model_indices=target_model_indices,
                             sigma=sigma, joint_loss_weight=joint_loss_weight, pose_preserve_weight=frame_cfg.pose_preserve_weight,
                             freeze_betas=frame_cfg.freeze_betas)
@@ -108,28 +115,8 @@ def _fit_videos(seqs, focal, principal_point, body_model, model, config, init_pa
         uvs, cfs = [u[: seq_cfg.limit_frames] for u in uvs], [c[: seq_cfg.limit_frames] for c in cfs]
     uv, cf = np.concatenate(uvs, axis=0), np.concatenate(cfs, axis=0)
     lengths = np.asarray([u.shape[0] for u in uvs], dtype=np.int32)
-    if target_model_indices is None:
-        ad = resolve_adapter(uv.shape[1], joint_layout)
-        if ad.rotate_osim_to_smpl or ad.out_layout not in ("SMPL24", "AMASS"):
-            raise ValueError(f"joint_layout={joint_layout!r} is defined for 3D joints only")
-        if ad.mapping is not None:
-            uv, cf = uv[:, list(ad.mapping)], cf[:, list(ad.mapping)]
-        category = ad.out_layout
-    else:
-        category = "GENERIC"
-    model = common.obtain_model(model, body_model, device)
-    fitter = ImageSpaceFitter(model, step_size=frame_cfg.step_size, num_iters=frame_cfg.num_iters, use_lbfgs=frame_cfg.use_lbfgs,
-                              joints_category=category, device=device, pose_prior_num_gaussians=frame_cfg.pose_prior_num_gaussians,
-                              pose_prior=pose_prior, num_iters_followup=frame_cfg.num_iters_followup)
-    if init_params is None:
-        mean_pose, mean_shape = mean_params if mean_params is not None else load_mean_pose_shape(common.DEFAULT_MEAN_FILE, device)
-        base = default_init_params(mean_pose.to(device), mean_shape.to(device), None, model, joints_category=category,
-                                   coordinate_mode="camera")
-        starts = [upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)] * S
-    else:
-        for p in init_params:
-            common.check_param_type(p, body_model, "init_params")
-        starts = [p.to(device) for p in init_params]
+    fitter, starts, uv, cf = _fitter_and_starts(uv, cf, frame_cfg, body_model, model, init_params, S, joint_layout, target_model_indices,
+                                                device, pose_prior, mean_params)
     kw = dict(target_model_indices=target_model_indices, sigma=sigma, joint_loss_weight=joint_loss_weight, want_vertices=want_vertices,
               pose_preserve_weight=frame_cfg.pose_preserve_weight, freeze_betas=frame_cfg.freeze_betas)
     if seq_cfg.use_previous_frame_init or len(uv) == 0:
@@ -138,13 +125,6 @@ def _fit_videos(seqs, focal, principal_point, body_model, model, config, init_pa
         rows = _stack_starts([starts[s] for s in range(S) for _ in range(int(lengths[s]))], device)
         out, joints, verts, loss = fitter.fit_batch(rows, uv, focal, principal_point, cf, seq_ind=0, per_frame_conf=True, **kw)
     return fitter, starts, out, joints, verts, loss, lengths
-
-
-class _FitterResults:
-    """What ``sequence._batched_results`` reads of an estimator."""
-
-    def __init__(self, fitter):
-        self.fitter = fitter
 
 
 def optimize_params_sequence_2d(keypoints_seq, *, focal, principal_point, body_model: ModelType = "smpl", model=None,
@@ -167,7 +147,7 @@ def optimize_params_sequence_2d(keypoints_seq, *, focal, principal_point, body_m
     fitter, starts, out, joints, verts, loss, lengths = _fit_videos(
         [keypoints_seq], focal, principal_point, body_model, model, config, None if init_params is None else [init_params],
         joint_layout, target_model_indices, sigma, joint_loss_weight, device, pose_prior, mean_params)
-    return _batched_results(_FitterResults(fitter), out, joints, verts, loss, starts[0], int(lengths[0]))
+    return _batched_results(fitter, out, joints, verts, loss, starts[0], int(lengths[0]))
 
 
 def optimize_params_sequences_2d(keypoints_seqs, *, focal, principal_point, body_model: ModelType = "smpl", model=None,
@@ -188,16 +168,4 @@ def optimize_params_sequences_2d(keypoints_seqs, *, focal, principal_point, body
         list(keypoints_seqs), focal, principal_point, body_model, model, config, init_params, joint_layout, target_model_indices,
         sigma, joint_loss_weight, device, pose_prior, mean_params, want_vertices=False)
     from ..native import ragged_offsets
-    offsets = ragged_offsets(lengths)
-    ref = fitter.result_params(out, starts[0])            # reference layout (SMPL-H / SMPL-X: hands and face unpacked)
-    params = {k: getattr(ref, k) for k in ("global_orient", "body_pose", "betas", "transl")}
-
-    def result_fn(s):
-        n, o = int(lengths[s]), int(offsets[s])
-        if n == 0:
-            return []
-        part = {k: v[o:o + n].contiguous() for k, v in out.items()}
-        j, v = fitter.final_forward(part)
-        return _batched_results(_FitterResults(fitter), part, j, v, part["loss"], starts[s], n)
-
-    return SequenceBatch(params=params, joints=joints, loss=loss, lengths=lengths, offsets=offsets, _result_fn=result_fn)
+    return _packed_batch(fitter, out, joints, loss, lengths, ragged_offsets(lengths), starts)

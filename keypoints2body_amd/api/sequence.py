@@ -31,7 +31,7 @@ from ..core.config import ModelType, SequenceOptimizeConfig, sequence_config_fro
 from ..core.engine import (OptimizeEngine, default_init_params, load_mean_pose_shape, optimize_shape_pass,
                            optimize_shape_pass_batched, upgrade_smpl_family_init_params)
 from ..core.joints.adapters import normalize_sequence_observations
-from ..models.smpl_data import BodyModelFitResult, BodyModelParams, SMPLData
+from ..models.smpl_data import BodyModelFitResult, BodyModelParams, SMPLData, param_rows
 from . import common
 from .frame import _with_root_aligned_transl, ikgat_init_params, ikgat_prev_params
 
@@ -127,20 +127,10 @@ def _preprocess_sequence(joints_seq, joint_layout, body_model, seq_cfg: Sequence
     return xyz, conf, model_indices
 
 
-def _param_rows(p: BodyModelParams):
-    """(name, 2-D float32 tensor) of every array field of a parameter object (metadata and absent fields skipped)."""
-    for f in dataclasses.fields(p):
-        v = getattr(p, f.name)
-        if f.name == "metadata" or v is None or isinstance(v, (dict, str)):
-            continue
-        t = torch.as_tensor(v, dtype=torch.float32)
-        yield f.name, (t.unsqueeze(0) if t.dim() <= 1 else t)
-
-
 def _repeat_params(p: BodyModelParams, n: int) -> BodyModelParams:
     """`p` (one row) as the start of n frames, every array field repeated and the data class kept - the reference hands
     `prev` itself (``SMPLHData`` / ``SMPLXData`` with hands, jaw, eyes, expression) to every frame (api/sequence.py:270-281)."""
-    return dataclasses.replace(p, **{k: t.expand(n, -1).contiguous() for k, t in _param_rows(p)})
+    return dataclasses.replace(p, **{k: t.expand(n, -1).contiguous() for k, t in param_rows(p)})
 
 
 def optimize_params_sequence(joints_seq, *, init_params: Optional[BodyModelParams] = None,
@@ -176,9 +166,8 @@ def optimize_params_sequence(joints_seq, *, init_params: Optional[BodyModelParam
         return []
 
     if init_params is None:
-        base = default_init_params(mean_pose, betas_opt, xyz[0:1], model, joints_category=frame_cfg.joints_category,
-                                   coordinate_mode=frame_cfg.coordinate_mode)
-        prev = upgrade_smpl_family_init_params(base, model_type=body_model, model=model, device=device)
+        prev = common.default_start(model, body_model, frame_cfg.joints_category, frame_cfg.coordinate_mode, xyz[0:1],
+                                    (mean_pose, mean_shape), device, betas=betas_opt)
     else:
         common.check_param_type(init_params, body_model, "init_params")
         prev = init_params.to(device)
@@ -193,7 +182,7 @@ def optimize_params_sequence(joints_seq, *, init_params: Optional[BodyModelParam
         if frame_cfg.coordinate_mode == "world" and prev.transl is None:
             prev = _with_root_aligned_transl(prev, xyz[0:1], model, frame_cfg, device)
         out, joints, verts, loss = est.fit_chain(prev, xyz, conf, model_indices)
-        return _batched_results(est, out, joints, verts, loss, prev, T)
+        return _batched_results(est.fitter, out, joints, verts, loss, prev, T)
     if seq_cfg.use_previous_frame_init or T == 1:
         for idx in range(T):
             frame = xyz[idx: idx + 1]
@@ -241,9 +230,9 @@ def _ikgat_sequence(xyz, init_params, body_model, model, seq_cfg, device) -> lis
     return [result_for(prev, quats[t], xyz[t: t + 1]) for t in range(T)]
 
 
-def _batched_results(est, out, joints, verts, loss, init, n) -> list[BodyModelFitResult]:
+def _batched_results(fitter, out, joints, verts, loss, init, n) -> list[BodyModelFitResult]:
     """Per-frame result objects (the data class the reference returns for the model / input type) of a batched fit."""
-    return [BodyModelFitResult(params=est.fitter.result_params(out, init, slice(i, i + 1)), vertices=verts[i: i + 1],
+    return [BodyModelFitResult(params=fitter.result_params(out, init, slice(i, i + 1)), vertices=verts[i: i + 1],
                                joints=joints[i: i + 1], loss=loss[i]) for i in range(n)]
 
 
@@ -316,9 +305,26 @@ def _batch_from_results(per_seq: list[list[BodyModelFitResult]], device) -> Sequ
                          _result_fn=lambda s: per_seq[s])
 
 
+def _packed_batch(fitter, out, joints, loss, lengths, offsets, starts) -> SequenceBatch:
+    """``SequenceBatch`` of a packed fit `out` over all frames: `starts` holds one start per sequence; ``results(s)`` cuts
+    sequence s out and runs the final forward for its vertices."""
+    ref = fitter.result_params(out, starts[0])                # reference layout (SMPL-H / SMPL-X: hands and face unpacked)
+    params = {k: getattr(ref, k) for k in ("global_orient", "body_pose", "betas", "transl")}
+
+    def result_fn(s):
+        n, o = int(lengths[s]), int(offsets[s])
+        if n == 0:
+            return []
+        part = {k: v[o:o + n].contiguous() for k, v in out.items()}
+        j, v = fitter.final_forward(part)
+        return _batched_results(fitter, part, j, v, part["loss"], starts[s], n)
+
+    return SequenceBatch(params=params, joints=joints, loss=loss, lengths=lengths, offsets=offsets, _result_fn=result_fn)
+
+
 def _stack_starts(starts: list[BodyModelParams], device) -> BodyModelParams:
     """One-row starts of the same data class -> one object with a row per start (kernel inputs of ``fit_chains``)."""
-    rows = [dict(_param_rows(p)) for p in starts]
+    rows = [dict(param_rows(p)) for p in starts]
     return dataclasses.replace(starts[0], **{k: torch.cat([r[k].to(device) for r in rows], dim=0).contiguous() for k in rows[0]})
 
 
@@ -430,26 +436,13 @@ def optimize_params_sequences(joints_seqs, *, init_params: Optional[list] = None
     j3d, lengths, offsets = pack_ragged(xs)
     conf = torch.cat(cs, dim=0).contiguous()
     # one start row per sequence (an empty sequence's row is never read: any live start stands in)
-    init_rows = _stack_starts([starts.get(s, starts[live[0]]) for s in range(S)], device)
+    starts = [starts.get(s, starts[live[0]]) for s in range(S)]
     try:
-        out = est.fit_chains(init_rows, j3d, conf, lengths, model_indices)
+        out = est.fit_chains(_stack_starts(starts, device), j3d, conf, lengths, model_indices)
     except NotImplementedError:                       # (L-BFGS on SMPL-H / SMPL-X): sequence by sequence
         return by_loop(model, pose_prior)
-    fitter = est.fitter
-    joints, _ = fitter.final_forward(out, want_vertices=False)
-    ref = fitter.result_params(out, starts[live[0]])          # reference layout (SMPL-H / SMPL-X: hands and face unpacked)
-    params = {k: getattr(ref, k) for k in ("global_orient", "body_pose", "betas", "transl")}
-
-    def result_fn(s):
-        n = int(lengths[s])
-        if n == 0:
-            return []
-        o = int(offsets[s])
-        part = {k: v[o:o + n].contiguous() for k, v in out.items()}
-        j, v = fitter.final_forward(part)
-        return _batched_results(est, part, j, v, part["loss"], starts[s], n)
-
-    return SequenceBatch(params=params, joints=joints, loss=out["loss"], lengths=lengths, offsets=offsets, _result_fn=result_fn)
+    joints, _ = est.fitter.final_forward(out, want_vertices=False)
+    return _packed_batch(est.fitter, out, joints, out["loss"], lengths, offsets, starts)
 
 
 def optimize_shape_sequence(joints_seq, *, body_model: ModelType = "smpl", joint_layout: Optional[str] = None,

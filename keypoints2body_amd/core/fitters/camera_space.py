@@ -40,11 +40,7 @@ from ... import native
 from ...models.body_model import check_target_indices
 from ...models.smpl_data import BodyModelFitResult, SMPLData
 from ...prior import MaxMixturePrior
-from ..constants import JOINT_MAP, TORSO_JOINTS
-from .common import FitterBase, torch_lbfgs
-
-_TORSO_IDX = [JOINT_MAP[name] for name in TORSO_JOINTS]     # same indices in the AMASS numbering
-_SQUARED_ERROR_SIGMA = 1.0e8                                # gmof(e, sigma) -> e^2 in fp32
+from .common import TORSO_IDX, FitterBase, stage1_config, stage2_config, torch_lbfgs
 
 
 def guess_init_3d(model_joints, j3d, joints_category="SMPL24", torso_index: Optional[torch.Tensor] = None,
@@ -56,13 +52,17 @@ def guess_init_3d(model_joints, j3d, joints_category="SMPL24", torso_index: Opti
     if joints_category not in ("SMPL24", "AMASS"):
         raise ValueError(f"Unknown joints category: {joints_category}")
     if torso_index is None:
-        return (j3d[:, _TORSO_IDX] - model_joints[:, _TORSO_IDX]).sum(dim=1) / 4.0
+        return (j3d[:, TORSO_IDX] - model_joints[:, TORSO_IDX]).sum(dim=1) / 4.0
     tgt = torso_targets if torso_targets is not None else j3d.index_select(1, torso_index)
     return (tgt - model_joints.index_select(1, torso_index)).sum(dim=1) / 4.0
 
 
 class CameraSpaceFitter(FitterBase):
     """Per-frame optimizer operating in camera coordinates, executed on one MI355X."""
+
+    # the start rows of a packed (SMPL-H / SMPL-X) model are taken in kernel layout as they come: camera mode is not built for
+    # those models (the tree kernel refuses the translation prior)
+    pack_starts = False
 
     def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=True, joints_category="SMPL24",
                  device=None, pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None):
@@ -77,17 +77,8 @@ class CameraSpaceFitter(FitterBase):
         plain squared error on the stage's joints (GMoF sigma -> inf, weight 1), depth prior ``depth_w^2 |t - t0|^2``
         (200 = the reference's 100 broadcast over the four torso joints, ``losses.py:91-93``), every other prior off.
         Stage 2 (``:215-298``): ``body_fitting_loss_3d``; betas optimised iff ``seq_ind == 0 or not freeze_betas``."""
-        cfg1 = native.default_fit_config()
-        cfg1.num_iters, cfg1.step_size = int(self.num_iters), float(self.step_size)
-        cfg1.sigma, cfg1.joint_loss_weight = _SQUARED_ERROR_SIGMA, 1.0
-        cfg1.pose_prior_weight = cfg1.angle_prior_weight = cfg1.shape_prior_weight = cfg1.pose_preserve_weight = 0.0
-        cfg1.optimize_mask, cfg1.transl_prior_weight = 9, float(depth_w)
-        cfg2 = native.default_fit_config()
-        cfg2.num_iters, cfg2.step_size = int(self.num_iters), float(self.step_size)
-        cfg2.joint_loss_weight = float(joint_loss_weight)
-        cfg2.pose_preserve_weight = float(pose_preserve_weight) if seq_ind > 0 else 0.0
-        fit_betas = seq_ind == 0 or not freeze_betas
-        cfg2.optimize_mask = 15 if fit_betas else 11
+        cfg1 = stage1_config(self.num_iters, self.step_size, depth_w)
+        cfg2, fit_betas = stage2_config(self.num_iters, self.step_size, seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas)
         return cfg1, cfg2, fit_betas
 
     def fit_batch(self, init_params: SMPLData, j3d: torch.Tensor, conf_3d: Optional[torch.Tensor] = None,
@@ -113,11 +104,6 @@ class CameraSpaceFitter(FitterBase):
         out["loss"] = self._loss_at(out, model_idx, targets, conf)
         return self._result(out, run_forward, want_vertices)
 
-    def _start_rows(self, init_params):
-        J = self.smpl.num_joints
-        return (self._dev(init_params.global_orient, 3), self._dev(init_params.body_pose, 3 * (J - 1)),
-                self._dev(init_params.betas, self.smpl.num_betas))
-
     def _device_index(self, idx) -> torch.Tensor:
         """`idx` as an int64 tensor on the device, uploaded once per index list."""
         cache = self.__dict__.setdefault("_index_cache", {})
@@ -131,10 +117,10 @@ class CameraSpaceFitter(FitterBase):
         four torso joints (``camera_space.py:183-198``) or, with caller-chosen indices, all of them (``:199-210``)."""
         model_idx, rows = self._target_selection(target_model_indices, j3d.shape[1])
         if target_model_indices is None:
-            torso = self._device_index(_TORSO_IDX)
+            torso = self._device_index(TORSO_IDX)
             return dict(custom=False, model_idx=model_idx,
                         targets=(j3d if rows is None else j3d.index_select(1, self._device_index(rows))).contiguous(),
-                        stage1_idx=_TORSO_IDX, stage1_tgt=j3d.index_select(1, torso).contiguous(), depth_w=200.0, torso=torso)
+                        stage1_idx=TORSO_IDX, stage1_tgt=j3d.index_select(1, torso).contiguous(), depth_w=200.0, torso=torso)
         check_target_indices(self.smpl, model_idx)
         targets = j3d.contiguous()
         return dict(custom=True, model_idx=model_idx, targets=targets, stage1_idx=model_idx, stage1_tgt=targets, depth_w=100.0,
@@ -163,28 +149,19 @@ class CameraSpaceFitter(FitterBase):
             cam_t0 = torch.as_tensor(init_cam_t, dtype=torch.float32).to(self.device)
         cam_t0 = cam_t0.detach().contiguous()
 
-        def fit(cfg, idx, tgt, cf, p):
-            # (vertex-selected joints among the targets are handled inside k2b_fit_world)
-            cur = (p["global_orient"], p["body_pose"], p["betas"], p["transl"])
-            cfg.conf_per_frame = int(cf is not None and cf.dim() == 2)
-            return native.fit_world(self.smpl.native, self.pose_prior.native, cfg, idx, tgt, cf, *cur,
-                                    transl_prior_target=cam_t0)
-
         cfg1, cfg2, fit_betas = self.stage_configs(seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas, tg["depth_w"])
         start = dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0)
         if self.use_lbfgs:
             return self._two_stages_lbfgs(cfg1, cfg2, fit_betas, stage1_idx, stage1_tgt, model_idx, targets, conf, start, cam_t0)
-        s1 = fit(cfg1, stage1_idx, stage1_tgt, None, start)
-        return fit(cfg2, model_idx, targets, conf, s1)
+        s1 = self._fit(cfg1, stage1_idx, stage1_tgt, None, start, transl_prior_target=cam_t0)
+        return self._fit(cfg2, model_idx, targets, conf, s1, transl_prior_target=cam_t0)
 
     def _loss_at(self, p, model_idx, targets, conf):
         """Loss at the fitted parameters: weight 600, no preserve term, no depth prior (``camera_space.py:316-326``) - one
         evaluate-only launch (one iteration with step size 0) over however many frames `p` holds."""
         cfg = native.default_fit_config()
         cfg.num_iters, cfg.step_size, cfg.joint_loss_weight = 1, 0.0, 600.0
-        cfg.conf_per_frame = int(conf is not None and conf.dim() == 2)
-        return native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, targets, conf, p["global_orient"],
-                                p["body_pose"], p["betas"], p["transl"])["loss"]
+        return self._fit(cfg, model_idx, targets, conf, p)["loss"]
 
     def chain_supported(self, target_model_indices=None) -> bool:
         """Any target set: the stages go through ``k2b_fit_world`` / ``k2b_fit_world_lbfgs`` frame by frame."""
@@ -235,9 +212,8 @@ class CameraSpaceFitter(FitterBase):
                   seq_ind: int = 0, target_model_indices: Optional[torch.Tensor] = None,
                   joint_loss_weight: float = 600.0, pose_preserve_weight: float = 5.0, freeze_betas: bool = True,
                   init_cam_t: Optional[torch.Tensor] = None) -> BodyModelFitResult:
-        out, joints, verts, loss = self.fit_batch(init_params, j3d, conf_3d, seq_ind, target_model_indices, joint_loss_weight,
-                                                  pose_preserve_weight, freeze_betas, init_cam_t=init_cam_t)
-        return BodyModelFitResult(params=self.result_params(out), vertices=verts, joints=joints, loss=loss.sum())
+        return self._frame_result(self.fit_batch(init_params, j3d, conf_3d, seq_ind, target_model_indices, joint_loss_weight,
+                                                 pose_preserve_weight, freeze_betas, init_cam_t=init_cam_t), init_params)
 
     # ------------------------------------------------------------------------------------------------
     def _two_stages_lbfgs(self, cfg1, cfg2, fit_betas, idx1, tgt1, idx2, tgt2, conf, start, cam_t0):
@@ -269,6 +245,7 @@ class CameraSpaceFitter(FitterBase):
 
             def run(cfg, idx, tgt, cfv, opt_keys):
                 tgt_f = tgt[sl].contiguous()
+                # (not through _fit: a frame's own (1, K) confidence row goes with the stage's conf_per_frame as it stands)
                 evaluate = lambda cur: native.fit_world(self.smpl.native, self.pose_prior.native, cfg, idx, tgt_f, cfv, *cur,
                                                         preserve_pose=pres_f, want_grad=True, transl_prior_target=cam_f)
                 torch_lbfgs(evaluate, p, opt_keys, cols, dev, max_iter, lr)

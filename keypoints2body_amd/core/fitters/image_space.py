@@ -34,24 +34,19 @@ Kinematic targets only (model index below the joint count): surface targets keep
 """
 from __future__ import annotations
 
-import dataclasses
 from typing import Optional
 
 import numpy as np
 import torch
 
 from ... import native
-from ...models.body_model import check_target_indices
-from ...models.smpl_data import BodyModelFitResult, SMPLData
+from ...models.smpl_data import BodyModelFitResult, SMPLData, select_rows
 from ...prior import MaxMixturePrior
 from ..config import FrameOptimizeConfig
-from ..constants import JOINT_MAP, TORSO_JOINTS
-from .common import FitterBase
-from .world_space import WorldSpaceFitter
+from ..constants import TORSO_JOINTS
+from .common import TORSO_IDX, FitterBase, stage1_config, stage2_config
 
-_TORSO_IDX = [JOINT_MAP[name] for name in TORSO_JOINTS]     # RHip, LHip, RShoulder, LShoulder: the same in every SMPL-family tree
-_TORSO_EDGES = ((0, 1), (2, 3), (0, 2), (1, 3))             # hips, shoulders, right side, left side
-_SQUARED_ERROR_SIGMA = 1.0e8                                # gmof(e, sigma) -> e^2 in fp32
+_TORSO_EDGES = ((0, 1), (2, 3), (0, 2), (1, 3))             # hips, shoulders, right side, left side (positions in TORSO_IDX)
 
 
 def centred_keypoints(keypoints2d, principal_point) -> np.ndarray:
@@ -92,11 +87,6 @@ def guess_init_2d(model_joints: torch.Tensor, torso_uv: torch.Tensor, focal: tup
 class ImageSpaceFitter(FitterBase):
     """Per-frame optimizer against 2D keypoints under a pinhole camera, executed on one MI355X."""
 
-    # SMPL-H / SMPL-X in kernel layout, and the data class of a result: the world fitter's, which read ``self.smpl`` alone
-    _pack = WorldSpaceFitter._pack
-    _packed_config = WorldSpaceFitter._packed_config
-    result_params = WorldSpaceFitter.result_params
-
     def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=False, joints_category="AMASS", device=None,
                  pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None,
                  num_iters_followup=FrameOptimizeConfig.num_iters_followup):
@@ -114,30 +104,17 @@ class ImageSpaceFitter(FitterBase):
         """Kernel configurations of the two stages, ``(cfg1, cfg2, fit_betas)`` (module docstring)."""
         fx, fy = focal_pair(focal)
         tree = self.smpl.num_joints != 24 or self.smpl.packed          # (no translation prior in the tree kernel)
-        cfg1 = native.default_fit_config()
-        cfg1.num_iters, cfg1.step_size = int(self.num_iters), float(self.step_size)
-        cfg1.sigma, cfg1.joint_loss_weight = _SQUARED_ERROR_SIGMA, 1.0
-        cfg1.pose_prior_weight = cfg1.angle_prior_weight = cfg1.shape_prior_weight = cfg1.pose_preserve_weight = 0.0
-        cfg1.optimize_mask, cfg1.transl_prior_weight = 9, 0.0 if tree else float(depth_weight)
-        cfg2 = native.default_fit_config()
-        cfg2.num_iters, cfg2.step_size = int(self.num_iters), float(self.step_size)
-        cfg2.sigma, cfg2.joint_loss_weight = float(sigma), float(joint_loss_weight)
-        cfg2.pose_preserve_weight = float(pose_preserve_weight) if seq_ind > 0 else 0.0
-        fit_betas = seq_ind == 0 or not freeze_betas
-        cfg2.optimize_mask = 15 if fit_betas else 11
+        cfg1 = stage1_config(self.num_iters, self.step_size, 0.0 if tree else depth_weight)
+        cfg2, fit_betas = stage2_config(self.num_iters, self.step_size, seq_ind, joint_loss_weight, pose_preserve_weight, freeze_betas,
+                                        float(sigma))
         for cfg in (cfg1, cfg2):
             cfg.projection, cfg.focal[0], cfg.focal[1] = 1, fx, fy
             self._packed_config(cfg)
         return cfg1, cfg2, fit_betas
 
-    def _start_rows(self, init_params):
-        go = self._dev(init_params.global_orient, 3)
-        if self.smpl.packed:
-            bp, be = self._pack(init_params, go.shape[0])
-        else:
-            bp = self._dev(init_params.body_pose, 3 * (self.smpl.num_joints - 1))
-            be = self._dev(init_params.betas, self.smpl.num_betas)
-        return go, bp, be
+    def _kinematic_only(self, model_idx):
+        if any(int(j) >= self.smpl.num_joints for j in model_idx):
+            raise NotImplementedError("projected surface targets (vertex-selected joints, landmarks) are not built: kinematic joints only")
 
     def _prepare(self, init_params, keypoints2d, first_rows, focal, principal_point, conf, target_model_indices, per_frame_conf,
                  init_cam_t):
@@ -148,28 +125,20 @@ class ImageSpaceFitter(FitterBase):
         targets = torch.from_numpy(centred_keypoints(keypoints2d, principal_point))
         B = targets.shape[0] if first_rows is None else len(first_rows)
         go, bp, be = self._start_rows(init_params)
-        if not (go.shape[0] == bp.shape[0] == be.shape[0] == B):
-            raise ValueError("init_params and keypoints2d disagree on the number of frames")
-        model_idx, rows = self._target_selection(target_model_indices, targets.shape[1])
-        if len(model_idx) != (targets.shape[1] if rows is None else len(rows)):
-            raise ValueError("target_model_indices must have one entry per keypoint")
-        check_target_indices(self.smpl, model_idx)
-        if any(int(j) >= self.smpl.num_joints for j in model_idx):
-            raise NotImplementedError("projected surface targets (vertex-selected joints, landmarks) are not built: kinematic joints only")
-        targets = (targets if rows is None else targets[:, rows]).to(self.device).contiguous()
-        cf = self._confidence(conf, per_frame_conf, rows)
+        model_idx, targets, cf = self._targets_and_conf(targets, target_model_indices, conf, per_frame_conf, (go, bp, be), B,
+                                                        names=("keypoints2d", "keypoint"), check_index=self._kinematic_only)
 
         # stage 1's targets: the four torso joints among the detections
-        missing = [TORSO_JOINTS[i] for i, j in enumerate(_TORSO_IDX) if j not in model_idx]
+        missing = [TORSO_JOINTS[i] for i, j in enumerate(TORSO_IDX) if j not in model_idx]
         if missing:
             raise ValueError(f"the torso joints {missing} are not among the targets: the initial translation and stage 1 need all four")
-        torso_cols = torch.tensor([model_idx.index(j) for j in _TORSO_IDX], dtype=torch.int64, device=self.device)
+        torso_cols = torch.tensor([model_idx.index(j) for j in TORSO_IDX], dtype=torch.int64, device=self.device)
         firsts = targets if first_rows is None else targets.index_select(
             0, torch.as_tensor(np.asarray(first_rows, dtype=np.int64), device=self.device))
         torso_tgt = firsts.index_select(1, torso_cols).contiguous()
         if init_cam_t is None:
             joints0 = self.smpl.native.lbs(go, bp, be, None, want_vertices=False)[0]
-            cam_t0 = guess_init_2d(joints0, torso_tgt, (fx, fy), torch.tensor(_TORSO_IDX, dtype=torch.int64, device=self.device))
+            cam_t0 = guess_init_2d(joints0, torso_tgt, (fx, fy), torch.tensor(TORSO_IDX, dtype=torch.int64, device=self.device))
         else:
             cam_t0 = self._dev(init_cam_t, 3)
         return fx, fy, targets, cf, model_idx, torso_tgt, (go, bp, be), cam_t0.detach().contiguous()
@@ -186,16 +155,13 @@ class ImageSpaceFitter(FitterBase):
 
         cfg1, cfg2, _ = self.stage_configs((fx, fy), seq_ind, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight)
         prior_target = cam_t0 if cfg1.transl_prior_weight != 0.0 else None
-        cfg2.conf_per_frame = int(cf is not None and cf.dim() == 2)
-        fit = lambda cfg, idx, tgt, c, p, centre=None: native.fit_world(
-            self.smpl.native, self.pose_prior.native, cfg, idx, tgt, c, p["global_orient"], p["body_pose"], p["betas"], p["transl"],
-            transl_prior_target=centre)
-        s1 = fit(cfg1, _TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0), prior_target)
-        s2 = fit(cfg2, model_idx, targets, cf, s1)
+        s1 = self._fit(cfg1, TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0),
+                       transl_prior_target=prior_target)
+        s2 = self._fit(cfg2, model_idx, targets, cf, s1)
         out = {k: s2[k] for k in native.PARAM_KEYS}
         # the loss at the result: stage 2's terms without the preserve term, one evaluate-only launch
         cfg2.num_iters, cfg2.step_size, cfg2.pose_preserve_weight = 1, 0.0, 0.0
-        out["loss"] = fit(cfg2, model_idx, targets, cf, out)["loss"]
+        out["loss"] = self._fit(cfg2, model_idx, targets, cf, out)["loss"]
         self.last_init_cam_t = cam_t0
         return self._result(out, run_forward, want_vertices)
 
@@ -228,32 +194,17 @@ class ImageSpaceFitter(FitterBase):
         if live.size == 0:                                            # no frame at all: zero rows of the right widths
             return self._result(native._fit_outputs(self.smpl.native, (0,)), run_forward, want_vertices)
         fx, fy, targets, cf, model_idx, torso_tgt, (go, bp, be), cam_t0 = self._prepare(
-            self._rows_of(init_params, live, L.size), keypoints2d, offsets[live], focal, principal_point, conf, target_model_indices,
+            select_rows(init_params, live, L.size), keypoints2d, offsets[live], focal, principal_point, conf, target_model_indices,
             True, None)
         cfg1, cfg2, _ = self.stage_configs((fx, fy), 0, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight)
         cfg2.pose_preserve_weight = float(pose_preserve_weight)       # (the chain leaves it out of a sequence's first frame itself)
         cfg2.conf_per_frame = int(cf is not None and cf.dim() == 2)
-        s1 = native.fit_world(self.smpl.native, self.pose_prior.native, cfg1, _TORSO_IDX, torso_tgt, None, go, bp, be, cam_t0,
-                              transl_prior_target=cam_t0 if cfg1.transl_prior_weight != 0.0 else None)
+        s1 = self._fit(cfg1, TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0),
+                       transl_prior_target=cam_t0 if cfg1.transl_prior_weight != 0.0 else None)
         out = native.fit_image_sequences(self.smpl.native, self.pose_prior.native, cfg2, int(self.num_iters_followup), bool(freeze_betas),
                                          model_idx, L[live], targets, cf, s1["global_orient"], s1["body_pose"], s1["betas"], s1["transl"])
         self.last_init_cam_t = cam_t0
         return self._result(out, run_forward, want_vertices)
-
-    @staticmethod
-    def _rows_of(params, rows, count):
-        """The parameter rows `rows` of `params` (every array field; the data class kept)."""
-        sel, fields = torch.as_tensor(rows, dtype=torch.int64), {}
-        for f in dataclasses.fields(params):
-            v = getattr(params, f.name)
-            if f.name == "metadata" or v is None or isinstance(v, (dict, str)):
-                continue
-            t = torch.as_tensor(v, dtype=torch.float32)
-            t = t.unsqueeze(0) if t.dim() <= 1 else t
-            if t.shape[0] != count:
-                raise ValueError(f"init_params.{f.name} has {t.shape[0]} rows for {count} sequences")
-            fields[f.name] = t.index_select(0, sel.to(t.device)).contiguous()
-        return dataclasses.replace(params, **fields)
 
     def final_forward(self, out, want_vertices=True):
         """Model-space joints / vertices: the camera translation is part of the parameters, not applied to the mesh."""
@@ -263,6 +214,6 @@ class ImageSpaceFitter(FitterBase):
                   target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
                   pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
                   init_cam_t=None) -> BodyModelFitResult:
-        out, joints, verts, loss = self.fit_batch(init_params, keypoints2d, focal, principal_point, conf, seq_ind, target_model_indices,
-                                                  sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight, init_cam_t)
-        return BodyModelFitResult(params=self.result_params(out, init_params), vertices=verts, joints=joints, loss=loss.sum())
+        return self._frame_result(self.fit_batch(init_params, keypoints2d, focal, principal_point, conf, seq_ind, target_model_indices,
+                                                 sigma, joint_loss_weight, pose_preserve_weight, freeze_betas, depth_weight, init_cam_t),
+                                  init_params)

@@ -38,15 +38,14 @@ Differences, all deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
-import dataclasses as _dc
 from typing import Optional
 
 import numpy as np
 import torch
 
 from ... import native
-from ...models.body_model import as_body_model, check_target_indices
-from ...models.smpl_data import BodyModelFitResult, SMPLData, SMPLHData, SMPLXData
+from ...models.body_model import as_body_model
+from ...models.smpl_data import BodyModelFitResult, SMPLData
 from ...prior import MaxMixturePrior
 from ..constants import root_indices
 from .common import FitterBase, split_params, torch_lbfgs, upload_params
@@ -96,20 +95,6 @@ class WorldSpaceFitter(FitterBase):
         cfg.pose_preserve_weight = float(pose_preserve_weight)      # frames >= 1 (frame 0 has no preserve term)
         return self._packed_config(cfg)
 
-    def _packed_config(self, cfg):
-        if self.smpl.packed:
-            cfg.prior_pose_dims = 3 * self.smpl.NUM_BODY_JOINTS       # 63: what the mixture, bending and preserve terms see
-            cfg.num_betas_prior = self.smpl.num_betas                 # 10: shape prior / freeze_betas leave the expression alone
-        return cfg
-
-    def _pack(self, init, B):
-        """SMPL-H / SMPL-X starts in kernel layout: one pose vector of all non-root joints, one of all shape coefficients."""
-        get = lambda name: getattr(init, name, None)
-        return (self.smpl.pack_pose(B, body_pose=init.body_pose, jaw_pose=get("jaw_pose"), leye_pose=get("leye_pose"),
-                                    reye_pose=get("reye_pose"), left_hand_pose=get("left_hand_pose"),
-                                    right_hand_pose=get("right_hand_pose")),
-                self.smpl.pack_shape(B, init.betas, get("expression")))
-
     def _prepare(self, init_params, j3d, conf_3d, target_model_indices, per_frame_conf, num_init=None):
         """Argument handling shared by ``fit_batch`` and ``fit_chain``: device tensors in kernel layout, the joint
         gather of world_space.py:194-201 and the confidence rules of world_space.py:163-164.  ``num_init``: expected
@@ -119,27 +104,11 @@ class WorldSpaceFitter(FitterBase):
         j3d = torch.as_tensor(j3d, dtype=torch.float32)
         if j3d.dim() != 3 or j3d.shape[2] != 3:
             raise ValueError(f"j3d must be (B,K,3), got {tuple(j3d.shape)}")
-        J = self.smpl.num_joints
-        B = j3d.shape[0]
-        go = self._dev(init_params.global_orient, 3)
-        if self.smpl.packed:                             # 52- / 55-joint trees (SMPL-H / SMPL-X)
-            bp, be = self._pack(init_params, go.shape[0])
-        else:
-            bp = self._dev(init_params.body_pose, 3 * (J - 1))
-            be = self._dev(init_params.betas, self.smpl.num_betas)
+        go, bp, be = self._start_rows(init_params)
         tr = self._dev(init_params.transl, 3)
-        if not (go.shape[0] == bp.shape[0] == be.shape[0] == tr.shape[0] == (B if num_init is None else num_init)):
-            raise ValueError("init_params and j3d disagree on the number of frames")
-
-        # joint gather (world_space.py:194-201): model joint per target, and the target rows.  AMASS / SMPL24 inputs arrive in
-        # target order: the gather is the identity (on a device tensor it would upload its index list per call)
-        model_idx, rows = self._target_selection(target_model_indices, j3d.shape[1])
-        if target_model_indices is not None:
-            if len(model_idx) != j3d.shape[1]:
-                raise ValueError("target_model_indices must have one entry per target joint")
-            check_target_indices(self.smpl, model_idx)
-        tgt = (j3d if rows is None else j3d[:, rows, :]).to(self.device).contiguous()
-        return go, bp, be, tr, model_idx, tgt, self._confidence(conf_3d, per_frame_conf, rows)
+        model_idx, tgt, conf = self._targets_and_conf(j3d, target_model_indices, conf_3d, per_frame_conf, (go, bp, be, tr),
+                                                      j3d.shape[0] if num_init is None else num_init)
+        return go, bp, be, tr, model_idx, tgt, conf
 
     def fit_batch(self, init_params: SMPLData, j3d, conf_3d=None, seq_ind: int = 0, target_model_indices=None,
                   joint_loss_weight: float = 600.0, pose_preserve_weight: float = 5.0, freeze_betas: bool = False,
@@ -156,7 +125,7 @@ class WorldSpaceFitter(FitterBase):
         if self.use_lbfgs:
             out = self._fit_lbfgs(cfg, model_idx, tgt, conf, go, bp, be, tr, freeze_betas)
         else:
-            out = native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt, conf, go, bp, be, tr)
+            out = self._fit(cfg, model_idx, tgt, conf, dict(global_orient=go, body_pose=bp, betas=be, transl=tr))
         return self._result(out, run_forward, want_vertices)
 
     def _target_index(self, target_model_indices):
@@ -232,19 +201,13 @@ class WorldSpaceFitter(FitterBase):
         return native.fit_sequences(self.smpl.native, self.pose_prior.native, cfg, int(self.num_iters_followup), model_idx,
                                     lengths, tgt, conf, go, bp, be, tr)
 
-    def packed_init(self, init):
-        """Kernel layout of SMPL-X parameters: ``body_pose`` = all 162 non-root joint values, ``betas`` = betas | expression."""
-        body_pose, betas = self._pack(init, init.global_orient.shape[0])
-        return SMPLData(global_orient=init.global_orient, transl=init.transl, body_pose=body_pose, betas=betas)
-
     def fit_params(self, cfg, targets, init, model_idx=None):
         """The hot call alone: ONE fused-fit launch on device tensors that are already in kernel layout
         (`targets` (B,K,3) in the order of this fitter's joint category or of `model_idx`, `init` on the device, packed
         for SMPL-X).  `bench.py` times this + `final_forward`; `fit_batch` is the same two calls behind the reference's
         argument handling."""
         idx = list(self.smpl_index) if model_idx is None else list(model_idx)
-        return native.fit_world(self.smpl.native, self.pose_prior.native, cfg, idx, targets, None,
-                                init.global_orient, init.body_pose, init.betas, init.transl)
+        return self._fit(cfg, idx, targets, None, vars(init))        # (the data class's own field dict: nothing is built)
 
     def final_forward(self, out, want_vertices=True):
         """Final no-grad forward of the reference (world_space.py:258-278): joints (+ vertices) of fitted parameters."""
@@ -280,8 +243,8 @@ class WorldSpaceFitter(FitterBase):
         opt_keys = ["global_orient", "body_pose", "transl"] + (["betas"] if not freeze_betas or self.smpl.packed else [])
         cols = native.param_columns(bp.shape[1], be.shape[1])
         p = {k: t.detach().to("cpu").clone() for k, t in zip(native.PARAM_KEYS, (go, bp, be, tr))}
-        evaluate = lambda cur, want_grad=True: native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt,
-                                                                conf, *cur, preserve_pose=preserve, want_grad=want_grad)
+        evaluate = lambda cur, want_grad=True: self._fit(cfg, model_idx, tgt, conf, dict(zip(native.PARAM_KEYS, cur)),
+                                                         preserve_pose=preserve, want_grad=want_grad)
         torch_lbfgs(evaluate, p, opt_keys, cols, self.device, max_iter, float(self.step_size))
         with torch.no_grad():
             loss = evaluate(upload_params(p, cols, self.device), False)["loss"]            # world_space.py:245-246
@@ -311,8 +274,8 @@ class WorldSpaceFitter(FitterBase):
             with torch.no_grad():
                 flat[:, free_t] = torch.from_numpy(np.ascontiguousarray(x_free, dtype=np.float32)).to(dev)
                 cur = split_params(flat, cols)
-                return native.fit_world(self.smpl.native, self.pose_prior.native, cfg, model_idx, tgt, conf, *cur,
-                                        preserve_pose=preserve, want_grad=want_grad), cur
+                return self._fit(cfg, model_idx, tgt, conf, dict(zip(native.PARAM_KEYS, cur)), preserve_pose=preserve,
+                                 want_grad=want_grad), cur
 
         def evaluate(x_free):
             r, _ = launch(x_free, True)
@@ -332,39 +295,6 @@ class WorldSpaceFitter(FitterBase):
         """Fit one frame (or a batch) with the reference's ``fit_frame`` contract:
         inputs are not modified, outputs are detached tensors, ``loss`` is the batch sum of
         the last iteration's loss evaluated before its step (world_space.py:256)."""
-        out, joints, verts, loss = self.fit_batch(
+        return self._frame_result(self.fit_batch(
             init_params, j3d, conf_3d, seq_ind, target_model_indices, joint_loss_weight, pose_preserve_weight,
-            freeze_betas, per_frame_conf=False)
-        return BodyModelFitResult(params=self.result_params(out, init_params), vertices=verts, joints=joints, loss=loss.sum())
-
-    def result_params(self, out, init_params, rows: Optional[slice] = None):
-        """Fitted parameters as the data class the reference returns for this model / input type; `rows` selects
-        frames of a batched result (hand / face fields a 24-joint fit does not touch are carried from `init_params`)."""
-        if rows is not None:
-            out = {k: v[rows] for k, v in out.items() if k != "loss"}
-        if self.smpl.model_type == "smplh" and self.smpl.packed:
-            u = self.smpl.unpack(out["body_pose"], out["betas"])
-            return SMPLHData(betas=u["betas"], global_orient=out["global_orient"], body_pose=u["body_pose"], transl=out["transl"],
-                             left_hand_pose=u["left_hand_pose"], right_hand_pose=u["right_hand_pose"])
-        if self.smpl.model_type == "smplx":
-            u = self.smpl.unpack(out["body_pose"], out["betas"])
-            fitted = SMPLXData(betas=u["betas"], global_orient=out["global_orient"], body_pose=u["body_pose"],
-                               transl=out["transl"], left_hand_pose=u["left_hand_pose"], right_hand_pose=u["right_hand_pose"],
-                               expression=u["expression"], jaw_pose=u["jaw_pose"], leye_pose=u["leye_pose"],
-                               reye_pose=u["reye_pose"])
-            return fitted
-        fields = dict(betas=out["betas"], global_orient=out["global_orient"], body_pose=out["body_pose"],
-                      transl=out["transl"])
-        if isinstance(init_params, SMPLXData):
-            keep = ("left_hand_pose", "right_hand_pose", "expression", "jaw_pose", "leye_pose", "reye_pose")
-            fitted = SMPLXData(**fields, **{k: _detached(getattr(init_params, k)) for k in keep})
-        elif isinstance(init_params, SMPLHData):
-            keep = ("left_hand_pose", "right_hand_pose")
-            fitted = SMPLHData(**fields, **{k: _detached(getattr(init_params, k)) for k in keep})
-        else:
-            fitted = SMPLData(**fields)
-        return fitted
-
-
-def _detached(x):
-    return x.detach() if isinstance(x, torch.Tensor) else x
+            freeze_betas, per_frame_conf=False), init_params)

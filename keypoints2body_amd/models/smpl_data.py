@@ -101,6 +101,26 @@ class FLAMEData(BodyModelParams):
     reye_pose: Optional[ArrayLike] = None
 
 
+def param_rows(p: BodyModelParams):
+    """(name, 2-D float32 tensor) of every array field of a parameter object (metadata and absent fields skipped)."""
+    for f in _dc.fields(p):
+        v = getattr(p, f.name)
+        if f.name == "metadata" or v is None or isinstance(v, (dict, str)):
+            continue
+        t = torch.as_tensor(v, dtype=torch.float32)
+        yield f.name, (t.unsqueeze(0) if t.dim() <= 1 else t)
+
+
+def select_rows(p: BodyModelParams, rows, count: int) -> BodyModelParams:
+    """The rows `rows` of `p`, which holds one row for each of `count` sequences (every array field; the data class kept)."""
+    sel, fields = torch.as_tensor(rows, dtype=torch.int64), {}
+    for name, t in param_rows(p):
+        if t.shape[0] != count:
+            raise ValueError(f"init_params.{name} has {t.shape[0]} rows for {count} sequences")
+        fields[name] = t.index_select(0, sel.to(t.device)).contiguous()
+    return _dc.replace(p, **fields)
+
+
 @_dc.dataclass
 class BodyModelFitResult:
     """What a fitter returns: parameters, final vertices / joints and the loss."""

@@ -31,7 +31,7 @@ print("init cam_t hip", t0.cpu().numpy())
 cfg = native.default_fit_config(); cfg.num_iters=5; cfg.sigma=1e8; cfg.joint_loss_weight=1.0
 cfg.pose_prior_weight=cfg.angle_prior_weight=cfg.shape_prior_weight=cfg.pose_preserve_weight=0.0
 cfg.optimize_mask=9; cfg.transl_prior_weight=200.0
-s1 = native.fit_world(model.native, prior.native, cfg, cs._TORSO_IDX, j3d[:, cs._TORSO_IDX].contiguous(), None, go, bp, be, t0, transl_prior_target=t0, want_grad=True)
+s1 = native.fit_world(model.native, prior.native, cfg, cs.TORSO_IDX, j3d[:, cs.TORSO_IDX].contiguous(), None, go, bp, be, t0, transl_prior_target=t0, want_grad=True)
 print("stage1 hip go", s1["global_orient"].cpu().numpy(), "t", s1["transl"].cpu().numpy())
 print("stage1 bp unchanged", (s1["body_pose"].cpu()-bp.cpu()).abs().max().item(), "betas", (s1["betas"].cpu()-be.cpu()).abs().max().item())
 diff = (res.params.body_pose.cpu() - t("out_body_pose")).abs()[0]
