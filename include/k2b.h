@@ -39,6 +39,9 @@
  *     an Adam chain those frames report a non-finite loss too.  The stand-alone terms, k2b_lbs and k2b_lbs_backward return
  *     non-finite values wherever float64 arithmetic on the same frame does, and possibly in
  *     more elements of that same frame.  (tests/test_gpu_isolation.py)
+ *   - a call does not depend on the calls before it: every output is, bit for bit, what the same call returns on freshly
+ *     created handles, whatever batches (larger ones, non-finite ones, refused ones) its handles, its thread and its
+ *     stream served before, and whatever the output buffers held.  (tests/test_gpu_call_history.py)
  */
 #ifndef K2B_H
 #define K2B_H
@@ -388,7 +391,8 @@ int k2b_fit_image_sequences(const k2b_model *model, const k2b_prior *prior, cons
  * J_dirs[root_joint] betas); the gradient takes the chain rule through that alignment.  betas_in / betas_out dev
  * [S][num_free_betas].  Per round one small prep launch, ONE evaluate-only fit launch over all N frames, one fixed-order
  * per-sequence reduction and the device L-BFGS step (one instance per sequence); only launches are queued.  A sequence's result
- * does not depend on the others.  Kinematic targets only.
+ * does not depend on the others; a sequence without frames (seq_offsets[s] == seq_offsets[s + 1]) has its own betas row and
+ * returns betas_in (tests/test_gpu_call_history.py).  Kinematic targets only.
  * ------------------------------------------------------------------------------- */
 int k2b_shape_pass_lbfgs(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
                          int32_t num_sequences, const int32_t *seq_offsets, int32_t num_frames, int32_t num_targets,
