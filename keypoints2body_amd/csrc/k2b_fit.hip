@@ -946,7 +946,8 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         // with a row wave: raised priority, so that the row wave (and its MFMAs, which hold the SIMD for 16 cycles each) fills
         // the tree wave's stalls instead of competing for its issue slots
         // (wide shape, same-box A/B at 4096 frames: tree waves 3 / row waves 0 0.3815 ms; rows above trees 0.417; all equal 0.417 -
-        //  the row waves issue few instructions and are starved either way, the tree waves are what the SIMD must keep fed)
+        //  the row waves issue few instructions and are starved either way, the tree waves are what the SIMD must keep fed.  Since the
+        //  fp32 scans the row waves arrive last, and they come level with the trees for two stretches of their iteration: see there)
         __builtin_amdgcn_s_setprio(3);
         const int steps = PAIR ? 1 : c_steps;
         // persistent L-BFGS (LbMode::persistent, at most two frames per workgroup): the IDLE tree wave 4 + s is slot s's optimiser, its state -
@@ -1103,7 +1104,12 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             __syncthreads();
             K2B_FSTAMP(2);
             // ---- component `wave` for all 16 slots: products tile by tile, tile t - 1 consumed under the products of tile t ----
+            // Priority by phase (profiles/wide_rows_first_ab.txt): the row waves are the last to arrive at barrier 2, and at priority 0
+            // beside two tree waves at 3 they issue in the gaps only.  Level with the trees for the first two tiles of the products,
+            // back to 0 for the rest and - before the arrival count, so that no wave spins at a raised priority - for the meeting,
+            // level again from the meeting to barrier 2.  (Level for all of the products, or for one tile or three: slower.)
             if (use_gmm) {
+                __builtin_amdgcn_s_setprio(3);
                 const half8 bh0 = *reinterpret_cast<const half8*>(cth_hi + 8 * cg);
                 const half8 bh1 = *reinterpret_cast<const half8*>(cth_hi + 32 + 8 * cg);
                 const half8 bl0 = *reinterpret_cast<const half8*>(cth_lo + 8 * cg);
@@ -1136,6 +1142,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                     if (t > 0) consume_tile(t - 1, accp);
                     __builtin_amdgcn_sched_barrier(0);
                     accp = acc;
+                    if (t == 1) __builtin_amdgcn_s_setprio(0);
                 }
                 {
                     const half8 rh0 = rf[0], rl0 = rf[21], rh1 = rf[42], rl1 = rf[63];
@@ -1161,11 +1168,17 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 }
                 K2B_FSTAMP(3);
                 K2B_FSTAMP(4);
+                // The priority is 0 here already (dropped behind tile 1).  This second s_setprio 0 is NOT dead weight: the build
+                // without it measured 0.3175-0.3192 against the parent's 0.3123-0.3140 ms at 4096 frames, +1.6 %, where the build
+                // with it is under the parent (profiles/wide_rows_first_ab.txt, builds "final" and "final2").  No model explains
+                // that; do not delete it without an A/B.  It also states the rule where it has to hold: nobody spins raised.
+                __builtin_amdgcn_s_setprio(0);
                 if (lane == 0) __hip_atomic_fetch_add(row_sync, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const int target = NROW * (it + 1);
                 while (__hip_atomic_load(row_sync, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
             }
             K2B_FSTAMP(5);
+            __builtin_amdgcn_s_setprio(3);
             // ---- priors: per frame in the (component, rim row) lane layout, then the set-A gradient; set B once for both --------
             float gpa[2] = {0.f, 0.f}, lossp[2] = {0.f, 0.f}, bestv[2] = {0.f, 0.f};
             float yQ = 0.f;
@@ -1228,6 +1241,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             }
             const float inv_bc2 = fast_rcp(co.y);      // (nor does the Adam coefficient's reciprocal)
             K2B_FSTAMP(6);
+            __builtin_amdgcn_s_setprio(0);
             __syncthreads();
             K2B_FSTAMP(7);
             // ---- joint gradient from the tree waves, Adam ------------------------------------------------------------------------
