@@ -21,15 +21,16 @@
  *     FIRST use of an (iterations, lr, beta1, beta2) combination per model (blocking upload
  *     of the Adam bias table; at most 64 tables are kept, least recently used evicted after
  *     a stream sync).  k2b_vertex_term never synchronises: its joint selection travels by value in
- *     the kernel arguments; k2b_surface_term and k2b_fit_world with surface targets synchronise the
+ *     the kernel arguments; k2b_surface_term, k2b_surface_term_image, and k2b_fit_world / k2b_fit_image with surface
+ *     targets synchronise the
  *     stream on the FIRST use of a selection per model (its vertex table is gathered and cached);
  *   - buffers are caller-owned; inputs are never written; handles may be shared by
  *     threads as long as concurrent calls use different streams AND different
  *     workspaces (one workspace per handle: serialise calls on one handle);
  *   - frames are independent, non-finite inputs included: in every entry with a frame or
  *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
- *     k2b_fit_image_sequences, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
- *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term) each output of a frame (in the chain
+ *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
+ *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term, k2b_surface_term_image) each output of a frame (in the chain
  *     entries and the shape pass: of a sequence; inside a chain a frame also never depends on
  *     a LATER frame) depends only on that frame's own inputs, bit for bit, even when another
  *     frame's inputs are NaN or +-Inf (a missing keypoint written as NaN, say).  A frame whose
@@ -186,7 +187,9 @@ typedef struct k2b_fit_config {
      * Z is divided by as it stands (no clamp): a joint behind the camera (Z < 0) is legal and finite; a targeted joint of
      * non-zero confidence at Z = 0 makes THAT frame's loss and gradient non-finite and no other frame's (Conventions); a joint
      * without a target, or with confidence 0, contributes exactly nothing whatever its depth.
-     * Kinematic targets only (a surface target: K2B_ERR_UNSUPPORTED), Adam only; independent frames here, warm-start chains
+     * Kinematic targets only in k2b_fit_world and the chains (a surface target: K2B_ERR_UNSUPPORTED); surface targets
+     * (vertex-selected joints, landmarks) under projection are taken by k2b_fit_image, their term alone by
+     * k2b_surface_term_image.  Adam only; independent frames here, warm-start chains
      * through k2b_fit_image_sequences (every other fit entry refuses projection != 0 with K2B_ERR_UNSUPPORTED, as does a
      * model created under K2B_FIT_SCAN64=1).
      * The term has NO counterpart in the reference (api/frame.py:71-75 raises for joints2d): it is defined here and held to
@@ -382,6 +385,33 @@ int k2b_fit_image_sequences(const k2b_model *model, const k2b_prior *prior, cons
                             float *loss_out, void *stream) K2B_SINCE(1, 8);
 
 /* ---------------------------------------------------------------------------------
+ * k2b_fit_image (ABI 1.9) — B independent frames of 2D keypoints under Adam, surface targets included.  The argument list is
+ * k2b_fit_world's; the target buffer holds rows (u - cx, v - cy, ignored), centred pixels (k2b_fit_config::projection).
+ * cfg->projection must be 1 and cfg->focal finite and positive (else K2B_ERR_INVALID_ARGUMENT: 3D targets have
+ * k2b_fit_world).  With kinematic targets only the call IS k2b_fit_world under projection: the same launch, the same bits.
+ * With surface targets among model_joint_index (indices >= J: extra joints and landmarks) it queues, per iteration, the fit
+ * kernel in evaluate-only mode (projected kinematic term and every prior) and the projected surface kernel
+ * (k2b_surface_term_image's) with its Adam tail; every surface selection takes that kernel, extras-only ones included.  For a
+ * surface target t with weighted vertex pairs (u_tk, b_tk):
+ *     (X, Y, Z) = sum_k b_tk x_u + (sum_k b_tk) transl,   e_x = fx X / Z - u',   e_y = fy Y / Z - v'
+ *     loss_t = w_j^2 c_t^2 (gmof(e_x, sigma) + gmof(e_y, sigma))
+ * under the conventions of the kinematic term: Z divided by as it stands (a point behind the camera is legal and finite), a
+ * target of confidence 0 contributes exactly nothing whatever its depth.  The surface rules of k2b_fit_world hold: at least
+ * one kinematic joint, at most 128 surface targets, conf per frame allowed, the first use of a selection on a model
+ * synchronises the stream.  Refused before anything is launched, outputs untouched: projection != 1 or a bad focal
+ * (K2B_ERR_INVALID_ARGUMENT); no kinematic joint, more than 128 surface targets, a 24-joint model without a scan plan or
+ * created under K2B_FIT_SCAN64=1 (K2B_ERR_UNSUPPORTED).  No counterpart in the reference (tests/test_gpu_reproj_surface.py
+ * holds it to a float64 oracle of the formula).
+ * ------------------------------------------------------------------------------- */
+int k2b_fit_image(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                  int32_t num_frames, int32_t num_targets, const int32_t *model_joint_index,
+                  const float *keypoints, const float *conf,
+                  const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                  const float *transl_in, const float *preserve_pose, const float *transl_prior_target,
+                  float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                  float *loss_out, float *grad_out, void *stream) K2B_SINCE(1, 9);
+
+/* ---------------------------------------------------------------------------------
  * k2b_shape_pass_lbfgs (ABI 1.3) — the shape pre-pass of many sequences together (reference core/shape.py:10-115,
  * optimize_shape_multi_frame: torch.optim.LBFGS([betas], max_iter, lr, strong_wolfe) per sequence).  Sequence s owns frames
  * seq_offsets[s] .. seq_offsets[s + 1] - 1 (dev int32 [S + 1]); per frame the kinematic targets j3d dev [N][K][3], conf dev
@@ -511,6 +541,14 @@ int k2b_surface_term(const k2b_model *model, int32_t num_frames, int32_t num_sel
                      int32_t conf_per_frame, float sigma, float joint_loss_weight, const float *global_orient,
                      const float *body_pose, const float *betas, const float *transl,
                      float *loss_out, float *grad_out, void *stream);
+/* k2b_surface_term_image (ABI 1.9): k2b_surface_term under perspective projection (k2b_fit_image has the formula).  targets dev
+ *   [B][T][3] rows (u - cx, v - cy, ignored); sigma in pixels; focal HOST [2] = (fx, fy), finite and > 0 (else
+ *   K2B_ERR_INVALID_ARGUMENT).  Limits, outputs and stream behaviour as k2b_surface_term. */
+int k2b_surface_term_image(const k2b_model *model, int32_t num_frames, int32_t num_selected,
+                           const int32_t *model_joint_index, const float *targets, const float *conf,
+                           int32_t conf_per_frame, float sigma, float joint_loss_weight, const float focal[2],
+                           const float *global_orient, const float *body_pose, const float *betas, const float *transl,
+                           float *loss_out, float *grad_out, void *stream) K2B_SINCE(1, 9);
 int k2b_adam_step(int64_t n, float *params, const float *grad, float *m, float *v, int32_t step,
                   double step_size, double beta1, double beta2, double eps, void *stream);
 

@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from ..core.config import FrameOptimizeConfig, ModelType, SequenceOptimizeConfig, frame_config_from, sequence_config_from
-from ..core.fitters.image_space import ImageSpaceFitter
-from ..core.joints.adapters import resolve_adapter
+from ..core.fitters.image_space import ImageSpaceFitter, check_torso_targets
+from ..core.joints.adapters import _BLOCKS, _block_indices, resolve_adapter
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams
 from . import common
 from .sequence import SequenceBatch, _batched_results, _packed_batch, _stack_starts
@@ -30,6 +30,40 @@ def _keypoints_and_conf(keypoints2d, conf):
     if conf.shape != (kp.shape[0],):
         raise ValueError(f"conf must be ({kp.shape[0]},), got {tuple(conf.shape)}")
     return kp[:, :2].astype(np.float64), conf.astype(np.float32)
+
+
+def _blocks_2d(blocks: dict, body_model: str, sequence: bool, target_model_indices):
+    """The reference-style dict of blocks (``body`` 22 or 24 points, ``left_hand`` / ``right_hand`` 21, ``face`` k) as one array
+    and its model indices, exactly as the 3D dict input maps them (``adapters._block_indices``; the face block at 67 ..): rows
+    (K,2|3) per block for a frame, (T,K,2|3) for a sequence, a third column the confidence.  Pure host work: every refusal
+    (an unknown or misplaced block, blocks of different T, missing torso joints) comes before any device call."""
+    if target_model_indices is not None:
+        raise ValueError("a dict of blocks names its own model indices: target_model_indices must be None")
+    unknown = sorted(set(blocks) - {name for name, _, _ in _BLOCKS})
+    if unknown:
+        raise ValueError(f"unknown keypoint blocks {unknown}: expected body, left_hand, right_hand, face")
+    pts, idx, frames = [], [], None
+    for name, _, _ in _BLOCKS:
+        if name not in blocks:
+            continue
+        b = blocks[name]
+        kp = np.asarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float64)
+        if kp.ndim != (3 if sequence else 2) or kp.shape[-1] not in (2, 3):
+            want = "(T,K,2) or (T,K,3)" if sequence else "(K,2) or (K,3)"
+            raise ValueError(f"Expected the {name} block of shape {want}, got {tuple(kp.shape)}")
+        if sequence:
+            if frames is None:
+                frames = kp.shape[0]
+            elif kp.shape[0] != frames:
+                raise ValueError("all dict sequence blocks must share same T")
+        if kp.shape[-1] == 2:                                 # (no confidence column: ones)
+            kp = np.concatenate([kp, np.ones(kp.shape[:-1] + (1,))], axis=-1)
+        idx.extend(_block_indices(name, kp.shape[-2], body_model).tolist())
+        pts.append(kp)
+    if not pts:
+        raise ValueError("dict input must provide at least one of: body, left_hand, right_hand, face")
+    check_torso_targets(idx)
+    return np.concatenate(pts, axis=-2), idx
 
 
 def _fitter_and_starts(uv, cf, frame_cfg, body_model, model, init_params, count, joint_layout, target_model_indices, device,
@@ -66,7 +100,10 @@ def optimize_params_frame_2d(keypoints2d, *, focal, principal_point, conf=None, 
                              mean_params: Optional[tuple] = None) -> BodyModelFitResult:
     """Optimise body parameters and the camera translation for a single frame of 2D keypoints.
 
-    ``keypoints2d`` (K,2) pixels, or (K,3) with a confidence column; ``focal`` a number or ``(fx, fy)`` in pixels;
+    ``keypoints2d`` (K,2) pixels, or (K,3) with a confidence column, or the reference-style dict of blocks (``body`` 22 or 24
+    points, ``left_hand`` / ``right_hand`` 21 points on SMPL-H / SMPL-X, ``face`` k points on SMPL-X, each (K,2) or (K,3)), mapped
+    to model indices as the 3D dict input maps them - hand and face points are surface targets, projected like the joints
+    (``k2b_fit_image``); ``target_model_indices`` may name such indices too (extra joints on SMPL).  ``focal`` a number or ``(fx, fy)`` in pixels;
     ``principal_point`` ``(cx, cy)``.  The joint order is named by ``joint_layout`` as for ``optimize_params_frame`` (22 AMASS
     or 24 SMPL joints by count; layouts that rotate 3D axes make no sense for pixels and are refused), or given joint by joint
     with ``target_model_indices``.  ``config`` supplies ``step_size``, ``num_iters`` (per stage), ``pose_preserve_weight`` and
@@ -75,10 +112,12 @@ def optimize_params_frame_2d(keypoints2d, *, focal, principal_point, conf=None, 
     shape, ``mean_params`` or the reference's file) starts the fit; its ``transl`` is not read - the camera translation starts
     from similar triangles over the torso.  The result's ``params.transl`` is the camera translation; joints and vertices are in
     model space.  The term has no reference counterpart (``ImageSpaceFitter``)."""
-    device = common.resolve_device(device)
-    frame_cfg = frame_config_from(config) if config is not None else FrameOptimizeConfig(use_lbfgs=False)
     if body_model not in common.SMPL_FAMILY:
         raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
+    if isinstance(keypoints2d, dict):
+        keypoints2d, target_model_indices = _blocks_2d(keypoints2d, body_model, False, target_model_indices)
+    device = common.resolve_device(device)
+    frame_cfg = frame_config_from(config) if config is not None else FrameOptimizeConfig(use_lbfgs=False)
     uv, cf = _keypoints_and_conf(keypoints2d, conf)
     fitter, (init_params,), uv, cf = _fitter_and_starts(uv, cf, frame_cfg, body_model, model, None if init_params is None else [init_params],
                                                         1, joint_layout, target_model_indices, device, pose_prior, mean_params)
@@ -100,11 +139,18 @@ def _fit_videos(seqs, focal, principal_point, body_model, model, config, init_pa
                 joint_loss_weight, device, pose_prior, mean_params, want_vertices=True):
     """The shared body of the two video entry points: ``(fitter, one start per sequence, params, joints, vertices, loss,
     lengths)`` with the results packed over all frames."""
+    if body_model not in common.SMPL_FAMILY:
+        raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
+    if any(isinstance(k, dict) for k in seqs):                # dicts of blocks: every video names the same model indices
+        if not all(isinstance(k, dict) for k in seqs):
+            raise ValueError("either every sequence is a dict of blocks or none is")
+        seqs, indices = zip(*(_blocks_2d(k, body_model, True, target_model_indices) for k in seqs))
+        if any(i != indices[0] for i in indices):
+            raise ValueError("every sequence must give the same blocks with the same number of keypoints")
+        target_model_indices = indices[0]
     device = common.resolve_device(device)
     seq_cfg = sequence_config_from(config) if config is not None else SequenceOptimizeConfig(frame=FrameOptimizeConfig(use_lbfgs=False))
     frame_cfg = seq_cfg.frame
-    if body_model not in common.SMPL_FAMILY:
-        raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
     S = len(seqs)
     if init_params is not None and (not isinstance(init_params, (list, tuple)) or len(init_params) != S):
         raise ValueError("init_params must be None or a list with one start per sequence")
@@ -132,8 +178,10 @@ def optimize_params_sequence_2d(keypoints_seq, *, focal, principal_point, body_m
                                 joint_layout: Optional[str] = None, target_model_indices=None, sigma: float = 100.0,
                                 joint_loss_weight: float = 1.0, device=None, pose_prior=None,
                                 mean_params: Optional[tuple] = None) -> list[BodyModelFitResult]:
-    """Fit a video of 2D keypoints, ``keypoints_seq`` (T,K,2) pixels or (T,K,3) with a confidence column, as ONE warm-start
-    chain on the device (stage 1 for the first frame, then one ``k2b_fit_image_sequences`` launch for all frames); results in
+    """Fit a video of 2D keypoints, ``keypoints_seq`` (T,K,2) pixels or (T,K,3) with a confidence column, or a dict of such
+    blocks (``optimize_params_frame_2d``), as ONE warm-start
+    chain on the device (stage 1 for the first frame, then one ``k2b_fit_image_sequences`` launch for all frames - with surface
+    targets among them, one ``k2b_fit_image`` call per frame index, queued without a host round trip); results in
     temporal order, frame 0's parameters equal to ``optimize_params_frame_2d`` on that frame.
 
     ``config`` is a ``SequenceOptimizeConfig`` or dict (without one: Adam, the defaults): ``frame.num_iters`` iterations for

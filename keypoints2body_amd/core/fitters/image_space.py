@@ -29,8 +29,12 @@ then the whole of stage 2 for every frame of every sequence as ONE launch (``k2b
 is stage 2 as above, every later frame starts from its predecessor's result, preserves that result's body pose and, with
 ``freeze_betas``, holds the shape the first frame estimated.
 
+Surface targets (model index at or above the joint count: smplx's vertex-selected joints - nose, eyes, ears, toes, heels,
+fingertips - and its barycentric face landmarks) are projected like the joints (``k2b_fit_image``, ``include/k2b.h``): stage 2
+and the loss re-evaluation then go through that entry, two launches per iteration, and a video runs its chain as queued steps
+in lockstep (``fit_sequences``), since the one-launch chain takes kinematic targets only.  Stage 1 is the torso's, kinematic.
+
 Adam only: the device L-BFGS entries refuse the projected term (``K2B_ERR_UNSUPPORTED``), so ``use_lbfgs=True`` raises.
-Kinematic targets only (model index below the joint count): surface targets keep their 3D term.
 """
 from __future__ import annotations
 
@@ -69,6 +73,14 @@ def focal_pair(focal) -> tuple:
     if f.shape != (2,) or not (np.isfinite(f).all() and (f > 0).all()):
         raise ValueError("focal must be a positive finite number or a pair (fx, fy)")
     return float(f[0]), float(f[1])
+
+
+def check_torso_targets(model_idx) -> None:
+    """Raise ``ValueError`` unless all four torso joints are among the targets (no device call)."""
+    have = {int(j) for j in model_idx}
+    missing = [TORSO_JOINTS[i] for i, j in enumerate(TORSO_IDX) if j not in have]
+    if missing:
+        raise ValueError(f"the torso joints {missing} are not among the targets: the initial translation and stage 1 need all four")
 
 
 def guess_init_2d(model_joints: torch.Tensor, torso_uv: torch.Tensor, focal: tuple, torso_index: torch.Tensor) -> torch.Tensor:
@@ -112,9 +124,17 @@ class ImageSpaceFitter(FitterBase):
             self._packed_config(cfg)
         return cfg1, cfg2, fit_betas
 
-    def _kinematic_only(self, model_idx):
-        if any(int(j) >= self.smpl.num_joints for j in model_idx):
-            raise NotImplementedError("projected surface targets (vertex-selected joints, landmarks) are not built: kinematic joints only")
+    def _has_surface_targets(self, model_idx) -> bool:
+        return any(int(j) >= self.smpl.num_joints for j in model_idx)
+
+    def _fit_image(self, cfg, idx, targets, conf, params):
+        """Stage 2's call: ``native.fit_image`` with surface targets among `idx`, else ``_fit`` (the same bits as ever)."""
+        if not self._has_surface_targets(idx):
+            return self._fit(cfg, idx, targets, conf, params)
+        if conf is not None:
+            cfg.conf_per_frame = int(conf.dim() == 2)
+        return native.fit_image(self.smpl.native, self.pose_prior.native, cfg, idx, targets, conf, params["global_orient"],
+                                params["body_pose"], params["betas"], params["transl"])
 
     def _prepare(self, init_params, keypoints2d, first_rows, focal, principal_point, conf, target_model_indices, per_frame_conf,
                  init_cam_t):
@@ -126,12 +146,10 @@ class ImageSpaceFitter(FitterBase):
         B = targets.shape[0] if first_rows is None else len(first_rows)
         go, bp, be = self._start_rows(init_params)
         model_idx, targets, cf = self._targets_and_conf(targets, target_model_indices, conf, per_frame_conf, (go, bp, be), B,
-                                                        names=("keypoints2d", "keypoint"), check_index=self._kinematic_only)
+                                                        names=("keypoints2d", "keypoint"))
 
         # stage 1's targets: the four torso joints among the detections
-        missing = [TORSO_JOINTS[i] for i, j in enumerate(TORSO_IDX) if j not in model_idx]
-        if missing:
-            raise ValueError(f"the torso joints {missing} are not among the targets: the initial translation and stage 1 need all four")
+        check_torso_targets(model_idx)
         torso_cols = torch.tensor([model_idx.index(j) for j in TORSO_IDX], dtype=torch.int64, device=self.device)
         firsts = targets if first_rows is None else targets.index_select(
             0, torch.as_tensor(np.asarray(first_rows, dtype=np.int64), device=self.device))
@@ -157,18 +175,18 @@ class ImageSpaceFitter(FitterBase):
         prior_target = cam_t0 if cfg1.transl_prior_weight != 0.0 else None
         s1 = self._fit(cfg1, TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0),
                        transl_prior_target=prior_target)
-        s2 = self._fit(cfg2, model_idx, targets, cf, s1)
+        s2 = self._fit_image(cfg2, model_idx, targets, cf, s1)
         out = {k: s2[k] for k in native.PARAM_KEYS}
         # the loss at the result: stage 2's terms without the preserve term, one evaluate-only launch
         cfg2.num_iters, cfg2.step_size, cfg2.pose_preserve_weight = 1, 0.0, 0.0
-        out["loss"] = self._fit(cfg2, model_idx, targets, cf, out)["loss"]
+        out["loss"] = self._fit_image(cfg2, model_idx, targets, cf, out)["loss"]
         self.last_init_cam_t = cam_t0
         return self._result(out, run_forward, want_vertices)
 
     def fit_sequences(self, init_params: SMPLData, keypoints2d, lengths, focal, principal_point=(0.0, 0.0), conf=None,
                       target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0,
                       pose_preserve_weight: float = 5.0, freeze_betas: bool = True, depth_weight: float = 100.0,
-                      want_vertices: bool = True, run_forward: bool = True):
+                      want_vertices: bool = True, run_forward: bool = True, _one_launch=None):
         """S videos as warm-start chains: `init_params` one start row per sequence, `keypoints2d` packed (sum T, K, 2) pixels,
         `lengths` (S,) frames per sequence (0: an empty sequence, whose start row is not read), `conf` None, (K,) or one row per
         frame (sum T, K).  Three fit launches whatever S and T: the initial translation of the S first frames by ``guess_init_2d``
@@ -177,6 +195,10 @@ class ImageSpaceFitter(FitterBase):
         term (so it equals ``fit_batch`` on that frame alone), every later frame starts from its predecessor's result, preserves
         that result's body pose with `pose_preserve_weight`, runs ``num_iters_followup`` iterations with a fresh optimiser and,
         with `freeze_betas`, holds the shape (SMPL-H / SMPL-X: the betas; the expression stays free).
+
+        With surface targets (which the one-launch chain refuses) the same chain runs as queued steps in lockstep
+        (``_lockstep_chain``): step t is one ``k2b_fit_image`` call over the sequences that have a frame t, nothing comes back
+        to the host between steps.  ``_one_launch=False`` forces that route for kinematic targets as well (tests).
 
         Returns ``fit_batch``'s ``(params, joints, vertices, loss)`` over the sum T packed rows.  ``loss`` is the chain's own: a
         frame's loss at its LAST iteration, before that iteration's step, preserve term included - the convention of the 3D
@@ -201,10 +223,46 @@ class ImageSpaceFitter(FitterBase):
         cfg2.conf_per_frame = int(cf is not None and cf.dim() == 2)
         s1 = self._fit(cfg1, TORSO_IDX, torso_tgt, None, dict(global_orient=go, body_pose=bp, betas=be, transl=cam_t0),
                        transl_prior_target=cam_t0 if cfg1.transl_prior_weight != 0.0 else None)
-        out = native.fit_image_sequences(self.smpl.native, self.pose_prior.native, cfg2, int(self.num_iters_followup), bool(freeze_betas),
-                                         model_idx, L[live], targets, cf, s1["global_orient"], s1["body_pose"], s1["betas"], s1["transl"])
+        one_launch = not self._has_surface_targets(model_idx) if _one_launch is None else bool(_one_launch)
+        if one_launch:
+            out = native.fit_image_sequences(self.smpl.native, self.pose_prior.native, cfg2, int(self.num_iters_followup), bool(freeze_betas),
+                                             model_idx, L[live], targets, cf, s1["global_orient"], s1["body_pose"], s1["betas"], s1["transl"])
+        else:
+            out = self._lockstep_chain(cfg2, bool(freeze_betas), model_idx, L[live], targets, cf, s1)
         self.last_init_cam_t = cam_t0
         return self._result(out, run_forward, want_vertices)
+
+    def _lockstep_chain(self, cfg2, freeze_betas, model_idx, lengths, targets, cf, s1):
+        """``k2b_fit_image_sequences``' chain as queued steps: `lengths` (S,) > 0 frames per sequence over the packed rows of
+        `targets` / `cf`, `s1` the S starts.  Step 0 runs `cfg2` without the preserve term; step t > 0 runs over the sequences
+        longer than t, each from its row of step t - 1 (whose body pose the preserve term holds: the entry's default),
+        ``num_iters_followup`` iterations, a fresh optimiser and, with `freeze_betas`, the shape held.  The row indices of every
+        step are uploaded before the first launch; the host reads nothing back in between."""
+        lengths = np.asarray(lengths, dtype=np.int64)
+        offsets = np.concatenate(([0], np.cumsum(lengths)[:-1]))
+        index = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int64), device=self.device)
+        steps, prev_live = [], np.arange(lengths.size)
+        for t in range(int(lengths.max())):
+            live = np.flatnonzero(lengths > t)
+            # (rows of this step in the packed arrays; positions of its sequences among the previous step's)
+            steps.append((index(offsets[live] + t), index(np.searchsorted(prev_live, live))))
+            prev_live = live
+        out = native._fit_outputs(self.smpl.native, (int(lengths.sum()),))
+        per_frame = cf is not None and cf.dim() == 2
+        first = native.FitConfigC.from_buffer_copy(cfg2)
+        first.pose_preserve_weight = 0.0
+        follow = native.FitConfigC.from_buffer_copy(cfg2)
+        follow.num_iters = int(self.num_iters_followup)
+        if freeze_betas:
+            follow.freeze_betas = 1
+        prev = s1
+        for t, (rows, among_prev) in enumerate(steps):
+            start = prev if t == 0 else {k: prev[k].index_select(0, among_prev) for k in native.PARAM_KEYS}
+            prev = self._fit_image(first if t == 0 else follow, model_idx, targets.index_select(0, rows),
+                                   cf.index_select(0, rows) if per_frame else cf, start)
+            for k in out:
+                out[k].index_copy_(0, rows, prev[k])
+        return out
 
     def final_forward(self, out, want_vertices=True):
         """Model-space joints / vertices: the camera translation is part of the parameters, not applied to the mesh."""

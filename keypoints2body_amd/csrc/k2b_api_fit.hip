@@ -67,23 +67,18 @@ int check_surface_targets(const Targets& t, const FitCall& c, int J) {
     return K2B_OK;
 }
 // k2b_fit_config::projection: its values, and what the projected joint term is not built into
-int check_focal(const char* who, const k2b_fit_config* cfg) {
-    for (int i = 0; i < 2; ++i)
-        if (!(cfg->focal[i] > 0.0f) || !(cfg->focal[i] <= 3.402823466e38f))      // (NaN fails the first comparison)
-            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: focal[%d]=%g must be finite and positive", who, i, (double)cfg->focal[i]);
-    return K2B_OK;
-}
 int check_projection(const k2b_fit_config* cfg, const FitCall& c) {
     if (cfg->projection == 0) return K2B_OK;
     if (cfg->projection != 1) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: projection=%d must be 0 or 1", cfg->projection);
-    if (const int rc = check_focal("k2b_fit_world", cfg); rc != K2B_OK) return rc;
+    if (const int rc = check_focal("k2b_fit_world", cfg->focal); rc != K2B_OK) return rc;
     // (a chain under projection is k2b_fit_image_sequences' alone: FitCall::Chain::image)
     if ((c.chain.len > 1 && !c.chain.image) || c.lbfgs.mode != k2b::LbMode::none)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the projected joint term is built for independent frames under Adam only");
     return K2B_OK;
 }
-int check_projected_targets(const k2b_fit_config* cfg, const Targets& t) {
-    if (cfg->projection != 0 && !t.vsel.empty())
+// (k2b_fit_image alone lets them through: FitCall::projected_surface)
+int check_projected_targets(const k2b_fit_config* cfg, const FitCall& c, const Targets& t) {
+    if (cfg->projection != 0 && !t.vsel.empty() && !c.projected_surface)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: surface targets (vertex-selected joints, landmarks) keep the 3D term: "
                     "no projection for model indices beyond the kinematic joints");
     return K2B_OK;
@@ -124,9 +119,10 @@ void fill_call_fields(Args& a, const k2b_fit_config* cfg, const FitCall& c, cons
 
 // ---- surface targets: the Adam loop as pairs of launches ---------------------------------------------------------------------
 // Targets with model index >= J go to the vertex-term kernel when they are at most 32 extra joints (the path of the first
-// release, bit for bit), to the surface-point kernel otherwise (landmarks among them, or more than 32).
-bool needs_surface_kernel(const k2b_model* m, const std::vector<int>& sel) {
-    if (sel.size() > 32) return true;
+// release, bit for bit), to the surface-point kernel otherwise (landmarks among them, or more than 32).  Under projection every
+// selection takes the surface-point kernel: the vertex-term kernel is 3D only.
+bool needs_surface_kernel(const k2b_model* m, const k2b_fit_config* cfg, const std::vector<int>& sel) {
+    if (cfg->projection != 0 || sel.size() > 32) return true;
     for (int j : sel)
         if (j >= m->J + m->E) return true;
     return false;
@@ -142,7 +138,7 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
     const std::vector<int>& ssel = targets.vsel;
     const std::vector<int>& vcol = targets.vcol;
     const int B = a.num_frames, NB = model->NB, D = 3 * (model->J - 1), P = 3 + D + NB + 3;
-    const bool surface = needs_surface_kernel(model, ssel);
+    const bool surface = needs_surface_kernel(model, cfg, ssel);
     k2b::SurfaceTermArgs s{};
     if (surface)
         if (const int rc = surface_table(model, ssel, vcol, stream, &s); rc != K2B_OK) return rc;
@@ -199,6 +195,7 @@ int fit_world_vertex_joints(k2b_model* model, const k2b_fit_config* cfg, Args a,
     s.loss_in = v.loss_in; s.grad_in = v.grad_in; s.adam_m = v.adam_m; s.adam_v = v.adam_v;
     s.one_minus_beta1 = v.one_minus_beta1; s.beta2 = v.beta2; s.one_minus_beta2 = v.one_minus_beta2; s.eps = v.eps;
     s.opt_mask = v.opt_mask; s.frozen_shape = v.frozen_shape;
+    s.projection = a.projection; s.focal_x = a.focal_x; s.focal_y = a.focal_y;
     for (int it = 0; it < iters; ++it) {
         TRY_VJ(launch_eval(a));
         v.adam_coef = coef + it;
@@ -229,7 +226,7 @@ int fit_tree(k2b_model* model, k2b_prior* prior, const k2b_fit_config* cfg, int 
     k2b::FitTreeArgs a{};
     Targets t;
     if (const int rc = classify_targets(model, c, model->kin.pos.data(), &t); rc != K2B_OK) return rc;
-    if (const int rc = check_projected_targets(cfg, t); rc != K2B_OK) return rc;
+    if (const int rc = check_projected_targets(cfg, c, t); rc != K2B_OK) return rc;
     memcpy(a.lane_target, t.lane_target, sizeof a.lane_target);
     for (int i = 0; i < 4; ++i) {
         const int ai = cfg->angle_prior_index[i];
@@ -270,7 +267,7 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
     k2b::FitArgs a{};
     Targets t;
     if (const int rc = classify_targets(model, c, nullptr, &t); rc != K2B_OK) return rc;
-    if (const int rc = check_projected_targets(cfg, t); rc != K2B_OK) return rc;
+    if (const int rc = check_projected_targets(cfg, c, t); rc != K2B_OK) return rc;
     if (cfg->projection != 0 && model->fit_scan64)
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_world: the projected joint term is built for the fp32 scans only (this model has no scan "
                     "plan, or was created under K2B_FIT_SCAN64)");
@@ -374,6 +371,12 @@ int ragged_slots(const char* who, int32_t S, const int32_t* lengths, const int32
         r->meta[(size_t)i * 4 + 1] = offsets[order[i]];
         r->meta[(size_t)i * 4 + 2] = lengths[order[i]];
     }
+    return K2B_OK;
+}
+int check_focal(const char* who, const float* focal) {
+    for (int i = 0; i < 2; ++i)
+        if (!(focal[i] > 0.0f) || !(focal[i] <= 3.402823466e38f))      // (NaN fails the first comparison)
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: focal[%d]=%g must be finite and positive", who, i, (double)focal[i]);
     return K2B_OK;
 }
 bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx) {
@@ -499,7 +502,7 @@ int k2b_fit_image_sequences(const k2b_model* model, const k2b_prior* prior, cons
     if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
     if (cfg->projection != 1)
         return fail(K2B_ERR_INVALID_ARGUMENT, "%s: projection=%d must be 1 (3D targets: k2b_fit_sequences)", who, cfg->projection);
-    if (const int rc = check_focal(who, cfg); rc != K2B_OK) return rc;
+    if (const int rc = check_focal(who, cfg->focal); rc != K2B_OK) return rc;
     if (followup_iters < 1 || followup_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, followup_iters);
     if (cfg->num_iters < 1 || cfg->num_iters > (1 << 20)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_iters=%d", who, cfg->num_iters);
     if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
@@ -524,6 +527,37 @@ int k2b_fit_image_sequences(const k2b_model* model, const k2b_prior* prior, cons
     c.loss_out = loss_out;
     c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.iters = followup_iters; c.chain.meta = meta;
     c.chain.image = true; c.chain.freeze_shape = followup_freeze_betas != 0;
+    return fit_world_impl(model, prior, cfg, c);
+}
+
+// Independent frames of 2D keypoints, surface targets included (ABI 1.9): k2b_fit_world under projection with the one flag that
+// lets surface targets through check_projected_targets (FitCall::projected_surface).  What the shared path would refuse about
+// the surface targets is refused here first, by this entry's name; every refusal comes before anything is queued.
+int k2b_fit_image(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t B, int32_t K,
+                  const int32_t* model_joint_index, const float* keypoints, const float* conf, const float* go_in,
+                  const float* bp_in, const float* be_in, const float* tr_in, const float* preserve, const float* tr_prior,
+                  float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out, float* grad_out, void* stream) {
+    const char* who = "k2b_fit_image";
+    if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (cfg->projection != 1)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: projection=%d must be 1 (3D targets: k2b_fit_world)", who, cfg->projection);
+    if (const int rc = check_focal(who, cfg->focal); rc != K2B_OK) return rc;
+    if (const int rc = check_targets(who, model, K, model_joint_index); rc != K2B_OK) return rc;
+    int surface = 0;
+    for (int k = 0; k < K; ++k) surface += model_joint_index[k] >= model->J ? 1 : 0;
+    if (surface > k2b::kSurfMaxTargets)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: %d surface targets (vertex-selected joints and landmarks), at most %d per call", who, surface,
+                    k2b::kSurfMaxTargets);
+    if (surface > 0 && surface == K)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: at least one kinematic joint (model index < %d) must be among the targets", who, model->J);
+    if (fused_eligibility(model, prior, cfg).fused && model->fit_scan64)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term is built for the fp32 scans only (this model has no scan plan, or "
+                    "was created under K2B_FIT_SCAN64)", who);
+    FitCall c = fit_call(B, K, model_joint_index, keypoints, conf, stream);
+    c.in = {go_in, bp_in, be_in, tr_in};
+    c.out = {go_out, bp_out, be_out, tr_out};
+    c.preserve = preserve; c.tr_prior = tr_prior; c.loss_out = loss_out; c.grad_out = grad_out;
+    c.projected_surface = true;
     return fit_world_impl(model, prior, cfg, c);
 }
 

@@ -78,7 +78,7 @@ int device_cus() {
 
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 8u; }
+uint32_t k2b_version(void) { return (1u << 16) | 9u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }
@@ -182,21 +182,25 @@ int k2b_vertex_term(const k2b_model* model_c, int32_t B, int32_t E_sel, const in
     return K2B_OK;
 }
 
-int k2b_surface_term(const k2b_model* model_c, int32_t B, int32_t T, const int32_t* model_joint_index, const float* targets,
-                     const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight, const float* go, const float* bp,
-                     const float* be, const float* tr, float* loss_out, float* grad_out, void* stream_v) {
+// k2b_surface_term (focal = null) and k2b_surface_term_image
+static int surface_term(const char* who, const k2b_model* model_c, int32_t B, int32_t T, const int32_t* model_joint_index,
+                        const float* targets, const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight,
+                        const float* focal, const float* go, const float* bp, const float* be, const float* tr, float* loss_out,
+                        float* grad_out, void* stream_v) {
     k2b_model* m = const_cast<k2b_model*>(model_c);
-    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model is NULL");
-    if (B < 0 || T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: negative size");
+    if (!m) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model is NULL", who);
+    if (B < 0 || T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: negative size", who);
+    if (focal)
+        if (const int rc = k2b::host::check_focal(who, focal); rc != K2B_OK) return rc;
     if (B == 0 || T == 0) return K2B_OK;
-    if (T > k2b::kSurfMaxTargets) return fail(K2B_ERR_UNSUPPORTED, "k2b_surface_term: %d targets, at most %d per call", T, k2b::kSurfMaxTargets);
+    if (T > k2b::kSurfMaxTargets) return fail(K2B_ERR_UNSUPPORTED, "%s: %d targets, at most %d per call", who, T, k2b::kSurfMaxTargets);
     if (!model_joint_index || !targets || !go || !bp || !be || !tr || !loss_out || !grad_out)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: NULL buffer");
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL buffer", who);
     std::vector<int> sel(T), col(T);
     for (int t = 0; t < T; ++t) {
         const int j = model_joint_index[t];
         if (j < m->J || j >= m->J + m->E + m->lmk.L)
-            return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term: model_joint_index[%d]=%d outside [%d,%d)", t, j, m->J, m->J + m->E + m->lmk.L);
+            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model_joint_index[%d]=%d outside [%d,%d)", who, t, j, m->J, m->J + m->E + m->lmk.L);
         sel[t] = j;
         col[t] = t;
     }
@@ -205,9 +209,26 @@ int k2b_surface_term(const k2b_model* model_c, int32_t B, int32_t T, const int32
     if (const int rc = surface_table(m, sel, col, stream, &a); rc != K2B_OK) return rc;
     a.num_frames = B; a.num_targets = T; a.targets = targets; a.conf = conf; a.conf_per_frame = conf_per_frame ? 1 : 0;
     a.sigma = sigma; a.joint_w = joint_loss_weight;
+    if (focal) { a.projection = 1; a.focal_x = focal[0]; a.focal_y = focal[1]; }
     a.go = go; a.bp = bp; a.be = be; a.tr = tr; a.loss_out = loss_out; a.grad_out = grad_out;
     HIP_TRY(k2b::launch_surface_term(a, stream));
     return K2B_OK;
+}
+
+int k2b_surface_term(const k2b_model* model, int32_t B, int32_t T, const int32_t* model_joint_index, const float* targets,
+                     const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight, const float* go, const float* bp,
+                     const float* be, const float* tr, float* loss_out, float* grad_out, void* stream) {
+    return surface_term("k2b_surface_term", model, B, T, model_joint_index, targets, conf, conf_per_frame, sigma, joint_loss_weight, nullptr,
+                        go, bp, be, tr, loss_out, grad_out, stream);
+}
+
+int k2b_surface_term_image(const k2b_model* model, int32_t B, int32_t T, const int32_t* model_joint_index, const float* targets,
+                           const float* conf, int32_t conf_per_frame, float sigma, float joint_loss_weight, const float focal[2],
+                           const float* go, const float* bp, const float* be, const float* tr, float* loss_out, float* grad_out,
+                           void* stream) {
+    if (!focal) return k2b::host::fail(K2B_ERR_INVALID_ARGUMENT, "k2b_surface_term_image: focal is NULL");
+    return surface_term("k2b_surface_term_image", model, B, T, model_joint_index, targets, conf, conf_per_frame, sigma, joint_loss_weight,
+                        focal, go, bp, be, tr, loss_out, grad_out, stream);
 }
 
 int k2b_adam_step(int64_t n, float* params, const float* grad, float* mbuf, float* vbuf, int32_t step, double step_size,

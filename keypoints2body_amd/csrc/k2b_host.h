@@ -231,6 +231,8 @@ struct FitCall {
     struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool image = false, freeze_shape = false; } chain;
     // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
     struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
+    // set by k2b_fit_image alone: surface targets are allowed under projection (the projected form of k2b_surface.hip)
+    bool projected_surface = false;
 };
 // what every entry knows of its call; the parameter arrays and the outputs are set by name
 inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, void* stream) {
@@ -258,6 +260,7 @@ inline int refuse_projection(const char* who, const k2b_fit_config* cfg) {
     return K2B_OK;
 }
 int check_targets(const char* who, const k2b_model* m, int32_t K, const int32_t* idx);
+int check_focal(const char* who, const float* focal);       // fx, fy: finite and positive
 
 // Ragged sequences of the k2b_fit_sequences* entries: the chain slots in launch order.
 struct RaggedSlots {

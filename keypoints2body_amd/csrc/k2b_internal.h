@@ -298,6 +298,9 @@ struct SurfaceTermArgs {
     float one_minus_beta1, beta2, one_minus_beta2, eps;
     int opt_mask;
     int frozen_shape;
+    // perspective form of the target block (k2b.h, k2b_fit_config::projection): targets are rows (u', v', ignored)
+    int projection;
+    float focal_x, focal_y;
 };
 hipError_t launch_surface_term(const SurfaceTermArgs& a, hipStream_t stream);
 hipError_t launch_surface_gather(const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights,

@@ -16,6 +16,11 @@
 // compact table (k2b_surface_gather_kernel), cached per model and selection (k2b_api_model.hip).  Per iteration one 256-lane
 // workgroup handles one frame: joints on the first wave, vertices / targets / pose features spread over all four waves,
 // every reduction a fixed-order loop (a frame's result does not depend on the batch it rides in).
+//
+// The term has a second, PROJECTED form (k2b_surface_term_kernel<true>: k2b_surface_term_image, k2b_fit_image) for 2D keypoints:
+// the same point x_t seen by a pinhole camera, e = (fx X / Z - u', fy Y / Z - v'), loss_t = w^2 c_t^2 (gmof(e_x) + gmof(e_y)),
+// dL/dx_t = (g_x, g_y, -(X g_x + Y g_y) / Z) with g_x = fx gmof'(e_x) / Z.  Only the target block differs; the 3D instantiation
+// keeps its code.
 #include "k2b_internal.h"
 
 namespace k2b {
@@ -34,6 +39,9 @@ __device__ __forceinline__ Vec3 axial_of_GRt_s(const Mat3& G, const Mat3& R) {
     return {M[7] - M[5], M[2] - M[6], M[3] - M[1]};
 }
 
+// PROJ: the perspective form of the target block (k2b.h, k2b_fit_config::projection, as k2b_fit_tree.hip's joint term); everything
+// before the point and after dL/dx_t is the 3D form's.
+template <bool PROJ>
 __global__ __launch_bounds__(kSurfThreads) void k2b_surface_term_kernel(const SurfaceTermArgs a) {
     constexpr int VJM = kMaxJoints, PFM = 9 * (kMaxJoints - 1), UM = kSurfMaxVerts, TM = kSurfMaxTargets;
     const int VJ = a.num_joints;
@@ -132,11 +140,31 @@ __global__ __launch_bounds__(kSurfThreads) void k2b_surface_term_kernel(const Su
         }
         const int kcol = a.sel_k[t];
         const float* y = a.targets + ((size_t)f * a.num_targets + kcol) * 3;
-        const float ex = x.x + sw * tx - y[0], ey = x.y + sw * ty - y[1], ez = x.z + sw * tz - y[2];
         swt[t] = sw;
         const float cf = a.conf ? a.conf[(a.conf_per_frame ? (size_t)f * a.num_targets : 0) + kcol] : 1.0f;
         const float wc = (a.joint_w * a.joint_w) * (cf * cf);
         const float s2 = a.sigma * a.sigma;
+        if constexpr (PROJ) {
+            // e = (fx X / Z - u', fy Y / Z - v'), the target row (u', v', ignored) in centred pixels, sigma in pixels.  Z is divided
+            // by as it stands (IEEE division, no clamp: a point behind the camera is legal), so a target of confidence 0 is left
+            // out by the branch, not by its weight (0 . inf at Z = 0).
+            float l = 0.f;
+            Vec3 g = {0.f, 0.f, 0.f};
+            if (cf != 0.f) {
+                const float X = x.x + sw * tx, Y = x.y + sw * ty, iz = 1.0f / (x.z + sw * tz);
+                const float ex = a.focal_x * X * iz - y[0], ey = a.focal_y * Y * iz - y[1];
+                const float x2 = ex * ex, y2 = ey * ey;
+                const float dx = s2 + x2, dy = s2 + y2;
+                l = wc * ((s2 * x2) / dx + (s2 * y2) / dy);
+                const float k2 = 2.f * wc * (s2 * s2);
+                const float gx = a.focal_x * (k2 * ex / (dx * dx)) * iz, gy = a.focal_y * (k2 * ey / (dy * dy)) * iz;
+                g = {gx, gy, -(X * gx + Y * gy) * iz};
+            }
+            slt[t] = l;
+            sgt[t][0] = g.x; sgt[t][1] = g.y; sgt[t][2] = g.z;
+            continue;
+        }
+        const float ex = x.x + sw * tx - y[0], ey = x.y + sw * ty - y[1], ez = x.z + sw * tz - y[2];
         const float x2 = ex * ex, y2 = ey * ey, z2 = ez * ez;
         const float dx = s2 + x2, dy = s2 + y2, dz = s2 + z2;
         slt[t] = wc * ((s2 * x2) / dx + (s2 * y2) / dy + (s2 * z2) / dz);
@@ -322,7 +350,10 @@ hipError_t launch_surface_term(const SurfaceTermArgs& a, hipStream_t stream) {
     if (a.num_sel > kSurfMaxTargets || a.num_u < 1 || a.num_u > kSurfMaxVerts || a.num_joints < 1 || a.num_joints > kMaxJoints ||
         a.num_betas > kMaxShape)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k2b_surface_term_kernel, dim3(a.num_frames), dim3(kSurfThreads), 0, stream, a);
+    if (a.projection)
+        hipLaunchKernelGGL(k2b_surface_term_kernel<true>, dim3(a.num_frames), dim3(kSurfThreads), 0, stream, a);
+    else
+        hipLaunchKernelGGL(k2b_surface_term_kernel<false>, dim3(a.num_frames), dim3(kSurfThreads), 0, stream, a);
     return hipGetLastError();
 }
 

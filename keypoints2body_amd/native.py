@@ -103,6 +103,8 @@ _PROTOTYPES = (
     ("k2b_debug_lbfgs_step", C.c_int, (_i32, _i32, _i32) + (_vp,) * 6 + (_i32, _i32, _f64, _f64, _f64, _vp, _i64, _i32, _i32) + _STREAM),
     ("k2b_point_error", C.c_int, (_i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp) + _STREAM),
     ("k2b_fit_image_sequences", C.c_int, _FIT_HEAD + (_i32, _vp, _vp, _i32, _i32) + _FIT_IN + _FIT_OUT + _STREAM),
+    ("k2b_fit_image", C.c_int, _FIT_HEAD + (_i32,) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + _STREAM),
+    ("k2b_surface_term_image", C.c_int, (_vp, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp) + (_vp,) * 6 + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -401,6 +403,18 @@ def fit_world(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joi
                      j3d, conf, global_orient, body_pose, betas, transl, world=(preserve_pose, transl_prior_target, want_grad))
 
 
+def fit_image(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joint_index: Sequence[int],
+              keypoints: torch.Tensor, conf: Optional[torch.Tensor], global_orient: torch.Tensor, body_pose: torch.Tensor,
+              betas: torch.Tensor, transl: torch.Tensor, preserve_pose: Optional[torch.Tensor] = None,
+              want_grad: bool = False, transl_prior_target: Optional[torch.Tensor] = None):
+    """Independent frames of 2D keypoints (``k2b_fit_image``): ``fit_world`` under ``cfg.projection = 1`` that also takes surface
+    targets (model indices >= J: extra joints, landmarks) through the projected surface kernel.  `keypoints` (B, K, 3): rows
+    (u - cx, v - cy, ignored)."""
+    B = keypoints.shape[0]
+    return _fit_call("k2b_fit_image", model, prior, cfg, (B,), _joint_index(model_joint_index, keypoints.shape[1]), (B,), B,
+                     keypoints, conf, global_orient, body_pose, betas, transl, world=(preserve_pose, transl_prior_target, want_grad))
+
+
 def fit_world_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joint_index: Sequence[int],
                     j3d: torch.Tensor, conf: Optional[torch.Tensor], global_orient: torch.Tensor, body_pose: torch.Tensor,
                     betas: torch.Tensor, transl: torch.Tensor, *, max_iter: int, lr: float,
@@ -651,11 +665,14 @@ def point_error(pred: torch.Tensor, gt: torch.Tensor, *, weights: Optional[torch
     return (err,) + extra if extra else err
 
 
-def _term_call(name, model: NativeModel, idx: np.ndarray, targets, conf, conf_shape, flags, sigma, joint_loss_weight, *params):
-    """Shared body of the two stand-alone joint-loss terms: loss (B,) and gradient (B, P) in the packed layout."""
+def _term_call(name, model: NativeModel, idx: np.ndarray, targets, conf, conf_shape, flags, sigma, joint_loss_weight, *params,
+               focal=None):
+    """Shared body of the stand-alone joint-loss terms: loss (B,) and gradient (B, P) in the packed layout.  `focal`: the host
+    (fx, fy) pair of the projected form, passed behind the weight."""
     dev, B, T = model.device, targets.shape[0], idx.shape[0]
+    focal_np = None if focal is None else _host_f32(np.asarray(focal, dtype=np.float64).reshape(2))
     ins = [_dev(targets, "targets", dev, (B, T, 3)), _dev(conf, "conf", dev, conf_shape), *flags, float(sigma),
-           float(joint_loss_weight), *_param_ptrs(model, B, *params)]
+           float(joint_loss_weight), *(() if focal_np is None else (_np_ptr(focal_np),)), *_param_ptrs(model, B, *params)]
     loss = torch.empty((B,), dtype=torch.float32, device=dev)
     grad = torch.empty((B, sum(_param_widths(model))), dtype=torch.float32, device=dev)
     _launch(name, dev, model.handle, B, T, _np_ptr(idx), *ins, _ptr(loss), _ptr(grad))
@@ -681,6 +698,18 @@ def surface_term(model: NativeModel, model_joint_index: Sequence[int], targets: 
     return _term_call("k2b_surface_term", model, _joint_index(model_joint_index, T), targets, conf,
                       (B, T) if per_frame else (T,), (1 if per_frame else 0,), sigma, joint_loss_weight,
                       global_orient, body_pose, betas, transl)
+
+
+def surface_term_image(model: NativeModel, model_joint_index: Sequence[int], targets: torch.Tensor, conf: Optional[torch.Tensor],
+                       sigma: float, joint_loss_weight: float, focal, global_orient: torch.Tensor, body_pose: torch.Tensor,
+                       betas: torch.Tensor, transl: torch.Tensor):
+    """``surface_term`` under perspective projection (``k2b_surface_term_image``): `targets` (B, T, 3) rows (u - cx, v - cy,
+    ignored) in centred pixels, `sigma` in pixels, `focal` = (fx, fy)."""
+    B, T = targets.shape[0], targets.shape[1]
+    per_frame = conf is not None and conf.dim() == 2
+    return _term_call("k2b_surface_term_image", model, _joint_index(model_joint_index, T), targets, conf,
+                      (B, T) if per_frame else (T,), (1 if per_frame else 0,), sigma, joint_loss_weight,
+                      global_orient, body_pose, betas, transl, focal=focal)
 
 
 def adam_step(params: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, step_size: float,
