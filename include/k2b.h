@@ -29,7 +29,7 @@
  *     workspaces (one workspace per handle: serialise calls on one handle);
  *   - frames are independent, non-finite inputs included: in every entry with a frame or
  *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
- *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
+ *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_multiview, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
  *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term, k2b_surface_term_image) each output of a frame (in the chain
  *     entries and the shape pass: of a sequence; inside a chain a frame also never depends on
  *     a LATER frame) depends only on that frame's own inputs, bit for bit, even when another
@@ -42,7 +42,9 @@
  *     more elements of that same frame.  (tests/test_gpu_isolation.py)
  *   - a call does not depend on the calls before it: every output is, bit for bit, what the same call returns on freshly
  *     created handles, whatever batches (larger ones, non-finite ones, refused ones) its handles, its thread and its
- *     stream served before, and whatever the output buffers held.  (tests/test_gpu_call_history.py)
+ *     stream served before, and whatever the output buffers held; k2b_fit_multiview included, whose camera table travels in
+ *     the kernel arguments and leaves nothing on a handle.  (tests/test_gpu_call_history.py, tests/test_gpu_multiview_fit.py;
+ *     DESIGN.md 4.4e.)
  */
 #ifndef K2B_H
 #define K2B_H
@@ -410,6 +412,47 @@ int k2b_fit_image(const k2b_model *model, const k2b_prior *prior, const k2b_fit_
                   const float *transl_in, const float *preserve_pose, const float *transl_prior_target,
                   float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
                   float *loss_out, float *grad_out, void *stream) K2B_SINCE(1, 9);
+
+/* ---------------------------------------------------------------------------------
+ * k2b_fit_multiview (ABI 1.10) — B independent frames of 2D keypoints seen by C calibrated cameras at once, under Adam.  Camera c
+ * has a row-major world-to-camera matrix R_c, a translation t_c and focals (fx_c, fy_c); with p the posed model joint of
+ * target k and transl the body's WORLD translation:
+ *     q   = R_c (p + transl) + t_c
+ *     e_x = fx_c q_x / q_z - u'_ck,   e_y = fy_c q_y / q_z - v'_ck     (u', v': pixels minus THAT camera's principal point)
+ *     joint loss = w_j^2 sum_c sum_k conf_ck^2 (gmof(e_x, sigma) + gmof(e_y, sigma))
+ *     d loss / d p = sum_c R_c^T (g_x, g_y, g_z)_c                       ((g_x, g_y, g_z)_c: the single-view form's, on q)
+ * Every other term, optimize_mask, freeze_betas, transl_prior_weight and the loss convention are k2b_fit_world's; so is the
+ * argument list from global_orient_in on.  The conventions of projection = 1 hold per pair (c, k): q_z is divided by as it
+ * stands (IEEE division; a point behind a camera is legal and finite), a pair of confidence 0 is selected out and contributes
+ * exactly nothing whatever its depth, a pair of non-zero confidence at q_z = 0 makes that frame non-finite and no other.  The
+ * views are summed in the order 0 .. C - 1 in every launch shape: a frame's result is bit-identical in any batch and at any
+ * position.  R_c need only be finite: the gradient is the exact chain rule for any linear map, and orthonormality is the
+ * caller's business (the Python layer checks it).
+ *   cameras    HOST [C], read during the call (they travel by value in the kernel arguments: all iterations in ONE launch, no
+ *              upload and no synchronisation beyond k2b_fit_world's Adam table)
+ *   keypoints  dev [B][C][K][3]: rows (u', v', ignored)
+ *   conf       dev [C][K], or [B][C][K] with cfg->conf_per_frame; NULL = ones
+ * 1 <= num_views <= 8; cfg->projection must be 1; cfg->focal is not read.  Refused before anything is queued, outputs
+ * untouched: num_views outside 1..8, a non-finite camera field, a focal that is not finite and positive, projection != 1
+ * (K2B_ERR_INVALID_ARGUMENT); surface targets (a model index >= J), a 24-joint model without a scan plan or created under
+ * K2B_FIT_SCAN64=1, a translation prior on the tree kernel (K2B_ERR_UNSUPPORTED).  No counterpart in the reference
+ * (tests/test_gpu_multiview_term.py holds it to a float64 oracle of the formula).
+ * ------------------------------------------------------------------------------- */
+typedef struct k2b_camera { /* K2B_SINCE(1, 10) */
+    float rotation[9];    /* R_c, row-major: camera = R_c world + t_c */
+    float translation[3]; /* t_c */
+    float focal[2];       /* fx_c, fy_c in pixels: finite and positive */
+} k2b_camera;
+/* sizeof(k2b_camera) as the library was built (bindings check their mirror against it). */
+uint32_t k2b_camera_size(void) K2B_SINCE(1, 10);
+int k2b_fit_multiview(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                      int32_t num_frames, int32_t num_views, const k2b_camera *cameras,
+                      int32_t num_targets, const int32_t *model_joint_index,
+                      const float *keypoints, const float *conf,
+                      const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                      const float *transl_in, const float *preserve_pose, const float *transl_prior_target,
+                      float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                      float *loss_out, float *grad_out, void *stream) K2B_SINCE(1, 10);
 
 /* ---------------------------------------------------------------------------------
  * k2b_shape_pass_lbfgs (ABI 1.3) — the shape pre-pass of many sequences together (reference core/shape.py:10-115,

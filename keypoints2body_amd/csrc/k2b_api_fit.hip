@@ -115,6 +115,14 @@ void fill_call_fields(Args& a, const k2b_fit_config* cfg, const FitCall& c, cons
     a.chain_meta = c.chain.len > 1 ? c.chain.meta : nullptr;
     a.projection = cfg->projection; a.focal_x = cfg->focal[0]; a.focal_y = cfg->focal[1];
     a.chain_freeze_shape = c.chain.len > 1 && c.chain.image && c.chain.freeze_shape ? 1 : 0;
+    a.num_views = c.num_views;
+    for (int v = 0; v < c.num_views; ++v) {
+        const k2b_camera& cam = c.cameras[v];
+        k2b::FitView& w = a.view[v];
+        memcpy(w.r, cam.rotation, sizeof w.r);
+        memcpy(w.t, cam.translation, sizeof w.t);
+        w.fx = cam.focal[0]; w.fy = cam.focal[1];
+    }
 }
 
 // ---- surface targets: the Adam loop as pairs of launches ---------------------------------------------------------------------
@@ -341,7 +349,8 @@ int fit_world_impl(const k2b_model* model_c, const k2b_prior* prior, const k2b_f
         return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence: followup_iters=%d", c.chain.iters);
     if (c.chain.len > 1 && (c.preserve || c.tr_prior || c.grad_out || cfg->transl_prior_weight != 0.0f))
         return fail(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence: no explicit preserve pose, translation prior or gradient output in a chain");
-    if (const int rc = check_projection(cfg, c); rc != K2B_OK) return rc;
+    // (several views: the entry has checked its own form of the projection - cfg->focal is not read there)
+    if (const int rc = c.num_views > 0 ? K2B_OK : check_projection(cfg, c); rc != K2B_OK) return rc;
     const FusedEligibility el = fused_eligibility(model, prior, cfg);
     if (!el.fused) return fit_tree(model, const_cast<k2b_prior*>(prior), cfg, el.prior_dims, c);
     return fit_fused(model, prior, cfg, c);
@@ -558,6 +567,48 @@ int k2b_fit_image(const k2b_model* model, const k2b_prior* prior, const k2b_fit_
     c.out = {go_out, bp_out, be_out, tr_out};
     c.preserve = preserve; c.tr_prior = tr_prior; c.loss_out = loss_out; c.grad_out = grad_out;
     c.projected_surface = true;
+    return fit_world_impl(model, prior, cfg, c);
+}
+
+// Independent frames of 2D keypoints seen by several calibrated cameras (ABI 1.10): the shared path with FitCall::num_views set.
+// Every refusal comes before anything is queued; what the shared path would refuse about the form is refused here, by name.
+int k2b_fit_multiview(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t B, int32_t num_views,
+                      const k2b_camera* cameras, int32_t K, const int32_t* model_joint_index, const float* keypoints,
+                      const float* conf, const float* go_in, const float* bp_in, const float* be_in, const float* tr_in,
+                      const float* preserve, const float* tr_prior, float* go_out, float* bp_out, float* be_out, float* tr_out,
+                      float* loss_out, float* grad_out, void* stream) {
+    const char* who = "k2b_fit_multiview";
+    // (what concerns the views alone comes first and follows no handle)
+    if (!cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (num_views < 1 || num_views > k2b::kMaxViews)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_views=%d must be 1..%d", who, num_views, k2b::kMaxViews);
+    if (!cameras) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: cameras is NULL", who);
+    if (cfg->projection != 1)
+        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: projection=%d must be 1 (3D targets: k2b_fit_world)", who, cfg->projection);
+    for (int v = 0; v < num_views; ++v) {
+        const k2b_camera& cam = cameras[v];
+        for (int i = 0; i < 12; ++i) {
+            const float x = i < 9 ? cam.rotation[i] : cam.translation[i - 9];
+            if (!(x >= -3.402823466e38f && x <= 3.402823466e38f))      // (NaN fails the first comparison)
+                return fail(K2B_ERR_INVALID_ARGUMENT, "%s: cameras[%d].%s[%d] is not finite", who, v, i < 9 ? "rotation" : "translation",
+                            i < 9 ? i : i - 9);
+        }
+        if (const int rc = check_focal(who, cam.focal); rc != K2B_OK) return rc;
+    }
+    if (!model || !prior) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
+    if (const int rc = check_targets(who, model, K, model_joint_index); rc != K2B_OK) return rc;
+    if (!kinematic_only(model, K, model_joint_index))
+        return fail(K2B_ERR_UNSUPPORTED, "%s: surface targets (vertex-selected joints, landmarks) are not built into the multi-view "
+                    "term: model indices below %d only", who, model->J);
+    if (fused_eligibility(model, prior, cfg).fused && model->fit_scan64)
+        return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term is built for the fp32 scans only (this model has no scan plan, or "
+                    "was created under K2B_FIT_SCAN64)", who);
+    if (B > 0 && (int64_t)B * num_views * K > ((int64_t)1 << 40)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: %d x %d x %d target rows", who, B, num_views, K);
+    FitCall c = fit_call(B, K, model_joint_index, keypoints, conf, stream);
+    c.in = {go_in, bp_in, be_in, tr_in};
+    c.out = {go_out, bp_out, be_out, tr_out};
+    c.preserve = preserve; c.tr_prior = tr_prior; c.loss_out = loss_out; c.grad_out = grad_out;
+    c.num_views = num_views; c.cameras = cameras;
     return fit_world_impl(model, prior, cfg, c);
 }
 

@@ -214,9 +214,11 @@ __device__ __forceinline__ float frame_loss(float lanes, float c_y, float best, 
 // the 3D instantiations keep their symbol names: their code objects can be compared with those of any earlier build.
 template <int NBTF, int MODE, bool SCAN64>
 __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel(const FitArgs a) {
-    constexpr int NBT = NBTF & (kProjForm - 1);
+    constexpr int NBT = NBTF & kFormMask;
     constexpr bool PROJ = (NBTF & kProjForm) != 0;
+    constexpr bool VIEWS = (NBTF & kViewsForm) != 0;         // NBT | kViewsForm: the reprojection summed over FitArgs::view (k2b_fit_multiview)
     static_assert(!(PROJ && SCAN64), "the projected form is built for the fp32 scans");
+    static_assert(!(VIEWS && (SCAN64 || PROJ)), "the multi-view form is a form of its own, built for the fp32 scans");
     constexpr bool SPLIT = Shape<MODE>::SPLIT, PAIR = Shape<MODE>::PAIR;
     constexpr int NROW = Shape<MODE>::NROW, CPW = Shape<MODE>::CPW;
     constexpr bool WIDE16 = Shape<MODE>::NWAVES == 16;       // four waves per SIMD: 128 registers per lane
@@ -430,7 +432,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
     const int tk = isJ ? a.lane_target[jj] : -1;
     Vec3 tgt = {0.f, 0.f, 0.f};
     float wconf = 0.f;  // w_j^2 c^2
-    if (tk >= 0) {
+    // several views: the lane's target rows and confidences stay in memory (one row and one weight per view, re-read in every
+    // pass - L2 / L1 hits; eight views in registers would be 24 of them): nothing of them is kept here, the pass forms the row of
+    // the lane's first view from the frame and tk.
+    if (!VIEWS && tk >= 0) {
         const size_t ft = (size_t)(PAIR ? (hb ? f[FW - 1] : f[0]) : c_off);          // (a chain: its first frame)
         const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
         tgt = {y[0], y[1], y[2]};
@@ -668,7 +673,61 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         // (no branch on "this lane has a target": wconf = 0 there, so its loss and gradient vanish)
         Vec3 gj;
         float part = 0.f;                  // per-lane partial of the joint loss
-        if constexpr (PROJ) {
+        if constexpr (VIEWS) {
+            // several calibrated views (k2b.h, k2b_fit_multiview): per view q = R (p + t) + t_c, the perspective form below on q
+            // with that view's focals, and R^T pulls its gradient back to the world; g and the loss partial are sums over the views
+            // in the fixed order 0 .. C - 1.  The cameras are wave-uniform kernel arguments (scalar loads); the lane's row and
+            // confidence of a view come from memory.  As in the single-view form a pair that contributes nothing is selected out
+            // (confidence 0, or no target), q_z is divided by as it stands and every fused operation is pinned: one sequence of
+            // roundings in every launch shape.
+            // (the paired shape has no three registers for p + t beside p: there the translation is read again in every view - the same
+            //  sum, formed later - and the empty asm keeps that read inside the loop)
+            constexpr bool LEAN = PAIR && !SPLIT;
+            const float Px0 = pj.x + tr.x, Py0 = pj.y + tr.y, Pz0 = pj.z + tr.z;
+            const float jw2 = a.joint_w * a.joint_w;
+            float ax = 0.f, ay = 0.f, az = 0.f;
+            // (the lane number enters through an empty asm: what is derived from it - the frame's first row, byte offsets 64 bits wide -
+            //  is formed here, in every pass, and not hoisted into registers that would stay live across the whole iteration loop.
+            //  A lane without a target reads target 0's and is selected out.  The row is a 32-bit index behind the launch's uniform base
+            //  pointers: launch_fit_world keeps a launch's rows below 2^27.)
+            int vl = lane;
+            asm volatile("" : "+v"(vl));
+            const unsigned ft = (unsigned)(PAIR ? ((vl >> 5) ? f[FW - 1] : f[0]) : f[0]);
+            const unsigned row = ft * (unsigned)(a.num_views * a.num_targets) + (tk >= 0 ? tk : 0);
+            for (int c = 0; c < a.num_views; ++c) {
+                const FitView& vw = a.view[c];
+                float Px = Px0, Py = Py0, Pz = Pz0;
+                if constexpr (LEAN) {
+                    int tro = XS_TRANSL;
+                    asm volatile("" : "+v"(tro));
+                    const float4 t4 = *reinterpret_cast<const float4*>(xs_t + tro);
+                    Px = pj.x + t4.x; Py = pj.y + t4.y; Pz = pj.z + t4.z;
+                }
+                const unsigned crow = a.conf_per_frame ? row : (tk >= 0 ? tk : 0);
+                const float* ty = a.j3d + (size_t)c * a.num_targets * 3;       // (uniform: view c of the launch's first frame)
+                const float tu = ty[3 * row], tv = ty[3 * row + 1];
+                const float cf = a.conf ? (a.conf + (size_t)c * a.num_targets)[crow] : 1.0f;
+                const float wc = jw2 * (cf * cf);
+                const bool on = tk >= 0 && wc != 0.f;
+                const float qx = __builtin_fmaf(vw.r[0], Px, __builtin_fmaf(vw.r[1], Py, __builtin_fmaf(vw.r[2], Pz, vw.t[0])));
+                const float qy = __builtin_fmaf(vw.r[3], Px, __builtin_fmaf(vw.r[4], Py, __builtin_fmaf(vw.r[5], Pz, vw.t[1])));
+                const float qz = __builtin_fmaf(vw.r[6], Px, __builtin_fmaf(vw.r[7], Py, __builtin_fmaf(vw.r[8], Pz, vw.t[2])));
+                const float iz = 1.0f / qz;
+                const float ex = __builtin_fmaf(vw.fx * qx, iz, -tu), ey = __builtin_fmaf(vw.fy * qy, iz, -tv);
+                const float x2 = ex * ex, y2 = ey * ey;
+                const float dx = s2 + x2, dy = s2 + y2;
+                const float k2 = 2.f * wc * (s2 * s2);
+                float gx = vw.fx * (k2 * ex * fast_rcp(dx * dx)) * iz, gy = vw.fy * (k2 * ey * fast_rcp(dy * dy)) * iz;
+                float gz = -__builtin_fmaf(qx, gx, qy * gy) * iz;
+                gx = on ? gx : 0.f; gy = on ? gy : 0.f; gz = on ? gz : 0.f;
+                ax = __builtin_fmaf(vw.r[6], gz, __builtin_fmaf(vw.r[3], gy, __builtin_fmaf(vw.r[0], gx, ax)));
+                ay = __builtin_fmaf(vw.r[7], gz, __builtin_fmaf(vw.r[4], gy, __builtin_fmaf(vw.r[1], gx, ay)));
+                az = __builtin_fmaf(vw.r[8], gz, __builtin_fmaf(vw.r[5], gy, __builtin_fmaf(vw.r[2], gx, az)));
+                // (the loss behind the gradient: its two divisions then find the residuals' registers free)
+                if (last) part += on ? wc * ((s2 * x2) / dx + (s2 * y2) / dy) : 0.f;
+            }
+            gj = {ax, ay, az};
+        } else if constexpr (PROJ) {
             // perspective form (k2b.h, k2b_fit_config::projection): e = (fx X / Z - u', fy Y / Z - v') with (X, Y, Z) = p + t and
             // the target row (u', v', ignored) in centred pixels; g = J^T d with d = d gmof / d e as below.  Z is divided by as it
             // stands (no clamp), so a lane that contributes nothing is SELECTED out, not multiplied by wconf = 0: beyond the tree
@@ -1463,9 +1522,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
 static FitArgs frame_range(const FitArgs& a, int f0, int n) {
     FitArgs r = a;
     const size_t f = (size_t)f0, P = (size_t)(3 + D + a.num_betas + 3);
+    const size_t rows = (size_t)a.num_targets * (a.num_views > 0 ? a.num_views : 1);     // target rows of a frame (several views: [view][target])
     r.num_frames = n;
-    r.j3d = a.j3d + f * a.num_targets * 3;
-    if (a.conf && a.conf_per_frame) r.conf = a.conf + f * a.num_targets;
+    r.j3d = a.j3d + f * rows * 3;
+    if (a.conf && a.conf_per_frame) r.conf = a.conf + f * rows;
     r.go_in = a.go_in + f * 3; r.bp_in = a.bp_in + f * D; r.be_in = a.be_in + f * a.num_betas; r.tr_in = a.tr_in + f * 3;
     if (a.preserve) r.preserve = a.preserve + f * D;
     if (a.tr_prior) r.tr_prior = a.tr_prior + f * 3;
@@ -1480,6 +1540,11 @@ template <int MODE>
 static void launch_shape(const FitLaunch& l, const FitArgs& a, hipStream_t stream) {
     const dim3 grid(l.grid), block(l.block_threads);
     if constexpr (MODE != MODE_SPLIT_LBFGS) {
+        if (a.num_views > 0) {
+            if (l.NBT == 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10 | kViewsForm, MODE, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k2b_fit_world_kernel<16 | kViewsForm, MODE, false>), grid, block, 0, stream, a);
+            return;
+        }
         if (a.projection) {
             if (l.NBT == 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10 | kProjForm, MODE, false>), grid, block, 0, stream, a);
             else hipLaunchKernelGGL((k2b_fit_world_kernel<16 | kProjForm, MODE, false>), grid, block, 0, stream, a);
@@ -1502,6 +1567,12 @@ hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
     if (!plan.ok) return hipErrorInvalidValue;       // lb_mode and the batch disagree: the caller asks lbfgs_scheme_for first
     // the projected term is instantiated for fp32 scans and Adam only (the entries refuse the rest by name)
     if (a_in.projection && (a_in.scan64 || a_in.lb_mode != LbMode::none)) return hipErrorInvalidValue;
+    // the multi-view term likewise, for independent frames
+    if (a_in.num_views != 0 && (a_in.num_views < 0 || a_in.num_views > kMaxViews || a_in.scan64 || a_in.lb_mode != LbMode::none || a_in.chain_len > 1))
+        return hipErrorInvalidValue;
+    // (a lane addresses its views' target rows by a 32-bit index behind its launch's base: checked before the first launch)
+    for (int i = 0; a_in.num_views > 0 && i < plan.num_launches; ++i)
+        if ((size_t)plan.launch[i].num_frames * a_in.num_views * a_in.num_targets >= ((size_t)1 << 27)) return hipErrorInvalidValue;
     for (int i = 0; i < plan.num_launches; ++i) {
         const FitLaunch& l = plan.launch[i];
         FitArgs a = frame_range(a_in, l.first_frame, l.num_frames);

@@ -47,8 +47,10 @@ __device__ __forceinline__ double shfl64(double v, int src) { return bperm64(src
 // their symbol names); CHAIN: warm-start chains (the projected ones also read FitTreeArgs::chain_freeze_shape)
 template <int NSF, bool CHAIN>
 __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs a) {
-    constexpr int NS = NSF & (kProjForm - 1);
+    constexpr int NS = NSF & kFormMask;
     constexpr bool PROJ = (NSF & kProjForm) != 0;
+    constexpr bool VIEWS = (NSF & kViewsForm) != 0;          // NS | kViewsForm: the reprojection summed over FitTreeArgs::view (k2b_fit_multiview)
+    static_assert(!(VIEWS && (PROJ || CHAIN)), "the multi-view form is a form of its own, for independent frames");
     extern __shared__ __attribute__((aligned(16))) float tlds[];
     // [8][16][64] half8 A fragments (128 KiB) | [M][64] h | [M][64] b | [M][64] mu | [TW][64] theta_v fp32 |
     // [TW][hi 64 | lo 64] theta_v f16 | [TW][M][64] y' | [TW][M] q | [M] constants | [M] 1 / scale
@@ -194,6 +196,17 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     // target of this joint
     const int tk = isJ ? a.lane_target[lane] : -1;
     float ty0 = 0.f, ty1 = 0.f, ty2 = 0.f, wconf = 0.f;
+    // several views: the lane's rows and confidences stay in memory and are re-read in every pass (k2b_fit.hip has the reason);
+    // here the addresses of its first view's
+    const float* vw_y = nullptr;
+    const float* vw_c = nullptr;
+    if constexpr (VIEWS) {
+        if (tk >= 0) {
+            const size_t row = (size_t)c_off * a.num_views * a.num_targets + tk;
+            vw_y = a.j3d + row * 3;
+            if (a.conf) vw_c = a.conf + (a.conf_per_frame ? row : (size_t)tk);
+        }
+    } else
     if (tk >= 0) {
         const size_t f0 = (size_t)c_off;                 // (a chain: its first frame)
         const float* y = a.j3d + (f0 * a.num_targets + tk) * 3;
@@ -354,7 +367,38 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
         const float t0 = read_lane(tr, 0), t1 = read_lane(tr, 1), t2 = read_lane(tr, 2);
         float lj = 0.f;
         Vec3 g = {0.f, 0.f, 0.f};
-        if constexpr (PROJ) {
+        if constexpr (VIEWS) {
+            // several calibrated views (k2b.h, k2b_fit_multiview): per view q = R (p + t) + t_c, the perspective form below on q with
+            // that view's focals, R^T pulls its gradient back; g and the loss are sums over the views in the fixed order 0 .. C - 1.
+            // The operations and their order are k2b_fit.hip's.
+            if (tk >= 0) {
+                const float Px = pg.x + t0, Py = pg.y + t1, Pz = pg.z + t2;
+                const float jw2 = a.joint_w * a.joint_w;
+                const int K3 = a.num_targets * 3;
+                for (int c = 0; c < a.num_views; ++c) {
+                    const FitView& vw = a.view[c];
+                    const float cf = vw_c ? vw_c[(size_t)c * a.num_targets] : 1.0f;
+                    const float wc = jw2 * (cf * cf);
+                    if (wc != 0.f) {
+                        const float tu = vw_y[(size_t)c * K3], tv = vw_y[(size_t)c * K3 + 1];
+                        const float qx = __builtin_fmaf(vw.r[0], Px, __builtin_fmaf(vw.r[1], Py, __builtin_fmaf(vw.r[2], Pz, vw.t[0])));
+                        const float qy = __builtin_fmaf(vw.r[3], Px, __builtin_fmaf(vw.r[4], Py, __builtin_fmaf(vw.r[5], Pz, vw.t[1])));
+                        const float qz = __builtin_fmaf(vw.r[6], Px, __builtin_fmaf(vw.r[7], Py, __builtin_fmaf(vw.r[8], Pz, vw.t[2])));
+                        const float iz = 1.0f / qz;
+                        const float ex = __builtin_fmaf(vw.fx * qx, iz, -tu), ey = __builtin_fmaf(vw.fy * qy, iz, -tv);
+                        const float x2 = ex * ex, y2 = ey * ey;
+                        const float dqx = s2 + x2, dqy = s2 + y2;
+                        if (it == nit - 1) lj += wc * ((s2 * x2) / dqx + (s2 * y2) / dqy);
+                        const float k2 = 2.f * wc * (s2 * s2);
+                        const float gx = vw.fx * (k2 * ex * fast_rcp(dqx * dqx)) * iz, gy = vw.fy * (k2 * ey * fast_rcp(dqy * dqy)) * iz;
+                        const float gz = -__builtin_fmaf(qx, gx, qy * gy) * iz;
+                        g.x = __builtin_fmaf(vw.r[6], gz, __builtin_fmaf(vw.r[3], gy, __builtin_fmaf(vw.r[0], gx, g.x)));
+                        g.y = __builtin_fmaf(vw.r[7], gz, __builtin_fmaf(vw.r[4], gy, __builtin_fmaf(vw.r[1], gx, g.y)));
+                        g.z = __builtin_fmaf(vw.r[8], gz, __builtin_fmaf(vw.r[5], gy, __builtin_fmaf(vw.r[2], gx, g.z)));
+                    }
+                }
+            }
+        } else if constexpr (PROJ) {
             // perspective form (k2b.h, k2b_fit_config::projection): e = (fx X / Z - u', fy Y / Z - v'), (X, Y, Z) = p + t, the target
             // row (u', v', ignored) in centred pixels; g = J^T d.  Z is divided by as it stands, so a target of confidence 0 is
             // left out by the branch, not by its weight (0 . inf at Z = 0).  1 / Z is the IEEE division (k2b_fit.hip has the reason).
@@ -523,6 +567,7 @@ hipError_t launch_tree(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, h
 }
 template <int NS>
 hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
+    if (a.num_views > 0) return p.chain ? hipErrorInvalidValue : launch_tree<NS | kViewsForm, false>(p, lds, a, stream);
     if (a.projection) return p.chain ? launch_tree<NS | kProjForm, true>(p, lds, a, stream) : launch_tree<NS | kProjForm, false>(p, lds, a, stream);
     return p.chain ? launch_tree<NS, true>(p, lds, a, stream) : launch_tree<NS, false>(p, lds, a, stream);
 }
@@ -533,6 +578,7 @@ hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a
 hipError_t launch_fit_tree(const FitTreeArgs& a_in, int num_cus, hipStream_t stream) {
     if (a_in.num_frames <= 0) return hipSuccess;
     if (a_in.num_joints > 64 || a_in.num_shape > 32 || a_in.prior_dims > 64 || a_in.num_gauss > TMG) return hipErrorInvalidValue;
+    if (a_in.num_views < 0 || a_in.num_views > kMaxViews) return hipErrorInvalidValue;
     const size_t lds = (size_t)(TMG * 16 * 64 * 4 + 3 * TMG * 64 + 2 * TW * 64 + TW * TMG * 64 + TW * TMG + 2 * TMG) * sizeof(float);
     const FitTreePlan p = plan_fit_tree(a_in.num_frames, num_cus, a_in.num_shape, a_in.chain_len > 1, a_in.debug_shape);
     FitTreeArgs a = a_in;

@@ -233,6 +233,10 @@ struct FitCall {
     struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
     // set by k2b_fit_image alone: surface targets are allowed under projection (the projected form of k2b_surface.hip)
     bool projected_surface = false;
+    // set by k2b_fit_multiview alone: the joint term summed over num_views calibrated cameras (HOST table, checked by the entry;
+    // targets [B][views][K][3], conf [views][K] or [B][views][K]); cfg->focal is not read then
+    int num_views = 0;
+    const k2b_camera* cameras = nullptr;
 };
 // what every entry knows of its call; the parameter arrays and the outputs are set by name
 inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, void* stream) {

@@ -16,6 +16,13 @@ constexpr int kMaxJoints = 64;
 // The fit kernels' joint term has two forms, the 3D residual and the perspective reprojection of k2b_fit_config::projection.  The
 // projected instantiations carry this bit in their first template argument (the shape-coefficient capacity, <= 32).
 constexpr int kProjForm = 256;
+// A third form (k2b_fit_multiview): the reprojection residual summed over up to kMaxViews calibrated cameras, a run-time loop over
+// FitArgs::view inside the joint term.  It rides in the first template argument as kProjForm does (never together with it).
+constexpr int kViewsForm = 512;
+constexpr int kFormMask = kProjForm - 1;      // the capacity under the form bits
+constexpr int kMaxViews = 8;
+// one camera of a multi-view call as the kernels read it (k2b.h, k2b_camera): q = r (p + transl) + t, pixels = (fx q_x, fy q_y) / q_z
+struct FitView { float r[9], t[3], fx, fy; };
 // the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api_prior.hip):
 //   [m][tile 4][ks0 hi, ks1 hi, ks0 lo, ks1 lo][64 lanes][8 halfs]
 constexpr int kPriorFrag32Halfs = kPriorMaxGauss * 4 * 4 * 64 * 8;
@@ -93,6 +100,10 @@ struct FitArgs {
     // projected chains (k2b_fit_image_sequences): 1 = the steps > 0 of a chain hold the shape group as freeze_betas does (a video's
     // shape is estimated on its first frame).  Last, and read by the projected instantiations only: every other argument keeps its offset.
     int chain_freeze_shape;
+    // several views (k2b_fit_multiview; 0 = one of the forms above): targets [frame][view][target][3], conf [view][target] or
+    // [frame][view][target], the cameras by value.  Behind everything else and read by the kViewsForm instantiations only.
+    int num_views;
+    FitView view[kMaxViews];
 };
 
 hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
@@ -136,6 +147,8 @@ struct FitTreeArgs {
     int projection;              // as FitArgs::projection, focal_x, focal_y
     float focal_x, focal_y;
     int chain_freeze_shape;      // as FitArgs::chain_freeze_shape: steps > 0 freeze the first num_betas_prior coefficients (the expression stays free)
+    int num_views;               // as FitArgs::num_views, view
+    FitView view[kMaxViews];
 };
 hipError_t launch_fit_tree(const FitTreeArgs& a, int num_cus, hipStream_t stream);
 

@@ -52,6 +52,12 @@ class FitConfigC(C.Structure):
     ]
 
 
+class CameraC(C.Structure):
+    """Mirror of ``k2b_camera`` (include/k2b.h): row-major world-to-camera rotation, translation, focals in pixels."""
+
+    _fields_ = [("rotation", C.c_float * 9), ("translation", C.c_float * 3), ("focal", C.c_float * 2)]
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -105,6 +111,8 @@ _PROTOTYPES = (
     ("k2b_fit_image_sequences", C.c_int, _FIT_HEAD + (_i32, _vp, _vp, _i32, _i32) + _FIT_IN + _FIT_OUT + _STREAM),
     ("k2b_fit_image", C.c_int, _FIT_HEAD + (_i32,) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + _STREAM),
     ("k2b_surface_term_image", C.c_int, (_vp, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp) + (_vp,) * 6 + _STREAM),
+    ("k2b_camera_size", C.c_uint32, ()),
+    ("k2b_fit_multiview", C.c_int, _FIT_HEAD + (_i32, _i32, C.POINTER(CameraC)) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -126,6 +134,8 @@ def load_library():
         fn.restype, fn.argtypes = restype, list(argtypes)
         if name == "k2b_fit_config_size" and fn() != C.sizeof(FitConfigC):     # before any prototype that takes the struct is used
             raise RuntimeError("libk2b.so was built with a different k2b_fit_config layout than native.FitConfigC")
+        if name == "k2b_camera_size" and fn() != C.sizeof(CameraC):
+            raise RuntimeError("libk2b.so was built with a different k2b_camera layout than native.CameraC")
     _lib = lib
     return lib
 
@@ -372,20 +382,22 @@ def _lbfgs_tail(history_size, lr, tolerance_grad, tolerance_change):
 
 
 def _fit_call(name: str, model: NativeModel, prior: NativePrior, cfg: FitConfigC, head: tuple, idx: np.ndarray, lead: tuple,
-              starts: int, j3d, conf, global_orient, body_pose, betas, transl, tail: tuple = (), world: Optional[tuple] = None):
+              starts: int, j3d, conf, global_orient, body_pose, betas, transl, tail: tuple = (), world: Optional[tuple] = None,
+              out_lead: Optional[tuple] = None):
     """Set-up and launch of every fit entry.  The C arguments are (model, prior, cfg, *`head`, K, joint index, targets of
     leading shape `lead`, confidences, `starts` rows of start parameters, [preserve_pose, transl_prior_target], the five
     outputs, [grad], *`tail`, stream); the bracketed ones belong to ``k2b_fit_world*`` and come with
-    `world` = (preserve_pose, transl_prior_target, want_grad)."""
+    `world` = (preserve_pose, transl_prior_target, want_grad).  `out_lead`: the leading shape of the outputs where it is not
+    `lead` (several views: targets (B, C, K, 3), shared confidences (C, K), outputs (B, .))."""
     dev, K = model.device, idx.shape[0]
-    conf_p = _dev(conf, "conf", dev, lead + (K,) if cfg.conf_per_frame else (K,))
+    conf_p = _dev(conf, "conf", dev, lead + (K,) if cfg.conf_per_frame else lead[len(lead if out_lead is None else out_lead):] + (K,))
     ins = [_dev(j3d, "j3d", dev, lead + (K, 3)), conf_p, *_param_ptrs(model, starts, global_orient, body_pose, betas, transl)]
     want_grad = False
     if world is not None:
         preserve_pose, transl_prior_target, want_grad = world
         ins += [_dev(preserve_pose, "preserve_pose", dev, (starts, _param_widths(model)[1])),
                 _dev(transl_prior_target, "transl_prior_target", dev, (starts, 3))]
-    out = _fit_outputs(model, lead, want_grad)
+    out = _fit_outputs(model, lead if out_lead is None else out_lead, want_grad)
     outs = [_ptr(out[k]) for k in PARAM_KEYS + ("loss",)]
     if world is not None:
         outs.append(_ptr(out.get("grad")))
@@ -413,6 +425,35 @@ def fit_image(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joi
     B = keypoints.shape[0]
     return _fit_call("k2b_fit_image", model, prior, cfg, (B,), _joint_index(model_joint_index, keypoints.shape[1]), (B,), B,
                      keypoints, conf, global_orient, body_pose, betas, transl, world=(preserve_pose, transl_prior_target, want_grad))
+
+
+def camera_table(cameras) -> C.Array:
+    """Host table of ``CameraC`` from rows ``(rotation (3,3) or (9,), translation (3,), focal (2,))``; values are rounded to
+    float32 here and checked by the entry."""
+    table = (CameraC * len(cameras))()
+    for slot, (rotation, translation, focal) in zip(table, cameras):
+        slot.rotation[:] = np.asarray(rotation, dtype=np.float64).reshape(9).astype(np.float32).tolist()
+        slot.translation[:] = np.asarray(translation, dtype=np.float64).reshape(3).astype(np.float32).tolist()
+        slot.focal[:] = np.asarray(focal, dtype=np.float64).reshape(2).astype(np.float32).tolist()
+    return table
+
+
+def fit_multiview(model: NativeModel, prior: NativePrior, cfg: FitConfigC, cameras, model_joint_index: Sequence[int],
+                  keypoints: torch.Tensor, conf: Optional[torch.Tensor], global_orient: torch.Tensor, body_pose: torch.Tensor,
+                  betas: torch.Tensor, transl: torch.Tensor, preserve_pose: Optional[torch.Tensor] = None,
+                  want_grad: bool = False, transl_prior_target: Optional[torch.Tensor] = None):
+    """Independent frames of 2D keypoints seen by C calibrated cameras (``k2b_fit_multiview``): `cameras` a ``CameraC`` array
+    (``camera_table``) or rows for one, `keypoints` (B, C, K, 3) rows (u - cx_c, v - cy_c, ignored), `conf` (C, K) or, with
+    ``cfg.conf_per_frame``, (B, C, K); `transl` is the body's world translation.  One launch for all iterations."""
+    table = cameras if isinstance(cameras, C.Array) else camera_table(cameras)
+    if keypoints.dim() != 4:
+        raise ValueError(f"keypoints must be (B, C, K, 3), got {tuple(keypoints.shape)}")
+    B, V = keypoints.shape[0], keypoints.shape[1]
+    if V != len(table):
+        raise ValueError(f"keypoints has {V} views for {len(table)} cameras")
+    return _fit_call("k2b_fit_multiview", model, prior, cfg, (B, V, table), _joint_index(model_joint_index, keypoints.shape[2]), (B, V), B,
+                     keypoints, conf, global_orient, body_pose, betas, transl, world=(preserve_pose, transl_prior_target, want_grad),
+                     out_lead=(B,))
 
 
 def fit_world_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, model_joint_index: Sequence[int],
