@@ -74,6 +74,12 @@ int lbfgs_drive(k2b::LbfgsScheme scheme, int rounds, int launches, Launch&& laun
     return K2B_OK;
 }
 
+// whether the fused kernel takes the frames of a call with the L-BFGS step inside: 24-joint model, the prior over the whole pose,
+// kinematic targets only
+bool fused_takes(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& c) {
+    return k2b::rules::fused_eligibility(fit_facts(model, prior), *cfg).fused && k2b::rules::kinematic_only(model->J, c.K, c.model_joint_index);
+}
+
 // One device-driven L-BFGS fit of the frames of `at`, whose start is ALREADY in the parameter arrays at.out (in place): state
 // cleared, then the schedule of its scheme.  `w` = the optimiser's part of stream-ordered scratch, at.preserve / at.tr_prior =
 // preserve pose / translation prior centre (device, outside the arrays).
@@ -94,8 +100,7 @@ int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_conf
     // One launch per round where the fused kernel takes the frames (24-joint model, the prior over the whole pose, kinematic
     // targets only, at most four frames per CU - lbfgs_scheme_for, k2b_launch_plan.h), otherwise two launches per round.
     const int stage_cap = lbfgs_stage_cap();
-    const bool fused_ok = fused_eligibility(model, prior, cfg).fused && kinematic_only(model, at.K, at.model_joint_index);
-    const k2b::LbfgsScheme scheme = k2b::lbfgs_scheme_for(B, device_cus(), fused_ok, stage_cap, lbfgs_scheme());
+    const k2b::LbfgsScheme scheme = k2b::lbfgs_scheme_for(B, device_cus(), fused_takes(model, prior, cfg, at), stage_cap, lbfgs_scheme());
     // the optimiser's arguments travel in the launch's own arguments: [0] reads result buffer A, [1] reads B
     const k2b::LbfgsArgs la = make_lbfgs_args(B, model, o, at.out, w);
     k2b::LbfgsArgs both[2] = {la, la};
@@ -119,27 +124,21 @@ int lbfgs_run(const k2b_model* model, const k2b_prior* prior, const k2b_fit_conf
     });
 }
 
-// What the entries check alike, in the order they always have: the handles, the iteration count, the history, the step length,
-// the model's width, and in a chain (`followup`) the follow-up count.  Fills the widths and the history cut.
+// The widths and the history cut of an accepted call.
 struct LbfgsDims { int D, NB, P, history, H; };      // history: the caller's (0: the default), H: what the longest fit can fill of it
-int lbfgs_preamble(const char* who, const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int max_iter,
-                   const int* followup, int history_size, double lr, LbfgsDims* d) {
-    if (!model || !prior || !cfg) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
-    if (const int rc = refuse_projection(who, cfg); rc != K2B_OK) return rc;
-    if (max_iter < 1 || max_iter > 10000) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: max_iter=%d", who, max_iter);
-    if (history_size <= 0) history_size = k2b::kLbfgsMaxHistory;
-    if (history_size > k2b::kLbfgsMaxHistory)
-        return fail(K2B_ERR_UNSUPPORTED, "%s: history_size=%d (at most %d)", who, history_size, k2b::kLbfgsMaxHistory);
-    if (!(lr > 0.0)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: lr must be positive", who);
-    d->D = 3 * (model->J - 1); d->NB = model->NB; d->P = 3 + d->D + d->NB + 3;
-    if (d->P > 256) return fail(K2B_ERR_UNSUPPORTED, "%s: %d parameters per frame (at most 256)", who, d->P);
-    if (followup && (*followup < 1 || *followup > 10000)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, *followup);
-    d->history = history_size;
-    d->H = k2b::lbfgs_history_cut(history_size, followup && *followup > max_iter ? *followup : max_iter);
-    return K2B_OK;
+LbfgsDims lbfgs_dims(const k2b_model* model, int max_iter, int followup_iters, int history_size) {
+    LbfgsDims d;
+    d.D = 3 * (model->J - 1); d.NB = model->NB; d.P = 3 + d.D + d.NB + 3;
+    d.history = history_size > 0 ? history_size : k2b::kLbfgsMaxHistory;
+    d.H = k2b::lbfgs_history_cut(d.history, followup_iters > max_iter ? followup_iters : max_iter);
+    return d;
 }
-bool any_null(const ConstParams& in, const Params& out) {
-    return !in.go || !in.bp || !in.be || !in.tr || !out.go || !out.bp || !out.be || !out.tr;
+// the entry's call as the rules see it (k2b_fit_rules.h), with the L-BFGS numbers
+k2b::rules::Call lbfgs_rule_call(k2b::rules::Entry entry, const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& c,
+                                 k2b::rules::Facts* facts, int max_iter, int followup_iters, int history_size, double lr) {
+    k2b::rules::Call r = rule_call(entry, model, prior, cfg, c, facts);
+    r.max_iter = max_iter; r.followup_iters = followup_iters; r.history_size = history_size; r.lr = lr;
+    return r;
 }
 
 // The default sequence mode in ONE launch (k2b_fit.hip: chain + LbMode::persistent): the frame loop runs inside the persistent launch -
@@ -170,13 +169,16 @@ int k2b_fit_world_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const 
                         int32_t max_iter, int32_t history_size, double lr, double tolerance_grad, double tolerance_change,
                         void* stream_v) {
     const char* who = "k2b_fit_world_lbfgs";
-    LbfgsDims d;
-    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, max_iter, nullptr, history_size, lr, &d); rc != K2B_OK) return rc;
-    if (B < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_frames=%d", who, B);
-    if (B == 0) return K2B_OK;
     const ConstParams in{go_in, bp_in, be_in, tr_in};
     const Params out{go_out, bp_out, be_out, tr_out};
-    if (any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter buffer", who);
+    FitCall at = fit_call(B, K, model_joint_index, j3d, conf, in, out, loss_out, stream_v);
+    at.preserve = preserve; at.tr_prior = tr_prior; at.grad_out = grad_out;
+    k2b::rules::Facts facts;
+    bool go;
+    if (const int rc = judge(lbfgs_rule_call(k2b::rules::Entry::fit_world_lbfgs, model_c, prior, cfg, at, &facts, max_iter, 0, history_size, lr), &go);
+        rc != K2B_OK || !go)
+        return rc;
+    const LbfgsDims d = lbfgs_dims(model_c, max_iter, 0, history_size);
     hipStream_t stream = (hipStream_t)stream_v;
     // stream-ordered workspace: optimiser state, closure results, the preserve pose and the translation prior's centre (their
     // defaults are the INITIAL parameters, which the parameter arrays stop holding after the first step)
@@ -186,9 +188,7 @@ int k2b_fit_world_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const 
     LbfgsWs w{ws.get(), m.opt, false};
     float *pres = ws_at<float>(ws.get(), m.preserve), *trp = ws_at<float>(ws.get(), m.tr_prior);
     HIP_TRY_MSG(start_in_place(B, d.D, d.NB, in, out, preserve, tr_prior, pres, trp, stream), "%s: HIP call failed", who);
-    FitCall at = fit_call(B, K, model_joint_index, j3d, conf, stream_v);
-    at.out = out;
-    at.preserve = pres; at.loss_out = loss_out; at.grad_out = grad_out;
+    at.preserve = pres;
     at.tr_prior = (tr_prior || cfg->transl_prior_weight != 0.0f) ? trp : nullptr;   // (the tree kernel has no translation prior)
     return lbfgs_run(model_c, prior, cfg, at, {max_iter, d.H, lr, tolerance_grad, tolerance_change}, w);
 }
@@ -203,15 +203,16 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
                            const float* bp_in, const float* be_in, const float* tr_in, float* go_out, float* bp_out, float* be_out,
                            float* tr_out, float* loss_out, int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr,
                            double tolerance_grad, double tolerance_change, void* stream_v) {
-    const char* who = "k2b_fit_sequence_lbfgs";
-    LbfgsDims d;
-    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, first_iters, &followup_iters, history_size, lr, &d); rc != K2B_OK) return rc;
-    if (T < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: frames=%d", who, T);
-    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_UNSUPPORTED, "%s: no translation prior in a chain", who);
-    if (T == 0) return K2B_OK;
     const ConstParams in{go_in, bp_in, be_in, tr_in};
     const Params out{go_out, bp_out, be_out, tr_out};
-    if (!j3d || any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    k2b::rules::Facts facts;
+    bool go;
+    if (const int rc = judge(lbfgs_rule_call(k2b::rules::Entry::fit_sequence_lbfgs, model_c, prior, cfg,
+                                             fit_call(T, K, model_joint_index, j3d, conf, in, out, loss_out, stream_v), &facts, first_iters,
+                                             followup_iters, history_size, lr), &go);
+        rc != K2B_OK || !go)
+        return rc;
+    const LbfgsDims d = lbfgs_dims(model_c, first_iters, followup_iters, history_size);
     hipStream_t stream = (hipStream_t)stream_v;
     const int D = d.D, NB = d.NB;
     const k2b::LbfgsSequenceMap m = k2b::lbfgs_sequence_map(d.P, D, d.H);
@@ -222,13 +223,10 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
     float* pres = ws_at<float>(ws.get(), m.preserve);
     // the whole sequence in ONE launch where the fused kernel takes it (24-joint model, the prior over the whole pose, kinematic targets)
     // (one sequence = one chain slot; any K2B_LBFGS_SCHEME but 0 keeps it out of the chain)
-    const bool fused_ok = fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index);
+    FitCall c = fit_call(1, K, model_joint_index, j3d, conf, in, out, loss_out, stream_v);       // rows t of the outputs: frame t's point
     if (lbfgs_scheme() == 0 && T > 1 &&
-        k2b::lbfgs_scheme_for(1, device_cus(), fused_ok, lbfgs_stage_cap(), 0) == k2b::LbfgsScheme::persistent) {
-        FitCall c = fit_call(1, K, model_joint_index, j3d, conf, stream_v);
-        c.in = in;
-        c.out = out;                                                          // rows t of the outputs: frame t's point
-        c.loss_out = loss_out; c.chain.len = T;
+        k2b::lbfgs_scheme_for(1, device_cus(), fused_takes(model_c, prior, cfg, c), lbfgs_stage_cap(), 0) == k2b::LbfgsScheme::persistent) {
+        c.chain.len = T;
         const k2b::LbfgsArgs la = make_lbfgs_args(1, model_c, {first_iters, d.H, lr, tolerance_grad, tolerance_change}, c.out, w);
         TRY_Q(w.clear(stream));
         return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
@@ -246,8 +244,9 @@ int k2b_fit_sequence_lbfgs(const k2b_model* model_c, const k2b_prior* prior, con
         fc.pose_preserve_weight = t ? cfg->pose_preserve_weight : 0.0f;
         const int iters = t ? followup_iters : first_iters;
         FitCall at = fit_call(1, K, model_joint_index, j3d + (size_t)t * K * 3,
-                              conf ? conf + (cfg->conf_per_frame ? (size_t)t * K : 0) : nullptr, stream_v);
-        at.out = {go, bp, be, tr}; at.preserve = pres; at.loss_out = loss_out ? loss_out + t : nullptr;
+                              conf ? conf + (cfg->conf_per_frame ? (size_t)t * K : 0) : nullptr, {}, {go, bp, be, tr},
+                              loss_out ? loss_out + t : nullptr, stream_v);
+        at.preserve = pres;
         const LbfgsOpts o{iters, k2b::lbfgs_history_cut(d.history, iters), lr, tolerance_grad, tolerance_change};
         if (const int rc = lbfgs_run(model_c, prior, &fc, at, o, w); rc != K2B_OK) return rc;
     }
@@ -265,18 +264,16 @@ int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, co
                             int32_t first_iters, int32_t followup_iters, int32_t history_size, double lr, double tolerance_grad,
                             double tolerance_change, void* stream_v) {
     const char* who = "k2b_fit_sequences_lbfgs";
-    RaggedSlots r;
-    if (const int rc = ragged_slots(who, num_sequences, lengths, offsets, &r); rc != K2B_OK) return rc;
-    LbfgsDims d;
-    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, first_iters, &followup_iters, history_size, lr, &d); rc != K2B_OK) return rc;
-    if (cfg->transl_prior_weight != 0.0f) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
-    if (const int rc = check_targets(who, model_c, K, model_joint_index); rc != K2B_OK) return rc;
-    if (r.slots == 0) return K2B_OK;
-    const ConstParams in{go_in, bp_in, be_in, tr_in};
-    const Params out{go_out, bp_out, be_out, tr_out};
-    if (!j3d || any_null(in, out)) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
-    if (!(fused_eligibility(model_c, prior, cfg).fused && kinematic_only(model_c, K, model_joint_index)))
-        return fail(K2B_ERR_UNSUPPORTED, "%s: one launch needs the 24-joint model, the prior over the whole pose and kinematic targets", who);
+    // (rows of the outputs: each frame's point)
+    FitCall c = fit_call(0, K, model_joint_index, j3d, conf, {go_in, bp_in, be_in, tr_in}, {go_out, bp_out, be_out, tr_out}, loss_out, stream_v);
+    k2b::rules::Facts facts;
+    k2b::rules::Call call = lbfgs_rule_call(k2b::rules::Entry::fit_sequences_lbfgs, model_c, prior, cfg, c, &facts, first_iters, followup_iters,
+                                            history_size, lr);
+    call.num_sequences = num_sequences; call.lengths = lengths; call.offsets = offsets;
+    bool go;
+    if (const int rc = judge(call, &go); rc != K2B_OK || !go) return rc;
+    const k2b::rules::RaggedSlots r = k2b::rules::ragged_order(num_sequences, lengths, offsets);
+    const LbfgsDims d = lbfgs_dims(model_c, first_iters, followup_iters, history_size);
     hipStream_t stream = (hipStream_t)stream_v;
     const k2b::LbfgsSequencesMap m = k2b::lbfgs_sequences_map(r.slots, d.P, d.H);
     StreamWorkspace ws(stream);
@@ -286,10 +283,7 @@ int k2b_fit_sequences_lbfgs(const k2b_model* model_c, const k2b_prior* prior, co
     const LbfgsWs w{ws.get(), m.opt, false};
     HIP_TRY_MSG(w.clear(stream), "%s: HIP call failed", who);
     // as k2b_fit_sequence_lbfgs's one-launch chain, with one optimiser instance per chain slot (k2b_fit.hip: LbMode::persistent)
-    FitCall c = fit_call(r.slots, K, model_joint_index, j3d, conf, stream_v);
-    c.in = in;
-    c.out = out;                                                              // frame rows of the outputs: each frame's point
-    c.loss_out = loss_out; c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.meta = meta;
+    c.B = r.slots; c.chain.len = r.max_len > 1 ? r.max_len : 2; c.chain.meta = meta;
     const k2b::LbfgsArgs la = make_lbfgs_args(r.slots, model_c, {first_iters, d.H, lr, tolerance_grad, tolerance_change}, c.out, w);
     return lbfgs_chain_launch(model_c, prior, cfg, c, la, followup_iters);
 }
@@ -304,21 +298,17 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
                          const float* root_targets, int32_t root_joint, int32_t num_free_betas, const float* betas_in,
                          float* betas_out, int32_t max_iter, int32_t history_size, double lr, double tolerance_grad,
                          double tolerance_change, void* stream_v) {
-    const char* who = "k2b_shape_pass_lbfgs";
-    LbfgsDims d;
-    if (const int rc = lbfgs_preamble(who, model_c, prior, cfg, max_iter, nullptr, history_size, lr, &d); rc != K2B_OK) return rc;
-    if (num_sequences < 0 || num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: %d sequences, %d frames", who, num_sequences, num_frames);
-    const int J = model_c->J, NB = d.NB, D = d.D;
-    if (root_joint < 0 || root_joint >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: root_joint=%d", who, root_joint);
-    if (num_free_betas < 1 || num_free_betas > NB || num_free_betas > 32)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_free_betas=%d (1..min(%d, 32))", who, num_free_betas, NB);
-    if (K < 1 || !model_joint_index) return fail(K2B_ERR_INVALID_ARGUMENT, "%s: num_targets=%d / model_joint_index", who, K);
-    for (int k = 0; k < K; ++k)
-        if (model_joint_index[k] < 0 || model_joint_index[k] >= J)
-            return fail(K2B_ERR_INVALID_ARGUMENT, "%s: model_joint_index[%d]=%d (kinematic joints only)", who, k, model_joint_index[k]);
-    if (num_sequences == 0) return K2B_OK;
-    if (!seq_offsets || !betas_in || !betas_out || (num_frames > 0 && (!j3d || !global_orient || !body_pose || !root_targets)))
-        return fail(K2B_ERR_INVALID_ARGUMENT, "%s: NULL buffer", who);
+    k2b::rules::Facts facts;
+    k2b::rules::Call r = lbfgs_rule_call(k2b::rules::Entry::shape_pass_lbfgs, model_c, prior, cfg,
+                                         fit_call(num_frames, K, model_joint_index, j3d, conf, {}, {}, nullptr, stream_v), &facts, max_iter, 0,
+                                         history_size, lr);
+    r.num_sequences = num_sequences; r.num_frames = num_frames; r.root_joint = root_joint; r.num_free_betas = num_free_betas;
+    r.params_null = !seq_offsets || !betas_in || !betas_out;
+    r.targets_null = num_frames > 0 && (!j3d || !global_orient || !body_pose || !root_targets);
+    bool go;
+    if (const int rc = judge(r, &go); rc != K2B_OK || !go) return rc;
+    const LbfgsDims d = lbfgs_dims(model_c, max_iter, 0, history_size);
+    const int NB = d.NB, D = d.D;
     hipStream_t stream = (hipStream_t)stream_v;
     const int S = num_sequences, N = num_frames, nb = num_free_betas;
     // behind the optimiser's workspace: its parameter arrays [S][...], then the per-frame closure buffers [N][...]
@@ -342,10 +332,9 @@ int k2b_shape_pass_lbfgs(const k2b_model* model_c, const k2b_prior* prior, const
     ec.num_iters = 1;
     ec.step_size = 0.0;                                                                  // evaluate-only: the closure
     ec.conf_per_frame = conf ? 1 : 0;
-    FitCall ev = fit_call(N, K, model_joint_index, j3d, conf, stream_v);
-    ev.in = {global_orient, body_pose, sa.be_f, sa.tr_f};
-    ev.out = {f(m.go_o), f(m.bp_o), f(m.be_o), f(m.tr_o)};
-    ev.loss_out = f(m.loss_f); ev.grad_out = f(m.grad_f);
+    FitCall ev = fit_call(N, K, model_joint_index, j3d, conf, {global_orient, body_pose, sa.be_f, sa.tr_f},
+                          {f(m.go_o), f(m.bp_o), f(m.be_o), f(m.tr_o)}, f(m.loss_f), stream_v);
+    ev.grad_out = f(m.grad_f);
     const k2b::LbfgsArgs la = make_lbfgs_args(S, model_c, {max_iter, d.H, lr, tolerance_grad, tolerance_change}, pts, w);
     // two launches per round with [prep, fit, reduce] as the closure; nothing asks for the loss at the result: the schedule
     // ends with its finalise step (the accepted points)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/k2b.h"
+#include "k2b_fit_rules.h"
 #include "k2b_internal.h"
 #include "k2b_model_tables.h"
 
@@ -194,14 +195,6 @@ struct __attribute__((visibility("hidden"))) k2b_ikgat {
 namespace k2b {
 namespace host __attribute__((visibility("hidden"))) {
 
-// Adam's eps as the kernels see it: its float32 rounding must be a normal positive number (k2b.h, k2b_fit_config).  With 0, a
-// negative value, NaN or a float32 denormal (flushed to 0) the update of a parameter with gradient 0 - one outside the
-// optimiser, say - is 0 * rcp(0) = NaN.  (NaN fails the first comparison.)
-inline bool adam_eps_ok(double eps) {
-    const float e = (float)eps;
-    return e >= 1.17549435e-38f && e <= 3.402823466e38f;
-}
-
 // ---- k2b_api_model.hip, k2b_api_prior.hip: per-handle tables built on first use ----------------------------------------------
 int adam_table(k2b_model* model, const k2b_fit_config* cfg, hipStream_t stream, float2** out);
 int folded_prior(k2b_prior* p, int Dv, const k2b_prior::Folded** out);
@@ -225,53 +218,64 @@ struct FitCall {
     const float *preserve = nullptr, *tr_prior = nullptr;
     float *loss_out = nullptr, *grad_out = nullptr;
     hipStream_t stream = nullptr;
-    // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta)
-    // image: set by k2b_fit_image_sequences alone - the chain runs under the projected joint term (every other entry's chain is
-    // refused there); freeze_shape: its steps > 0 hold the shape (FitArgs::chain_freeze_shape)
-    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool image = false, freeze_shape = false; } chain;
+    // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta);
+    // freeze_shape (k2b_fit_image_sequences): the steps > 0 hold the shape (FitArgs::chain_freeze_shape)
+    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool freeze_shape = false; } chain;
     // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
     struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
-    // set by k2b_fit_image alone: surface targets are allowed under projection (the projected form of k2b_surface.hip)
-    bool projected_surface = false;
-    // set by k2b_fit_multiview alone: the joint term summed over num_views calibrated cameras (HOST table, checked by the entry;
-    // targets [B][views][K][3], conf [views][K] or [B][views][K]); cfg->focal is not read then
+    // k2b_fit_multiview: the joint term summed over num_views calibrated cameras (HOST table; targets [B][views][K][3], conf
+    // [views][K] or [B][views][K]); cfg->focal is not read then
     int num_views = 0;
     const k2b_camera* cameras = nullptr;
 };
-// what every entry knows of its call; the parameter arrays and the outputs are set by name
-inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, void* stream) {
+// what every entry knows of its call; the optional arrays, the chain and the views are set by name
+inline FitCall fit_call(int32_t B, int32_t K, const int32_t* model_joint_index, const float* j3d, const float* conf, const ConstParams& in,
+                        const Params& out, float* loss_out, void* stream) {
     FitCall c;
-    c.B = B; c.K = K; c.model_joint_index = model_joint_index; c.j3d = j3d; c.conf = conf; c.stream = (hipStream_t)stream;
+    c.B = B; c.K = K; c.model_joint_index = model_joint_index; c.j3d = j3d; c.conf = conf; c.in = in; c.out = out; c.loss_out = loss_out;
+    c.stream = (hipStream_t)stream;
     return c;
 }
+
+// ---- what a call is refused for: k2b_fit_rules.h, asked once by every fit entry before anything is allocated, built or queued -----
+using rules::adam_eps_ok;
+inline rules::Facts fit_facts(const k2b_model* m, const k2b_prior* p) {
+    return {m->J, m->E, m->lmk.L, m->NB, m->fit_ok, m->fit_scan64, m->kin.depth.data(), p->D, p->M};
+}
+// the call of `entry` as the rules see it: the handles' facts go to *facts (absent handles: no facts), what the entry alone
+// knows (chain, ragged table, L-BFGS numbers) is set by name
+inline rules::Call rule_call(rules::Entry entry, const k2b_model* m, const k2b_prior* p, const k2b_fit_config* cfg, const FitCall& c,
+                             rules::Facts* facts) {
+    rules::Call r;
+    r.entry = entry; r.cfg = cfg;
+    if (m && p) { *facts = fit_facts(m, p); r.facts = facts; }
+    r.B = c.B; r.K = c.K; r.index = c.model_joint_index;
+    r.targets_null = !c.j3d;
+    r.params_null = !c.in.go || !c.in.bp || !c.in.be || !c.in.tr || !c.out.go || !c.out.bp || !c.out.be || !c.out.tr;
+    r.preserve = c.preserve != nullptr; r.tr_prior = c.tr_prior != nullptr; r.grad_out = c.grad_out != nullptr;
+    r.num_views = c.num_views; r.cameras = c.cameras;
+    return r;
+}
+// K2B_OK with *go saying whether there is anything to fit, or the refusal recorded for k2b_last_error()
+inline int judge(const rules::Call& r, bool* go) {
+    rules::Verdict v;
+    if (rules::judge(r, v) != K2B_OK) return fail(v.code, "%s", v.message);
+    *go = !v.nothing;
+    return K2B_OK;
+}
+inline int check_focal(const char* who, const float* focal) {      // (the term entries of k2b_api_misc.hip)
+    rules::Verdict v;
+    return rules::check_focal(who, focal, v) != K2B_OK ? fail(v.code, "%s", v.message) : K2B_OK;
+}
+
+// The shared set-up of a call that the rules have accepted: the fused kernel or the tree kernel, surface targets, the launches.
 int fit_world_impl(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, const FitCall& call);
 // The in-place start of a fit that steps in the output arrays: the defaults of the preserve pose and of the translation prior's
 // centre are the INITIAL parameters, so they go to scratch (`pres` [B][D], `trp` [B][3]) first; then the start goes into the
 // outputs where the two differ.
 hipError_t start_in_place(int B, int D, int NB, const ConstParams& in, const Params& out, const float* preserve, const float* tr_prior,
                           float* pres, float* trp, hipStream_t stream);
-
-// Whether the fused 24-lane kernel takes calls of (model, prior, cfg), and the prior width the call means.  k2b_fit.hip relies
-// on `fused` having been checked here.
-struct FusedEligibility { int prior_dims; bool fused; };
-FusedEligibility fused_eligibility(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg);
-bool kinematic_only(const k2b_model* m, int32_t K, const int32_t* idx);
-// k2b_fit_config::projection is built into k2b_fit_world's Adam loop and k2b_fit_image_sequences' chain: the other chain entries
-// and the L-BFGS entries refuse it by name
-inline int refuse_projection(const char* who, const k2b_fit_config* cfg) {
-    if (cfg && cfg->projection != 0)
-        return fail(K2B_ERR_UNSUPPORTED, "%s: the projected joint term (projection=%d) is built into k2b_fit_world only", who, cfg->projection);
-    return K2B_OK;
-}
-int check_targets(const char* who, const k2b_model* m, int32_t K, const int32_t* idx);
-int check_focal(const char* who, const float* focal);       // fx, fy: finite and positive
-
-// Ragged sequences of the k2b_fit_sequences* entries: the chain slots in launch order.
-struct RaggedSlots {
-    std::vector<int> meta;                   // [slot][4] = {sequence (row of its start parameters), first frame row, frames, 0}
-    int slots = 0, max_len = 0;
-};
-int ragged_slots(const char* who, int32_t S, const int32_t* lengths, const int32_t* offsets, RaggedSlots* r);
+// Ragged sequences of the k2b_fit_sequences* entries: the chain slots (rules::ragged_order) go up to the device.
 int upload_slots(const std::vector<int>& meta, int* dev, hipStream_t stream);
 
 }  // namespace host

@@ -20,7 +20,6 @@ constexpr int kProjForm = 256;
 // FitArgs::view inside the joint term.  It rides in the first template argument as kProjForm does (never together with it).
 constexpr int kViewsForm = 512;
 constexpr int kFormMask = kProjForm - 1;      // the capacity under the form bits
-constexpr int kMaxViews = 8;
 // one camera of a multi-view call as the kernels read it (k2b.h, k2b_camera): q = r (p + transl) + t, pixels = (fx q_x, fy q_y) / q_z
 struct FitView { float r[9], t[3], fx, fy; };
 // the 64 x 64 core of every component as MFMA A fragments (f16 hi / lo, see k2b_api_prior.hip):
@@ -283,7 +282,6 @@ hipError_t launch_vertex_term(const VertexTermArgs& a, hipStream_t stream);
 
 // Surface-point term (k2b_surface.hip): targets that are weighted vertex sets of up to 3 (vertex, weight) pairs (extra joints:
 // one pair of weight 1; landmarks: the barycentric pairs of a triangle), over a compact table of the selection's U vertices.
-constexpr int kSurfMaxTargets = 128;                  // surface targets per call
 constexpr int kSurfMaxVerts = 3 * kSurfMaxTargets;    // distinct vertices per call
 constexpr int kMaxLandmarks = 1024;                   // landmarks per model (k2b_model_set_landmarks)
 struct SurfaceTermArgs {

@@ -12,6 +12,8 @@ constexpr int kMaxShape = 32;       // shape coefficients (betas | expression) o
 constexpr int kMaxRounds = 4;       // pointer-doubling rounds: tree depth < 2^4
 constexpr int kLaneTabStride = 9;   // ints per lane: joint, parent lane, anc[kMaxRounds], subtree size, depth, scan flags
 constexpr int kLaneTabScan = 8;     // scan flags of the lane (k2b_scan_plan.h: kScan*), 0 where the model has no scan plan
+constexpr int kMaxViews = 8;        // calibrated cameras of a multi-view call (k2b_internal.h, FitView)
+constexpr int kSurfMaxTargets = 128;   // surface targets per call (k2b_surface.hip)
 
 // LBS operands are f16 hi/lo pairs in MFMA fragment order: [k-step][row][16 halfs].
 constexpr float kPdScale = 256.0f;   // power-of-two scale of the vertex-GEMM B operand (keeps f16 lo terms normal)

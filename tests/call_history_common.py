@@ -85,7 +85,7 @@ def cache_schedule(size: int) -> dict:
 
 
 def surface_target_limit() -> int:
-    src = (L.CSRC / "k2b_internal.h").read_text()
+    src = (L.CSRC / "k2b_layout.h").read_text()
     return int(re.search(r"constexpr int kSurfMaxTargets = (\d+);", src).group(1))
 
 

@@ -59,7 +59,7 @@ TERMS = ("joint", "mixture", "bending", "shape", "preserve", "transl")
 # every loss weight of k2b_fit_config (sigma is the GMoF scale); "transl" is the translation prior, built for 24 joints only
 ALL_ON = dict(sigma=100.0, joint=600.0, mixture=4.78 * 1.5, bending=15.2, shape=5.0, preserve=5.0, transl=100.0)
 
-# Odd trees for the tree kernel.  Its entry (k2b_api_fit.hip, fit_tree) takes up to 63 joints, targeted joints down to depth 15
+# Odd trees for the tree kernel.  Its entry (k2b_fit_rules.h, shared_path) takes up to 63 joints, targeted joints down to depth 15
 # (four pointer-doubling rounds) and a prior over the first 3..63 pose dimensions that hold the bending prior's indices (up to 55).
 TREES = {
     # 21 joints, 60 pose dimensions (all of them under the prior), junctions at the root, inside limbs and a three-way one at 7
@@ -78,9 +78,9 @@ def tree_limits_in_source():
     """(joints, depth, prior dimensions) the tree kernel's entry accepts, read from its own checks."""
     import re
     from pathlib import Path
-    src = (Path(__file__).resolve().parents[1] / "keypoints2body_amd" / "csrc" / "k2b_api_fit.hip").read_text()
-    m = re.search(r"if \(J > (\d+) \|\| a\.num_rounds > (\d+)\)", src)
-    p = re.search(r"prior_dims < 3 \|\| prior_dims > (\d+) \|\| prior_dims % 3 != 0", src)
+    src = (Path(__file__).resolve().parents[1] / "keypoints2body_amd" / "csrc" / "k2b_fit_rules.h").read_text()
+    m = re.search(r"\(f\.J > (\d+) \|\| rounds_for_depth\(max_depth\) > (\d+)\)", src)
+    p = re.search(r"prior_dims < 3 \|\| el\.prior_dims > (\d+) \|\| el\.prior_dims % 3 != 0", src)
     return int(m.group(1)), 2 ** int(m.group(2)) - 1, int(p.group(1)) // 3 * 3
 
 
