@@ -27,6 +27,15 @@
  *   - buffers are caller-owned; inputs are never written; handles may be shared by
  *     threads as long as concurrent calls use different streams AND different
  *     workspaces (one workspace per handle: serialise calls on one handle);
+ *   - an entry writes every element of its outputs and no byte outside them, and never an input; outputs and inputs of one
+ *     call do not overlap, with ONE exception, the aliasing rule of the four frame fitters k2b_fit_world, k2b_fit_image,
+ *     k2b_fit_multiview and k2b_fit_world_lbfgs: each of global_orient_out, body_pose_out, betas_out, transl_out may be the
+ *     very buffer of its own *_in (the same address: the fit is then in place); preserve_pose may be the body_pose buffer
+ *     and transl_prior_target the transl buffer, in place or not (the call keeps what it needs of the INITIAL values
+ *     before it overwrites them, as it does for their NULL defaults); the result is, bit for bit, that of the call with
+ *     separate buffers.  Any other overlap between an output and another buffer of the same call - a partial overlap, an
+ *     output on another parameter's input, on the targets or on loss_out / grad_out - is not supported.  k2b_adam_step
+ *     updates params, m and v in place by definition.  (tests/test_gpu_caller_buffers.py)
  *   - frames are independent, non-finite inputs included: in every entry with a frame or
  *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
  *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_multiview, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
@@ -229,7 +238,8 @@ uint32_t k2b_fit_config_size(void);
  *   *_in dev: initial global_orient [B][3], body_pose [B][3(J-1)], betas [B][NB], transl [B][3]
  *   preserve_pose dev [B][3(J-1)] or NULL (= body_pose_in, as world_space.py:159)
  *   transl_prior_target dev [B][3] or NULL (= transl_in): centre of the transl prior
- *   *_out dev: fitted parameters, same shapes (may alias the inputs)
+ *   *_out dev: fitted parameters, same shapes; each may be the buffer of its own *_in (Conventions, the aliasing rule;
+ *       tests/test_gpu_caller_buffers.py)
  *   loss_out dev [B]: per-frame loss of the LAST iteration evaluated BEFORE its step
  *       (world_space.py:256); the reference's scalar is the sum over the batch
  *   grad_out dev [B][P] or NULL: d loss / d params at the last iteration, P = 3J + NB + 3,
@@ -281,7 +291,8 @@ int k2b_fit_sequence(const k2b_model *model, const k2b_prior *prior, const k2b_f
  * final evaluation, as ONE launch for at most two frames per CU (the rounds are iterations of the fused kernel's loop, the
  * optimiser runs on an idle wave of the workgroup), one launch per round up to four frames per CU (the step as a prologue
  * of the closure's launch), two launches per round beyond that and for the larger models; the result does not depend on which.  Arguments as k2b_fit_world; preserve_pose / transl_prior_target NULL = the initial body pose /
- * translation; *_out may alias *_in; loss_out dev [B] and grad_out dev [B][3 + 3(J-1) + NB + 3] (either may be NULL) receive
+ * translation; each *_out may be the buffer of its own *_in (Conventions, the aliasing rule; tests/test_gpu_caller_buffers.py);
+ * loss_out dev [B] and grad_out dev [B][3 + 3(J-1) + NB + 3] (either may be NULL) receive
  * loss and gradient AT the result.  Frames never interact (torch couples the frames of a batch in one line search; the
  * reference only ever passes one frame).  At most 256 parameters per frame (3 + 3(J-1) + NB + 3): every model the fit
  * kernels take (63 joints and 32 shape coefficients are 224); beyond 192 the optimiser's step kernel runs in its wide form.
@@ -388,7 +399,8 @@ int k2b_fit_image_sequences(const k2b_model *model, const k2b_prior *prior, cons
 
 /* ---------------------------------------------------------------------------------
  * k2b_fit_image (ABI 1.9) — B independent frames of 2D keypoints under Adam, surface targets included.  The argument list is
- * k2b_fit_world's; the target buffer holds rows (u - cx, v - cy, ignored), centred pixels (k2b_fit_config::projection).
+ * k2b_fit_world's, the aliasing rule for *_out, preserve_pose and transl_prior_target included (Conventions;
+ * tests/test_gpu_caller_buffers.py); the target buffer holds rows (u - cx, v - cy, ignored), centred pixels (k2b_fit_config::projection).
  * cfg->projection must be 1 and cfg->focal finite and positive (else K2B_ERR_INVALID_ARGUMENT: 3D targets have
  * k2b_fit_world).  With kinematic targets only the call IS k2b_fit_world under projection: the same launch, the same bits.
  * With surface targets among model_joint_index (indices >= J: extra joints and landmarks) it queues, per iteration, the fit
@@ -422,7 +434,7 @@ int k2b_fit_image(const k2b_model *model, const k2b_prior *prior, const k2b_fit_
  *     joint loss = w_j^2 sum_c sum_k conf_ck^2 (gmof(e_x, sigma) + gmof(e_y, sigma))
  *     d loss / d p = sum_c R_c^T (g_x, g_y, g_z)_c                       ((g_x, g_y, g_z)_c: the single-view form's, on q)
  * Every other term, optimize_mask, freeze_betas, transl_prior_weight and the loss convention are k2b_fit_world's; so is the
- * argument list from global_orient_in on.  The conventions of projection = 1 hold per pair (c, k): q_z is divided by as it
+ * argument list from global_orient_in on, with its aliasing rule (Conventions; tests/test_gpu_caller_buffers.py).  The conventions of projection = 1 hold per pair (c, k): q_z is divided by as it
  * stands (IEEE division; a point behind a camera is legal and finite), a pair of confidence 0 is selected out and contributes
  * exactly nothing whatever its depth, a pair of non-zero confidence at q_z = 0 makes that frame non-finite and no other.  The
  * views are summed in the order 0 .. C - 1 in every launch shape: a frame's result is bit-identical in any batch and at any

@@ -6,8 +6,10 @@ point raises ``RuntimeError`` (the product path must fail loudly).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
 from pathlib import Path
 from typing import Optional, Sequence
 
@@ -181,6 +183,48 @@ def _dev(t: Optional[torch.Tensor], name: str, device: torch.device, shape=None)
     return C.c_void_p(t.data_ptr())
 
 
+# ---- the one place a result is allocated ---------------------------------------------------------------------------------------------
+class _Outputs(threading.local):
+    provider = None                   # the innermost ``outputs_from`` of this thread (the class default: none; a plain attribute read)
+
+
+_outputs = _Outputs()
+
+
+@contextlib.contextmanager
+def outputs_from(provider):
+    """Inside the block every wrapper of this module asks ``provider(name, shape)`` for each result tensor before it allocates
+    one: a tensor is used as that result (validated as an input is: device, float32, contiguous, exact shape), ``None`` means
+    "allocate as before".  So a caller can pass the output buffers of the C ABI: its own arena, or - for the four fitted
+    parameters of ``fit_world`` / ``fit_image`` / ``fit_multiview`` / ``fit_world_lbfgs`` - the input tensors themselves (k2b.h,
+    Conventions: aliasing).  Per thread, nestable (the innermost provider is asked, and it alone), restored on exit and on
+    exceptions; ``outputs_from(None)`` switches an outer provider off.
+
+    `name` is the key of the result: ``global_orient``, ``body_pose``, ``betas``, ``transl``, ``loss``, ``grad`` (the fit entries, in
+    this order; ``shape_pass_lbfgs``: ``betas``; the stand-alone terms: ``loss``, ``grad``), ``joints``, ``vertices``
+    (``NativeModel.lbs``), ``grad_global_orient``, ``grad_body_pose``, ``grad_betas``, ``grad_transl`` (``lbs_backward``), ``deg``
+    (``angular_error_deg``), ``err``, ``per_point``, ``transform`` (``point_error``), ``quaternions`` (``NativeIkgat.predict``).
+    ``adam_step`` works in place and asks for nothing."""
+    before = _outputs.provider
+    _outputs.provider = provider
+    try:
+        yield
+    finally:
+        _outputs.provider = before
+
+
+def _output(name: str, shape, device: torch.device) -> torch.Tensor:
+    """The result tensor `name` of a call: the current provider's (``outputs_from``), else a fresh ``torch.empty``."""
+    provider = _outputs.provider                                  # the whole cost outside ``outputs_from``: one thread-local read
+    if provider is not None:
+        shape = tuple(int(n) for n in shape)
+        given = provider(name, shape)
+        if given is not None:
+            _dev(given, f"the provided output {name}", device, shape)
+            return given
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
 def require_device(device=None) -> torch.device:
     """Resolve a HIP device or raise: the engine has no CPU path."""
     if not torch.cuda.is_available():
@@ -287,8 +331,8 @@ class NativeModel(_Handle):
         dev = self.device
         B = global_orient.shape[0]
         params = _param_ptrs(self, B, global_orient, body_pose, betas, transl)
-        joints = torch.empty((B, self.num_output_joints, 3), dtype=torch.float32, device=dev)
-        verts = torch.empty((B, self.num_vertices, 3), dtype=torch.float32, device=dev) if want_vertices else None
+        joints = _output("joints", (B, self.num_output_joints, 3), dev)
+        verts = _output("vertices", (B, self.num_vertices, 3), dev) if want_vertices else None
         _launch("k2b_lbs", dev, self._h, B, *params, _ptr(joints), _ptr(verts))
         return joints, verts
 
@@ -301,8 +345,8 @@ class NativeModel(_Handle):
         params = _param_ptrs(self, B, global_orient, body_pose, betas, transl)
         gj = _dev(grad_joints, "grad_joints", dev, (B, self.num_output_joints, 3))
         gv = _dev(grad_vertices, "grad_vertices", dev, (B, self.num_vertices, 3))
-        grads = [torch.empty((B, w), dtype=torch.float32, device=dev) if wanted else None
-                 for w, wanted in zip(_param_widths(self), want)]
+        grads = [_output(f"grad_{k}", (B, w), dev) if wanted else None
+                 for k, w, wanted in zip(PARAM_KEYS, _param_widths(self), want)]
         _launch("k2b_lbs_backward", dev, self._h, B, *params, gj, gv, *(_ptr(g) for g in grads))
         return tuple(grads)
 
@@ -368,12 +412,12 @@ def _joint_index(index, count: int, name: str = "model_joint_index") -> np.ndarr
 
 def _fit_outputs(model: NativeModel, lead: tuple, want_grad: bool = False) -> dict:
     """The result tensors of a fit over frames of leading shape `lead` (+ ``grad`` in the packed layout)."""
-    new = lambda *shape: torch.empty(lead + shape, dtype=torch.float32, device=model.device)
+    new = lambda name, *shape: _output(name, lead + shape, model.device)
     widths = _param_widths(model)
-    out = {k: new(w) for k, w in zip(PARAM_KEYS, widths)}
-    out["loss"] = new()
+    out = {k: new(k, w) for k, w in zip(PARAM_KEYS, widths)}
+    out["loss"] = new("loss")
     if want_grad:
-        out["grad"] = new(sum(widths))
+        out["grad"] = new("grad", sum(widths))
     return out
 
 
@@ -580,7 +624,7 @@ def shape_pass_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, se
     if not isinstance(seq_offsets, torch.Tensor) or seq_offsets.dtype != torch.int32 or seq_offsets.device != dev \
             or tuple(seq_offsets.shape) != (S + 1,) or not seq_offsets.is_contiguous():
         raise ValueError("seq_offsets must be a contiguous int32 device tensor of S + 1 entries")
-    out = torch.empty((S, nb), dtype=torch.float32, device=dev)
+    out = _output("betas", (S, nb), dev)
     _launch("k2b_shape_pass_lbfgs", dev, model.handle, prior.handle, C.byref(cfg), S, _ptr(seq_offsets), N, K, _np_ptr(idx),
             _dev(j3d, "j3d", dev, (N, K, 3)), _dev(conf, "conf", dev, (N, K)), _dev(global_orient, "global_orient", dev, (N, 3)),
             _dev(body_pose, "body_pose", dev, (N, D)), _dev(root_targets, "root_targets", dev, (N, 3)), int(root_joint), nb,
@@ -668,7 +712,7 @@ def angular_error_deg(pred_rotvec: torch.Tensor, gt_rotvec: torch.Tensor) -> tor
     if tuple(pred_rotvec.shape) != tuple(gt_rotvec.shape) or pred_rotvec.shape[-1] != 3:
         raise ValueError(f"expected two (...,3) tensors of equal shape, got {tuple(pred_rotvec.shape)} and {tuple(gt_rotvec.shape)}")
     n = pred_rotvec.numel() // 3
-    out = torch.empty(pred_rotvec.shape[:-1], dtype=torch.float32, device=dev)
+    out = _output("deg", pred_rotvec.shape[:-1], dev)
     _launch("k2b_angular_error_deg", dev, n, _dev(pred_rotvec, "pred_rotvec", dev), _dev(gt_rotvec, "gt_rotvec", dev),
             _ptr(out) if n else None)
     return out
@@ -697,9 +741,9 @@ def point_error(pred: torch.Tensor, gt: torch.Tensor, *, weights: Optional[torch
             per_frame = 1
         elif tuple(weights.shape) != (N,):
             raise ValueError(f"weights has shape {tuple(weights.shape)}, expected {(N,)} or {lead + (N,)}")
-    err = torch.empty(lead, dtype=torch.float32, device=dev)
-    dist = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if per_point else None
-    tf = torch.empty(lead + (13,), dtype=torch.float32, device=dev) if transform else None
+    err = _output("err", lead, dev)
+    dist = _output("per_point", lead + (N,), dev) if per_point else None
+    tf = _output("transform", lead + (13,), dev) if transform else None
     _launch("k2b_point_error", dev, B, N, _dev(pred, "pred", dev), _dev(gt, "gt", dev), _dev(weights, "weights", dev), per_frame,
             POINT_ALIGN_MODES[align], _ptr(err) if B else None, _ptr(dist) if B else None, _ptr(tf) if B else None)
     extra = tuple(t for t in (dist, tf) if t is not None)
@@ -714,8 +758,8 @@ def _term_call(name, model: NativeModel, idx: np.ndarray, targets, conf, conf_sh
     focal_np = None if focal is None else _host_f32(np.asarray(focal, dtype=np.float64).reshape(2))
     ins = [_dev(targets, "targets", dev, (B, T, 3)), _dev(conf, "conf", dev, conf_shape), *flags, float(sigma),
            float(joint_loss_weight), *(() if focal_np is None else (_np_ptr(focal_np),)), *_param_ptrs(model, B, *params)]
-    loss = torch.empty((B,), dtype=torch.float32, device=dev)
-    grad = torch.empty((B, sum(_param_widths(model))), dtype=torch.float32, device=dev)
+    loss = _output("loss", (B,), dev)
+    grad = _output("grad", (B, sum(_param_widths(model))), dev)
     _launch(name, dev, model.handle, B, T, _np_ptr(idx), *ins, _ptr(loss), _ptr(grad))
     return loss, grad
 
@@ -799,6 +843,6 @@ class NativeIkgat(_Handle):
             if quat_in.dim() != 3 or quat_in.shape[1:] != (J, 4) or quat_in.shape[0] not in ((1, T) if chain else (T,)):
                 raise ValueError(f"quat_in has shape {tuple(quat_in.shape)}, expected ({T}, {J}, 4)"
                                  + (" or (1, J, 4) in chain mode" if chain else ""))
-        out = torch.empty((T, J, 4), dtype=torch.float32, device=dev)
+        out = _output("quaternions", (T, J, 4), dev)
         _launch("k2b_ikgat_predict", dev, self._h, T, pos, q, 1 if chain else 0, _ptr(out))
         return out
