@@ -654,7 +654,8 @@ int k2b_point_error(int32_t num_frames, int32_t num_points, const float *pred, c
  *     J == 1 is accepted although the reference cannot run it (its edge tensor is malformed there): the graph
  *     is the self loop only, so every attention weight is 1 and the joint sees its own features.
  *   weights [num_weights] float32: the state dict's tensors, row-major, concatenated in this order
- *   (H = hidden_dim, H2 = H / 2, IN = input_dim):
+ *   (H = hidden_dim, H2 = H / 2, IN = input_dim; the table the library reads is ikgat_segment in csrc/k2b_ikgat_plan.h,
+ *   and num_weights is its sum):
  *     input_proj.weight [H][IN], input_proj.bias [H], joint_pos_embed.weight [J][H],
  *     residual_proj.weight [H][IN], residual_proj.bias [H],
  *     for each layer l: gat_layers.l.lin.weight [H][H], gat_layers.l.att_src [H], gat_layers.l.att_dst [H],

@@ -2,7 +2,8 @@
 
 The reference runs its graph-attention regressor one frame at a time through PyTorch and PyG.  Here the
 checkpoint is read on the host, checked against the network the config describes and packed into the layout
-of ``k2b_ikgat_create`` (include/k2b.h); inference is the HIP kernel ``k2b_ikgat_kernel``
+of ``k2b_ikgat_create`` (include/k2b.h; the one table of that order is ``ikgat_segment`` in csrc/k2b_ikgat_plan.h, and
+``expected_shapes`` below is held to it by tests/test_ikgat_plan_host.py); inference is the HIP kernel ``k2b_ikgat_kernel``
 (csrc/k2b_ikgat.hip), which also does the reference's pre- and post-processing (root subtraction, quaternion
 -> 6-D, 6-D -> quaternion).  The uploaded network is cached per checkpoint file (path, size, mtime) and
 network shape, so a per-frame loop of ``optimize_params_frame`` reads and uploads it once.

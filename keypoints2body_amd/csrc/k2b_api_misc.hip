@@ -15,14 +15,6 @@ namespace {
 
 thread_local std::string g_err;
 
-constexpr size_t kIkgatBatchLds = 80 * 1024;     // two workgroups per CU for batched launches
-constexpr int kIkgatMaxFrames = 16;
-
-int64_t ikgat_num_weights(int J, int IN, int H, int L) {
-    const int64_t h = H, h2 = H / 2;
-    return h * IN + h + (int64_t)J * h + h * IN + h + (int64_t)L * (h * h + 5 * h) + h2 * h + 3 * h2 + 6 * h2 + 6;
-}
-
 // One skin pass of k2b_lbs (k2b_lbs_plan.h, LbsPass): the fields StreamArgs and TileArgs share, then each one's own, launched by
 // the model's route.
 template <class Args>
@@ -279,87 +271,24 @@ int k2b_point_error(int32_t B, int32_t N, const float* pred, const float* gt, co
     return K2B_OK;
 }
 
-// ---- IK-GAT regressor (k2b_ikgat.hip) ----
+// ---- IK-GAT regressor (k2b_ikgat.hip; the set-up is k2b_ikgat_plan.h) ----
 int k2b_ikgat_create(k2b_ikgat** out, int32_t J, int32_t IN, int32_t H, int32_t L, int32_t NH, const int32_t* parents,
                      const float* weights, int64_t num_weights) {
-    if (!out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: out is NULL");
-    *out = nullptr;
-    if (!parents || !weights) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: NULL array");
-    if (J < 1 || J > 64) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: %d joints, supported 1..64", J);
-    if (IN != 3 && IN != 9) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: input_dim=%d, supported 3 or 9", IN);
-    if (H < 16 || H > 256 || H % 16 != 0)
-        return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: hidden_dim=%d, supported multiples of 16 up to 256", H);
-    if (L < 1 || L > 8) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: num_layers=%d, supported 1..8", L);
-    if (NH < 1 || H % NH != 0) return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: num_heads=%d does not divide hidden_dim=%d", NH, H);
-    for (int i = 0; i < J; ++i)
-        if (parents[i] >= J) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: parents[%d]=%d, only %d joints", i, parents[i], J);
-    const int64_t expect = ikgat_num_weights(J, IN, H, L);
-    if (num_weights != expect)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_create: %lld weights, the dimensions need %lld", (long long)num_weights,
-                    (long long)expect);
-    // edges of gan_regressor.py:16-36 (source -> target), then PyG's remove_self_loops + add_self_loops: CSR of in-edges
-    std::vector<std::pair<int, int>> edges;
-    for (int c = 0; c < J; ++c)
-        if (parents[c] >= 0) { edges.emplace_back(parents[c], c); edges.emplace_back(c, parents[c]); }
-    if (edges.empty())
-        for (int i = 0; i + 1 < J; ++i) { edges.emplace_back(i, i + 1); edges.emplace_back(i + 1, i); }
-    std::vector<std::vector<int>> in_nb(J);
-    for (const auto& e : edges)
-        if (e.first != e.second) in_nb[e.second].push_back(e.first);
-    for (int i = 0; i < J; ++i) in_nb[i].push_back(i);
-    std::vector<int> csr(J + 1, 0);
-    for (int i = 0; i < J; ++i) csr[i + 1] = csr[i] + (int)in_nb[i].size();
-    for (int i = 0; i < J; ++i) csr.insert(csr.end(), in_nb[i].begin(), in_nb[i].end());
-    const int nedges = csr[J];
-
-    const int KC = std::min(H / 2, (k2b::kIkgatChunkFloats / k2b::ikgat_ldx(H, NH)) & ~3);   // >= 4: LDX <= 3 H + 3 <= 771
-    const size_t one = k2b::ikgat_lds_bytes(J, H, NH, IN, nedges, 1, KC);
-    if (one > k2b::kIkgatMaxLds)
-        return fail(K2B_ERR_UNSUPPORTED, "k2b_ikgat_create: one frame needs %zu B of LDS (J=%d H=%d heads=%d), the limit is %zu", one, J,
-                    H, NH, k2b::kIkgatMaxLds);
-    int F = 1;
-    while (F < kIkgatMaxFrames && k2b::ikgat_lds_bytes(J, H, NH, IN, nedges, F + 1, KC) <= kIkgatBatchLds) ++F;
+    if (out) *out = nullptr;
+    const k2b::IkgatDims dims{J, IN, H, L, NH};
+    k2b::IkgatVerdict v;
+    if (k2b::ikgat_create_rules(out != nullptr, dims, parents, weights != nullptr, num_weights, v) != K2B_OK) return fail(v.code, "%s", v.message);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(K2B_ERR_NO_DEVICE, "k2b_ikgat_create: no HIP device visible (this engine has no CPU path)");
-    // device layout (k2b_ikgat.hip): the input layers as given; per layer the projection extended by the attention vectors,
-    // [W^T | W^T att_src | W^T att_dst | 0] (H x LDX, folded in double), then bias and LayerNorm; the head's matrices transposed
-    const int LDX = k2b::ikgat_ldx(H, NH), C = H / NH, H2 = H / 2;
-    std::vector<float> dw(weights, weights + (size_t)2 * H * IN + 2 * H + (size_t)J * H);
-    const float* src = weights + dw.size();
-    for (int l = 0; l < L; ++l) {
-        const float *W = src, *as = W + (size_t)H * H, *ad = as + H;
-        std::vector<float> ext((size_t)H * LDX, 0.f);
-        for (int k = 0; k < H; ++k) {
-            for (int c = 0; c < H; ++c) ext[(size_t)k * LDX + c] = W[(size_t)c * H + k];
-            for (int hd = 0; hd < NH; ++hd) {
-                double s0 = 0.0, s1 = 0.0;
-                for (int c = hd * C; c < (hd + 1) * C; ++c) {
-                    s0 += (double)W[(size_t)c * H + k] * as[c];
-                    s1 += (double)W[(size_t)c * H + k] * ad[c];
-                }
-                ext[(size_t)k * LDX + H + hd] = (float)s0;
-                ext[(size_t)k * LDX + H + NH + hd] = (float)s1;
-            }
-        }
-        dw.insert(dw.end(), ext.begin(), ext.end());
-        dw.insert(dw.end(), ad + H, ad + 4 * H);          // bias, LayerNorm weight, LayerNorm bias
-        src = ad + 4 * H;
-    }
-    const float *w1 = src, *b1 = w1 + (size_t)H2 * H, *w2 = b1 + 3 * H2, *b2 = w2 + 6 * H2;
-    for (int k = 0; k < H; ++k)
-        for (int c = 0; c < H2; ++c) dw.push_back(w1[(size_t)c * H + k]);
-    dw.insert(dw.end(), b1, b1 + 3 * H2);                  // bias, LayerNorm weight, LayerNorm bias
-    for (int k = 0; k < H2; ++k)
-        for (int c = 0; c < 8; ++c) dw.push_back(c < 6 ? w2[(size_t)c * H2 + k] : 0.f);
-    dw.insert(dw.end(), b2, b2 + 6);
-    std::unique_ptr<k2b_ikgat> owner(new k2b_ikgat);          // released with its buffers if an upload fails
-    k2b_ikgat* n = owner.get();
-    n->J = J; n->IN = IN; n->H = H; n->L = L; n->NH = NH; n->nedges = nedges; n->F = F; n->KC = KC; n->LDX = LDX;
-    hipError_t e = n->w.upload(dw.data(), dw.size());
+    const std::vector<int> csr = k2b::ikgat_csr(J, parents);
+    std::unique_ptr<k2b_ikgat> n(new k2b_ikgat);              // released with its buffers if an upload fails
+    n->plan = k2b::ikgat_plan(dims, csr[J]);
+    const std::vector<float> image = k2b::ikgat_pack(n->plan, weights);
+    hipError_t e = n->w.upload(image.data(), image.size());
     if (e == hipSuccess) e = n->csr.upload(csr.data(), csr.size());
     if (e != hipSuccess) return fail(K2B_ERR_HIP, "k2b_ikgat_create: upload failed: %s", hipGetErrorString(e));
-    *out = owner.release();
+    *out = n.release();
     return K2B_OK;
 }
 
@@ -371,19 +300,18 @@ void k2b_ikgat_destroy(k2b_ikgat* n) {
 
 int k2b_ikgat_predict(const k2b_ikgat* n, int32_t num_frames, const float* positions, const float* quat_in, int32_t chain,
                       float* quat_out, void* stream_v) {
-    if (!n) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: net is NULL");
-    if (num_frames < 0) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: num_frames=%d must be >= 0", num_frames);
-    if (num_frames == 0) return K2B_OK;
-    if (!positions || !quat_out) return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: NULL buffer");
-    if (n->IN == 9 && !quat_in)
-        return fail(K2B_ERR_INVALID_ARGUMENT, "k2b_ikgat_predict: the pos-rot6 network (input_dim 9) needs input quaternions");
+    k2b::IkgatVerdict v;
+    if (k2b::ikgat_predict_rules(n ? &n->plan : nullptr, num_frames, positions != nullptr, quat_in != nullptr, quat_out != nullptr, v) != K2B_OK)
+        return fail(v.code, "%s", v.message);
+    if (v.nothing) return K2B_OK;
+    const k2b::IkgatPlan& p = n->plan;
+    const k2b::IkgatLaunch launch = k2b::ikgat_launch(p, num_frames, chain != 0);
     k2b::IkgatArgs a{};
-    a.w = n->w.get(); a.csr = n->csr.get(); a.pos = positions; a.quat_in = n->IN == 9 ? quat_in : nullptr; a.quat_out = quat_out;
-    a.B = num_frames; a.J = n->J; a.H = n->H; a.heads = n->NH; a.L = n->L; a.in = n->IN; a.KC = n->KC; a.ldx = n->LDX; a.nedges = n->nedges;
+    a.w = n->w.get(); a.csr = n->csr.get(); a.pos = positions; a.quat_in = p.IN == 9 ? quat_in : nullptr; a.quat_out = quat_out;
+    a.B = num_frames; a.J = p.J; a.H = p.H; a.heads = p.NH; a.L = p.L; a.in = p.IN; a.KC = p.KC; a.ldx = p.LDX; a.nedges = p.nedges;
     a.chain = chain ? 1 : 0;
-    a.F = a.chain ? 1 : std::min(n->F, (int)num_frames);
-    const size_t lds = k2b::ikgat_lds_bytes(n->J, n->H, n->NH, n->IN, n->nedges, a.F, n->KC);
-    HIP_TRY(k2b::launch_ikgat(a, lds, (hipStream_t)stream_v));
+    a.F = launch.F;
+    HIP_TRY(k2b::launch_ikgat(a, launch, (hipStream_t)stream_v));
     return K2B_OK;
 }
 

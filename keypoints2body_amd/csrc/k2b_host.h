@@ -186,8 +186,7 @@ struct __attribute__((visibility("hidden"))) k2b_prior {
 };
 
 struct __attribute__((visibility("hidden"))) k2b_ikgat {
-    int J = 0, IN = 0, H = 0, L = 0, NH = 0, nedges = 0;
-    int F = 1, KC = 4, LDX = 4;              // frames per workgroup of a batched launch; k-chunk of the staged weights; x' stride
+    k2b::IkgatPlan plan{};                   // (k2b_ikgat_plan.h)
     k2b::host::DevBuf<float> w;
     k2b::host::DevBuf<int> csr;
 };

@@ -33,7 +33,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // out[r][n] = sum_k A[r][k] * Wt[k][n] for r < R, n < N.  Wt is the weight matrix TRANSPOSED (K x N, row-major, laid out
-// so by k2b_ikgat_create); each k-chunk of KC rows is one contiguous block of at most kIkgatChunkFloats floats, copied into
+// so by ikgat_pack, k2b_ikgat_plan.h); each k-chunk of KC rows is one contiguous block of at most kIkgatChunkFloats floats, copied into
 // wb with 16-byte loads and reused by every row of the workgroup.  N, KC and the chunk offsets are multiples of 4.
 // Starts and ends with a barrier.
 __device__ void block_mm(const float* A, int lda, int R, int K, const float* __restrict__ Wt, int N, float* out, int ldo,
@@ -141,33 +141,19 @@ __global__ __launch_bounds__(kThreads) void k2b_ikgat_kernel(IkgatArgs a) {
     extern __shared__ float lds[];
     const int J = a.J, H = a.H, NH = a.heads, C = H / NH, IN = a.in, H2 = H / 2, F = a.F, LDX = a.ldx;
     const int R = F * J;
-    float* hb = lds;                         // [R][H]    node features h; the head's 6 outputs (stride 8) at the end
-    float* xb = hb + (size_t)R * H;          // [R][LDX]  x' | a_src | a_dst of a GAT layer, then the head's hidden layer
-    float* wb = xb + (size_t)R * LDX;        // [KC][LDX] staged weight chunk
-    float* xin = wb + (size_t)a.KC * LDX;    // [R][IN]   network input
-    float* qv = xin + (size_t)R * IN;        // [R][4]    input quaternions (chain: the previous frame's outputs)
-    int* csr = reinterpret_cast<int*>(qv + (size_t)R * 4);   // [J+1] offsets, then the in-neighbours
+    // the LDS regions and the weight pointers, once, from the descriptions of k2b_ikgat_plan.h (what each one holds is said there);
+    // both before the graph copy: with the weight pointers after it the SGPR spill count moves (profiles/ikgat_plan_ab.txt)
+    const IkgatLdsT<float*> map = ikgat_lds_map(lds, J, IN, H, LDX, a.nedges, F, a.KC);
+    float *hb = map.hb, *xb = map.xb, *wb = map.wb, *xin = map.xin, *qv = map.qv;
+    int* csr = reinterpret_cast<int*>(map.csr);
+
+    const IkgatImageT<const float*> img = ikgat_image(a.w, J, IN, H, a.L, LDX);
+    const float *w_in = img.w_in, *b_in = img.b_in, *emb = img.emb, *w_res = img.w_res, *b_res = img.b_res;
+    const float *w1t = img.w1t, *b1 = img.b1, *g1 = img.g1, *be1 = img.be1, *w2t = img.w2t, *b2 = img.b2;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ncsr = J + 1 + a.nedges;
     for (int i = tid; i < ncsr; i += kThreads) csr[i] = a.csr[i];
-
-    // device weight layout (k2b_ikgat_create): the state dict's input layers as given, then per layer the projection
-    // extended by the attention vectors and transposed, then the head with both matrices transposed
-    const float* w_in = a.w;
-    const float* b_in = w_in + (size_t)H * IN;
-    const float* emb = b_in + H;
-    const float* w_res = emb + (size_t)J * H;
-    const float* b_res = w_res + (size_t)H * IN;
-    const float* layers = b_res + H;
-    const size_t LS = (size_t)H * LDX + 3 * (size_t)H;
-    const float* head = layers + (size_t)a.L * LS;
-    const float* w1t = head;                 // [H][H2]
-    const float* b1 = w1t + (size_t)H * H2;
-    const float* g1 = b1 + H2;
-    const float* be1 = g1 + H2;
-    const float* w2t = be1 + H2;             // [H2][8], columns 6, 7 zero
-    const float* b2 = w2t + 8 * (size_t)H2;
 
     const int nsteps = a.chain ? a.B : 1;
     for (int step = 0; step < nsteps; ++step) {
@@ -207,13 +193,11 @@ __global__ __launch_bounds__(kThreads) void k2b_ikgat_kernel(IkgatArgs a) {
         }
         // ---- GAT layers: one block_mm gives x' = h W^T and the attention logits a_src = h (W^T att_src), a_dst likewise
         for (int l = 0; l < a.L; ++l) {
-            const float* Wl = layers + (size_t)l * LS;
-            const float* bias = Wl + (size_t)H * LDX;
-            const float* lng = bias + H;
-            const float* lnb = lng + H;
+            const IkgatLayerT<const float*> layer = img.layer(l);
+            const float *Wl = layer.w, *bias = layer.bias, *lng = layer.lng, *lnb = layer.lnb;
             block_mm(hb, H, R, H, Wl, LDX, xb, LDX, wb, a.KC);
-            const float* as = xb + H;
-            const float* ad = xb + H + NH;
+            const float* as = xb + ikgat_col_src(H, NH);
+            const float* ad = xb + ikgat_col_dst(H, NH);
             for (int r = wave; r < R; r += kWaves) {
                 const int base = (r / J) * J, node = r % J;
                 const int e0 = csr[node], e1 = csr[node + 1];
@@ -276,12 +260,12 @@ __global__ __launch_bounds__(kThreads) void k2b_ikgat_kernel(IkgatArgs a) {
                 if (c < H2) xb[r * LDX + c] = v[q];
             }
         }
-        block_mm(xb, LDX, R, H2, w2t, 8, hb, 8, wb, a.KC);
+        block_mm(xb, LDX, R, H2, w2t, kIkgatOutCols, hb, kIkgatOutCols, wb, a.KC);
         // ---- 6-D -> quaternion
         for (int r = tid; r < R; r += kThreads) {
             float o[6], q[4];
 #pragma unroll
-            for (int k = 0; k < 6; ++k) o[k] = hb[r * 8 + k] + b2[k];
+            for (int k = 0; k < 6; ++k) o[k] = hb[r * kIkgatOutCols + k] + b2[k];
             rot6_to_quat(o, q);
             const int f = frame0 + r / J;
             if (f < a.B) {
@@ -297,16 +281,10 @@ std::atomic<unsigned long long> g_ikgat_lds_done{0};
 
 }  // namespace
 
-size_t ikgat_lds_bytes(int J, int H, int heads, int in, int nedges, int F, int KC) {
-    const size_t R = (size_t)F * J, ldx = ikgat_ldx(H, heads);
-    return sizeof(float) * (R * H + R * ldx + (size_t)KC * ldx + R * in + R * 4) + sizeof(int) * (J + 1 + nedges);
-}
-
-hipError_t launch_ikgat(const IkgatArgs& a, size_t lds_bytes, hipStream_t stream) {
+hipError_t launch_ikgat(const IkgatArgs& a, const IkgatLaunch& launch, hipStream_t stream) {
     hipError_t e = ensure_dynamic_lds(k2b_ikgat_kernel, g_ikgat_lds_done, kIkgatMaxLds);
     if (e != hipSuccess) return e;
-    const int grid = a.chain ? 1 : (a.B + a.F - 1) / a.F;
-    hipLaunchKernelGGL(k2b_ikgat_kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, a);
+    hipLaunchKernelGGL(k2b_ikgat_kernel, dim3(launch.grid), dim3(kThreads), launch.lds_bytes, stream, a);
     return hipGetLastError();
 }
 

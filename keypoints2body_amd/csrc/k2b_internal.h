@@ -8,6 +8,7 @@
 #include "k2b_device.h"
 #include "k2b_launch_plan.h"   // (and k2b_layout.h: kFitJoints, kPrior*, the fit kernel's LDS layout)
 #include "k2b_lbfgs_plan.h"    // kLbfgsMaxHistory, lbfgs_state_bytes / lbfgs_state_rows, the schedule and the workspace maps
+#include "k2b_ikgat_plan.h"    // the IK-GAT set-up: weight image, LDS map, launch
 #include "k2b_lbs_plan.h"      // LbsRoute, the stream kernels' k-step counts, lbs_frames_padded, the sizes and passes of the LBS pair
 
 namespace k2b {
@@ -371,18 +372,13 @@ hipError_t launch_point_error(const PointErrorArgs& a, hipStream_t stream);
 // quaternions per frame.  Batched: ceil(B / F) workgroups of F frames; chain: one workgroup walks the B frames in order,
 // frame t + 1 reading frame t's outputs as its input quaternions.
 struct IkgatArgs {
-    const float* w;          // device weight layout (k2b_ikgat_create in k2b_api_misc.hip)
+    const float* w;          // the device weight image (IkgatImage, k2b_ikgat_plan.h)
     const int* csr;          // [J + 1] in-edge offsets, then the source node of every in-edge (self loops included)
     const float* pos;        // [B][J][3]
     const float* quat_in;    // [B][J][4] xyzw (in == 9), or NULL
     float* quat_out;         // [B][J][4] xyzw
     int B, J, H, heads, L, in, F, KC, ldx, nedges, chain;
 };
-// columns of a GAT layer's extended projection: H of x', heads of a_src, heads of a_dst, padded to a multiple of 4
-inline int ikgat_ldx(int H, int heads) { return (H + 2 * heads + 3) & ~3; }
-constexpr size_t kIkgatMaxLds = 160 * 1024;
-constexpr int kIkgatChunkFloats = 4096;      // weights staged per k-chunk: KC * (columns) <= this
-size_t ikgat_lds_bytes(int J, int H, int heads, int in, int nedges, int F, int KC);
-hipError_t launch_ikgat(const IkgatArgs& a, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_ikgat(const IkgatArgs& a, const IkgatLaunch& launch, hipStream_t stream);   // a.F = launch.F
 
 }  // namespace k2b
