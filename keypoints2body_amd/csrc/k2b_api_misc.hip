@@ -30,6 +30,7 @@ hipError_t launch_skin(const k2b_model* m, const k2b::PoseArgs& pa, const Vertex
     if (m->lbs.streams()) {
         k2b::StreamArgs sa = skin_args<k2b::StreamArgs>(pa, vs, p, out, m->dump.get());
         sa.pd = vs.spd.get(); sa.w = vs.sw.get(); sa.f32_tiles = pa.frames_padded / 32; sa.nv16 = vs.nv16;
+        sa.pose_fp8 = m->lbs.pose_fp8; sa.pd8_lo_exp = vs.pd8_lo_exp; sa.pd8_hi_exp = vs.pd8_hi_exp;
         return k2b::launch_skin_stream(m->lbs.route, sa, device_cus(), stream);
     }
     k2b::TileArgs ta = skin_args<k2b::TileArgs>(pa, vs, p, out, m->dump.get());
@@ -127,6 +128,7 @@ int k2b_lbs(const k2b_model* model_c, int32_t B, const float* go, const float* b
     pa.go = go; pa.bp = bp; pa.be = be; pa.tr = tr;
     pa.xh = m->wsXh.get(); pa.xl = m->wsXl.get(); pa.a2 = m->wsA2.get(); pa.joints_out = joints_out;
     pa.a2_stream_order = m->lbs.streams() ? 1 : 0;
+    pa.x_fp8 = m->lbs.pose_fp8 ? 1 : 0;
     const VertexSet* const sets[] = {&m->mesh, &m->extra, &m->lmk.verts};                 // by LbsPass::Set
     float* const bufs[] = {vertices_out, joints_out, m->lmk.ws.get()};                    // by LbsPass::Buf
     for (int i = 0; i < plan.num_passes; ++i) {

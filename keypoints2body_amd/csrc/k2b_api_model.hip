@@ -20,11 +20,15 @@ namespace {
 // route (k2b_model_tables.h, vertex_set_images) go up; a stream model has none of the tile kernel's (SMPL-X: 64 MB less per GPU)
 int build_vertex_set(k2b_model* m, VertexSet& vs, const std::vector<int>& ids, const std::vector<int>& tag,
                      const float* v_template, const float* shapedirs, const float* posedirs, const float* lbs_weights, int V) {
-    const k2b::tables::VertexSetShape shape{m->J, m->NB, m->P, m->lbs.k_steps_x, m->lbs.w_frags};
+    // (the e4m3 strips of a subset of the mesh take the mesh's scales: a vertex has the same codes in every set)
+    const bool subset = &vs != &m->mesh;
+    const k2b::tables::VertexSetShape shape{m->J, m->NB, m->P, m->lbs.k_steps_x, m->lbs.w_frags, m->lbs.pose_fp8, subset, m->mesh.pd8_lo_exp, m->mesh.pd8_hi_exp};
     const k2b::tables::VertexSetImages im = k2b::tables::vertex_set_images(shape, ids, tag, v_template, shapedirs, posedirs, lbs_weights, V);
     vs.num = (int)ids.size();
     vs.v_tiles = im.v_tiles;
     vs.nv16 = im.nv16;
+    vs.pd8_lo_exp = im.pd8_lo_exp;
+    vs.pd8_hi_exp = im.pd8_hi_exp;
     const std::pair<DevBuf<k2b::k2b_half>*, const std::vector<k2b::k2b_half>*> images[] = {
         {&vs.spd, &im.spd}, {&vs.sw, &im.sw}, {&vs.w2, &im.w2}, {&vs.pdh, &im.pdh}, {&vs.pdl, &im.pdl}};
     for (const auto& [dev, host] : images)
@@ -73,7 +77,11 @@ int create_lbs_operands(k2b_model* m, const float* v_template, const float* shap
     // development switch K2B_LBS_TILE (non-zero): this model is skinned by the tile kernel whatever the stream kernels would
     // take - their run-time twin.  Per model, fixed here; nothing else reads it.
     const char* tile_env = getenv("K2B_LBS_TILE");
-    m->lbs = k2b::lbs_route(m->J, m->NB, K2B_LBS_STREAM != 0, tile_env && atoi(tile_env) != 0);
+    // development switch K2B_LBS_POSE_F16 (non-zero): a model of the route `stream` keeps the three f16 products of the pose phase
+    // (images, pose set-up and kernel) - the run-time twin of the e4m3 form, and the choice for a model with large pose
+    // correctives (k2b_lbs_plan.h, lbs_route).  Per model, fixed here; nothing else reads it.
+    const char* f16_env = getenv("K2B_LBS_POSE_F16");
+    m->lbs = k2b::lbs_route(m->J, m->NB, K2B_LBS_STREAM != 0, tile_env && atoi(tile_env) != 0, f16_env && atoi(f16_env) != 0);
     HIP_TRY(m->dump.alloc(64 * 1024 / sizeof(float)));     // 64 x 3 floats used; the rest is room for diagnostic builds
     std::vector<int> all(V), tag(V, 0);
     std::iota(all.begin(), all.end(), 0);
@@ -344,6 +352,48 @@ int k2b_dev_fit_scan_plan(int32_t J, const int32_t* parents, int32_t* lane_of, i
     for (int j = 0; j < J; ++j) lane_of[j] = plan.lane_of[j];
     for (int l = 0; l < k2b::kScanLanes; ++l) lane_flags[l] = plan.flags[l];
     return 1;
+}
+
+// Development entries, outside include/k2b.h: the e4m3 operands of the SMPL stream kernel's pose phase (k2b_lbs_fp8.h) without a
+// device, for the host tests.
+// out[i] = e4m3fn code of x[i] / 2^exp (round to nearest even, saturating)
+int k2b_dev_e4m3_encode(int64_t n, const float* x, int32_t exp, uint8_t* out) {
+    if (n < 0 || !x || !out || exp < -60 || exp > 60) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = k2b::e4m3_encode_scaled(x[i], exp);
+    return 0;
+}
+// the smallest power-of-two scale exponent at which max_abs does not saturate
+int k2b_dev_e4m3_scale_exp(float max_abs) { return k2b::e4m3_scale_exp(max_abs); }
+// X side: the f16 terms of x[i] (as floats) and their two codes, as the pose set-up stores them
+int k2b_dev_lbs_x_fp8(int64_t n, const float* x, float* hi, float* lo, uint8_t* hi8, uint8_t* lo8) {
+    if (n < 0 || !x || !hi || !lo || !hi8 || !lo8) return -1;
+    for (int64_t i = 0; i < n; ++i) {
+        const k2b::k2b_half h = (k2b::k2b_half)x[i], l = (k2b::k2b_half)(x[i] - (float)h);
+        const k2b::XCodes q = k2b::x_fp8_codes(h, l);
+        hi[i] = (float)h; lo[i] = (float)l; hi8[i] = q.hi8; lo8[i] = q.lo8;
+    }
+    return 0;
+}
+// The stream image Pd of the vertex set `ids` (n rows of a V-vertex model) as k2b_model_create would build it with or without
+// K2B_LBS_POSE_F16.  info[4]: pose_fp8 of the route, 16-vertex tiles, the two scale exponents (lo, hi).  spd = NULL: only
+// *spd_halfs and info are written.  Returns 0, -1 for bad arguments, -2 where the model is not on the route `stream`.
+// given_exps != NULL: the two scales (lo, hi) of the model's mesh, as a subset of it takes them.
+int k2b_dev_lbs_pose_fp8_image(int32_t J, int32_t NB, int32_t V, int32_t n, const int32_t* ids, const float* v_template, const float* shapedirs,
+                               const float* posedirs, const float* lbs_weights, int32_t pose_f16, const int32_t* given_exps, uint16_t* spd,
+                               int64_t* spd_halfs, int32_t* info) {
+    if (J < 2 || NB < 1 || V < 1 || n < 1 || !ids || !v_template || !shapedirs || !posedirs || !lbs_weights || !spd_halfs || !info) return -1;
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= V) return -1;
+    const k2b::LbsRouteRecord r = k2b::lbs_route(J, NB, true, false, pose_f16 != 0);
+    if (r.route != k2b::LbsRoute::stream) return -2;
+    const k2b::tables::VertexSetShape shape{J, NB, 9 * (J - 1), r.k_steps_x, r.w_frags, r.pose_fp8, given_exps != nullptr, given_exps ? given_exps[0] : 0,
+                                            given_exps ? given_exps[1] : 0};
+    const k2b::tables::VertexSetImages im = k2b::tables::vertex_set_images(shape, std::vector<int>(ids, ids + n), std::vector<int>(), v_template, shapedirs, posedirs, lbs_weights, V);
+    info[0] = r.pose_fp8; info[1] = im.nv16; info[2] = im.pd8_lo_exp; info[3] = im.pd8_hi_exp;
+    if (spd && *spd_halfs >= (int64_t)im.spd.size()) memcpy(spd, im.spd.data(), im.spd.size() * sizeof(uint16_t));
+    else if (spd) return -1;
+    *spd_halfs = (int64_t)im.spd.size();
+    return 0;
 }
 
 void k2b_model_destroy(k2b_model* m) {

@@ -98,6 +98,7 @@ struct VertexSet {
     DevBuf<k2b_half> w2;                     // W in the tile kernel's group layout (k2b_internal.h, TileArgs)
     DevBuf<k2b_half> spd, sw;                // stream kernel's Pd / W (k2b_internal.h, StreamArgs), or null
     int v_tiles = 0, num = 0, nv16 = 0;
+    int pd8_lo_exp = 0, pd8_hi_exp = 0;      // scales of spd's e4m3 strips (LbsRouteRecord::pose_fp8; k2b_model_tables.h, pose_fp8_strips)
 };
 
 }  // namespace host

@@ -181,6 +181,8 @@ struct PoseArgs {
     int a2_stream_order;       // 1: k-groups of an entry in the stream kernel's order hi.. | PAD | lo.. | ZERO (see StreamArgs)
     float* joints_out;         // [B][num_out_joints][3] (first J rows written) or null
     int xcd_frames;            // set by the launcher: 0 = workgroup b takes frame b; else XCD label b % 8 takes the frames [x, x + 1) * xcd_frames
+    int x_fp8;                 // LbsRouteRecord::pose_fp8: the pieces of xl of the 32-deep k-steps 0..kF8PoseSteps - 1 hold the e4m3 strip
+                               // [X_hi8 | X_lo8] of the k-step (k2b_lbs_fp8.h) instead of the f16 lo terms; 17-24 joints only
 };
 hipError_t launch_pose_setup(const PoseArgs& a, int pose_capacity, hipStream_t stream);   // (LbsRouteRecord::pose_capacity)
 
@@ -217,6 +219,7 @@ hipError_t launch_skin_tiles(const TileArgs& a, int num_cus, hipStream_t stream)
 // One kernel body (stream_body<S>) behind three entry points, one description S each; the descriptions hold what differs (pose
 // k-steps, X resident or in a ring, fragment counts and products, the counted-wait tables) and live in k2b_lbs_stream.hip.
 //   k2b_lbs_stream_kernel     17-24 joints, 7 pose k-steps (SMPL)                                      LbsRoute::stream
+//   k2b_lbs_stream_f8_kernel  the same with the pose corrections of the k-steps 0..5 as e4m3 MFMAs: 23, 24 joints        LbsRoute::stream, pose_fp8
 //   k2b_lbs_stream_x_kernel   49-56 joints, 16 pose k-steps (<= 512 features: SMPL-H, SMPL-X up to 24 shape coefficients) LbsRoute::stream_x
 //   k2b_lbs_stream_xw_kernel  49-56 joints, 17 pose k-steps (513-544 features: SMPL-X with 25-32, 56 joints with 16-32)   LbsRoute::stream_xw
 // Every other model with 17-24 or 49-56 joints, and any model created under K2B_LBS_TILE=1, runs the tile kernel (the rule and
@@ -238,8 +241,11 @@ struct StreamArgs {
     float* joints_out;           // see TileArgs
     int joints_stride, joints_row0;
     int num_wgs;
+    // route stream with LbsRouteRecord::pose_fp8 (description SmplF8; k2b_lbs_fp8.h): the lo strips of the k-steps 0..5 of xl and pd are
+    // e4m3, and these are the scale exponents of pd's two terms (the model's image: VertexSetImages::pd8_lo_exp, pd8_hi_exp)
+    int pose_fp8, pd8_lo_exp, pd8_hi_exp;
 };
-hipError_t launch_skin_stream(LbsRoute route, const StreamArgs& a, int num_cus, hipStream_t stream);   // one of the three stream routes
+hipError_t launch_skin_stream(LbsRoute route, const StreamArgs& a, int num_cus, hipStream_t stream);   // one of the three stream routes (stream: a.pose_fp8 picks SmplF8)
 // SMPL-X: the same operands with
 //   A   [16-frame tile][entry 12][fragment 4]: hi_0-3 | hi_4-6 PAD | lo_0-3 | lo_4-6 ZERO   (a2_stream_order with GA = 7)
 //   Pd  [k-step 16][16-vertex tile][coordinate 3][hi | lo]

@@ -36,6 +36,13 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
     lo = (_Float16)(x - (float)hi);
 }
 
+// x_fp8_codes (k2b_lbs_fp8.h) on the conversion unit: v_cvt_pk_fp8_f32 is OCP e4m3fn on gfx950 and rounds to nearest even; the
+// clamp in front makes it saturating whatever the overflow mode, a NaN passes through.  Byte 0: X_hi8, byte 1: X_lo8.
+__device__ __forceinline__ unsigned x_fp8_codes_device(_Float16 hi, _Float16 lo) {
+    auto sat = [](float x) { const float c = fminf(fmaxf(x, -448.f), 448.f); return x != x ? x : c; };
+    return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(sat((float)hi * f8_pow2(-kF8XHiExp)), sat((float)lo * f8_pow2(-kF8XLoExp)), 0, false);
+}
+
 // Timing-only diagnostic builds (no stores / no fills / no MFMAs / L2-resident stores / s_memtime stamps) live outside this file:
 // tools/build_lbs_variants.sh compiles it with -DK2B_LBS_DIAG_HEADER=<tools/lbs_diag.h>, which redefines the hooks below.
 #ifdef K2B_LBS_DIAG_HEADER
@@ -60,8 +67,9 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
 // ---------------------------------------------------------------------------------------------
 // (kMaxXSteps, the 16-deep k-steps of the feature vector this kernel can stage: k2b_lbs_plan.h)
 // NBC = capacity of the shape loop (10 / 16 / 20 / 32: the unrolled J(beta) loads and products are a third of this
-// kernel's instructions at 32), GA = ceil(J / 8) (compile-time divisors in the A2 store loop)
-template <int NBC, int GA>
+// kernel's instructions at 32), GA = ceil(J / 8) (compile-time divisors in the A2 store loop), F8: the lo pieces of X of the
+// k-steps 0..kF8PoseSteps - 1 hold the e4m3 strip of the k-step (PoseArgs::x_fp8; k2b_lbs_fp8.h) - 17-24 joints only
+template <int NBC, int GA, bool F8 = false>
 __global__ __launch_bounds__(64) void k2b_pose_setup_kernel(const PoseArgs a) {
     __shared__ float sR[kMaxJoints][9];
     __shared__ float sd[kMaxJoints][3];
@@ -129,11 +137,20 @@ __global__ __launch_bounds__(64) void k2b_pose_setup_kernel(const PoseArgs a) {
     __shared__ __attribute__((aligned(16))) _Float16 sXh[kMaxXSteps * 16], sXl[kMaxXSteps * 16];
     __shared__ __attribute__((aligned(16))) _Float16 sAh[12][kMaxJoints], sAl[12][kMaxJoints];
     __shared__ __attribute__((aligned(16))) _Float16 sTp[3][8];      // translation as three f16 terms (PAD group of the tile kernel)
+    // F8: per 32-deep k-step the 64-byte strip [X_hi8 32 | X_lo8 32], the four 16-byte chunks of the lane groups 0..3
+    __shared__ __attribute__((aligned(16))) unsigned char sXq[F8 ? kF8PoseSteps * 64 : 16];
     auto put_x = [&](int k, float x) {
         _Float16 hi, lo;
         split_f16(x, hi, lo);
         sXh[k] = hi;
         sXl[k] = lo;
+        if constexpr (F8) {
+            if (k < 32 * kF8PoseSteps) {
+                const unsigned q = x_fp8_codes_device(hi, lo);
+                sXq[(k >> 5) * 64 + (k & 31)] = (unsigned char)q;
+                sXq[(k >> 5) * 64 + 32 + (k & 31)] = (unsigned char)(q >> 8);
+            }
+        }
     };
     const int P = 9 * (J - 1);
     if (act && j > 0) {
@@ -178,7 +195,10 @@ __global__ __launch_bounds__(64) void k2b_pose_setup_kernel(const PoseArgs a) {
         const int nx = 2 * a.k_steps_x;                    // chunks per X array
         for (int c = j; c < 2 * nx; c += 64) {
             const int lo = c >= nx, kc = lo ? c - nx : c, ks = kc >> 1, h = kc & 1;
-            const uint4 v = *reinterpret_cast<const uint4*>((lo ? sXl : sXh) + ks * 16 + 8 * h);
+            uint4 v = *reinterpret_cast<const uint4*>((lo ? sXl : sXh) + ks * 16 + 8 * h);
+            if constexpr (F8) {                            // chunk (16-deep k-step ks, half h) is the one of lane group 2 (ks & 1) + h
+                if (lo && (ks >> 1) < kF8PoseSteps) v = *reinterpret_cast<const uint4*>(sXq + (ks >> 1) * 64 + 16 * (2 * (ks & 1) + h));
+            }
             *reinterpret_cast<uint4*>((lo ? a.xl : a.xh) + frag_elem((size_t)ks * tiles + tile, 8 * h, f)) = v;
         }
     }
@@ -622,11 +642,12 @@ hipError_t launch_pose_setup(const PoseArgs& a_in, int pose_capacity, hipStream_
 #endif
     const LbsPoseGrid g = lbs_pose_grid(a.num_frames, K2B_POSE_XCD);
     a.xcd_frames = g.xcd_frames;
-#define K2B_POSE(NBC_, GA_) \
-    case NBC_ * 8 + GA_: hipLaunchKernelGGL((k2b_pose_setup_kernel<NBC_, GA_>), dim3(g.grid), dim3(64), 0, stream, a); break
-    switch (pose_capacity * 8 + tile_groups_a(a.num_joints)) {
-        K2B_POSE(10, 3); K2B_POSE(16, 3); K2B_POSE(32, 3);
-        K2B_POSE(10, 7); K2B_POSE(20, 7); K2B_POSE(32, 7);
+#define K2B_POSE(NBC_, GA_, F8_) \
+    case (NBC_ * 8 + GA_) * 2 + F8_: hipLaunchKernelGGL((k2b_pose_setup_kernel<NBC_, GA_, F8_ != 0>), dim3(g.grid), dim3(64), 0, stream, a); break
+    switch ((pose_capacity * 8 + tile_groups_a(a.num_joints)) * 2 + (a.x_fp8 ? 1 : 0)) {
+        K2B_POSE(10, 3, 0); K2B_POSE(16, 3, 0); K2B_POSE(32, 3, 0);
+        K2B_POSE(10, 3, 1); K2B_POSE(16, 3, 1); K2B_POSE(32, 3, 1);      // e4m3 strips: the route stream alone
+        K2B_POSE(10, 7, 0); K2B_POSE(20, 7, 0); K2B_POSE(32, 7, 0);
         default: return hipErrorInvalidValue;              // 17..24 joints (SMPL) or 49..56 (SMPL-H / SMPL-X)
     }
 #undef K2B_POSE

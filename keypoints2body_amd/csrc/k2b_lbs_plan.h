@@ -6,6 +6,7 @@
 #pragma once
 #include "k2b_launch_plan.h"
 #include "k2b_layout.h"
+#include "k2b_lbs_fp8.h"
 
 namespace k2b {
 
@@ -24,13 +25,20 @@ struct LbsRouteRecord {
     int k_steps_x = 0;                        // 16-deep k-steps of the vertex GEMM (features), even: the kernels stage 32-deep slices
     int w_frags = 0;                          // W fragments per 16-vertex tile of the stream kernel's image (0: the tile kernel's images)
     int pose_capacity = 0;                    // shape-loop capacity of the pose set-up instantiation
+    bool pose_fp8 = false;                    // route stream only: the correction products of the pose k-steps 0..5 as block-scaled
+                                              // e4m3 MFMAs (k2b_lbs_fp8.h): e4m3 strips in the Pd images and in X, description SmplF8
     constexpr bool streams() const { return route == LbsRoute::stream || route == LbsRoute::stream_x || route == LbsRoute::stream_xw; }
 };
 // stream_kernels: the build routes to the stream kernels (K2B_LBS_STREAM); tile_forced: the model was created under K2B_LBS_TILE.
 // 17-24 joints take the stream kernel only at its own k-step count.  49-56 joints with fewer features than SMPL-X (SMPL-H: 477 ->
 // 15 k-steps) are padded up to the 16-k-step kernel - one all-zero k-step more buys the stream kernel - or take the 17-k-step one
 // (513-544 features: 55 joints from 25 shape coefficients on, 56 from 16).  Everything else, and a forced model, runs the tile kernel.
-constexpr LbsRouteRecord lbs_route(int J, int NB, bool stream_kernels, bool tile_forced) {
+// A model on the route `stream` gets the e4m3 form of the pose corrections (pose_fp8) when the k-steps 0..5 hold pose features
+// only - 9 (J - 1) >= 192: 23 and 24 joints; shape coefficients and the template there would cost more than 5e-6 m - and the model
+// was not created under K2B_LBS_POSE_F16 (pose_f16_forced): the three-f16-product twin, which is also the choice for a model whose
+// pose correctives are large (measured on the synthetic model: X . Pd within 1.2e-6 m of float64 at +-pi per component; with 1 %
+// of the posedirs x 20 or all of them x 10 the e4m3 form reads 5e-6 to 1.2e-5 m, the f16 form 1e-8).
+constexpr LbsRouteRecord lbs_route(int J, int NB, bool stream_kernels, bool tile_forced, bool pose_f16_forced = false) {
     LbsRouteRecord r;
     const int GA = r.groups_a = tile_groups_a(J);
     int KX = (9 * (J - 1) + NB + 2 + 31) / 32 * 2;
@@ -43,6 +51,7 @@ constexpr LbsRouteRecord lbs_route(int J, int NB, bool stream_kernels, bool tile
             : streams && GA == 7 && KX == 2 * kStreamXWKSteps ? LbsRoute::stream_xw
                                                               : LbsRoute::tile;
     r.w_frags = r.route == LbsRoute::stream ? 3 : r.streams() ? 5 : 0;
+    r.pose_fp8 = r.route == LbsRoute::stream && !pose_f16_forced && 9 * (J - 1) >= 32 * kF8PoseSteps;
     r.pose_capacity = NB <= 10 ? 10 : GA == 3 ? (NB <= 16 ? 16 : 32) : (NB <= 20 ? 20 : 32);
     return r;
 }

@@ -1,7 +1,9 @@
 // k2b_lbs_stream.hip — vertex skinning for SMPL (k2b_lbs_stream_kernel: 17-24 joints, 7 pose k-steps) and SMPL-H / SMPL-X
 // (k2b_lbs_stream_x_kernel: 49-56 joints, 16 pose k-steps; k2b_lbs_stream_xw_kernel: the same with 25-32 shape coefficients,
-// 17 pose k-steps) on gfx950: ONE kernel body, stream_body<S>, and three descriptions S (Smpl, SmplX, SmplXWide) that hold what
-// the kernels do not share - the counted-wait tables among it.
+// 17 pose k-steps) on gfx950: ONE kernel body, stream_body<S>, and the descriptions S (Smpl, SmplX, SmplXWide) that hold what
+// the kernels do not share - the counted-wait tables among it.  A fourth description, SmplF8 (k2b_lbs_stream_f8_kernel), is Smpl
+// with the correction products of the pose k-steps 0..5 on the block-scaled e4m3 MFMA (k2b_lbs_fp8.h): the default of the 23- and
+// 24-joint models, the f16 form being their K2B_LBS_POSE_F16 twin.
 //
 // Same arithmetic as the tile kernel of k2b_lbs.hip (two GEMMs over frames x vertices on v_mfma_f32_16x16x32_f16, operands
 // as f16 hi/lo pairs, v = T [v_posed; 1] + t; reference seam: the final forward of world_space.py:258-278, smplx's
@@ -104,6 +106,17 @@ template <int N> __device__ __forceinline__ void lds_ready(half8 (&b)[2]) {
 template <int N> __device__ __forceinline__ void lds_ready(half8 (&b)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]) : "n"(N) : "memory");
 }
+// (SmplF8: one fragment, or three - hi, the e4m3 strip, the previous k-step's e4m3 strip)
+template <int N> __device__ __forceinline__ void lds_ready(half8& b) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(b) : "n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void lds_ready(half8& b0, half8& b1, half8& b2) {
+    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(b0), "+v"(b1), "+v"(b2) : "n"(N) : "memory");
+}
+// the 32 bytes a lane gives v_mfma_scale_f32_16x16x128_f8f6f4: the e4m3 strips of the even and of the odd k-step of a pair
+typedef int int8v __attribute__((ext_vector_type(8)));
+typedef _Float16 half16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int8v f8_pair(half8 even, half8 odd) {
+    return __builtin_bit_cast(int8v, __builtin_shufflevector(even, odd, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15));
+}
 // at most N vector-memory operations in flight: the W fragments have landed
 template <int N> __device__ __forceinline__ void w_ready(half8 (&w)[3]) {
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]) : "n"(N) : "memory");
@@ -134,6 +147,7 @@ constexpr int kNoWait = 63;    // the counter's ceiling: ties the registers to t
 
 struct Smpl {
     static constexpr int kPoseSteps = kStreamKSteps;
+    static constexpr int kF8Steps = 0;                      // k-steps whose correction products are e4m3 (SmplF8)
     static constexpr int kXSlots = 7;                       // 16 KiB slots of X in LDS: the whole tile is resident
     static constexpr bool pose_barrier(int) { return false; }
     static constexpr bool pose_x_fill(int) { return false; }
@@ -170,6 +184,7 @@ struct Smpl {
 
 struct SmplX {
     static constexpr int kPoseSteps = kStreamXKSteps;
+    static constexpr int kF8Steps = 0;
     static constexpr int kXSlots = 4;                       // a ring: k-step ks in slot ks % 4, filled three k-steps ahead
     static constexpr bool pose_barrier(int ks) { return ks >= 1 && ks <= 14; }   // publishes X(ks + 1), frees the slot of X(ks - 1)
     static constexpr bool pose_x_fill(int ks) { return ks >= 1 && ks <= 12; }    // X(ks + 3) into that slot
@@ -198,10 +213,29 @@ struct SmplX {
     [[maybe_unused]] static constexpr int kDiagLevel = K2B_STREAMX_DIAG;
 };
 
+// SMPL with the correction products of the k-steps 0..5 on the block-scaled e4m3 instruction (k2b_lbs_fp8.h; the route's default
+// for 23 and 24 joints, LbsRouteRecord::pose_fp8).  Everything is Smpl's but the product list of the pose phase:
+//   k-step 0, 2, 4:  X_hi . Pd_hi (f16, 3 MFMAs per 16-frame tile); the k-step's e4m3 Pd strip stays in its buffer
+//   k-step 1, 3, 5:  X_hi . Pd_hi, then ONE v_mfma_scale_f32_16x16x128_f8f6f4 per coordinate over the e4m3 strips of the k-steps
+//                    ks - 1 and ks: X_hi8 . Pd_lo8 + X_lo8 . Pd_hi8 of both, into the same accumulator (units Pd x 256: the
+//                    scales are X's constants kF8XHiExp / kF8XLoExp and the image's pd8_lo_exp / pd8_hi_exp)
+//   k-step 6:        the three f16 products, as Smpl
+// The e4m3 strips take the place of the f16 lo strips in X (LDS slots, fills) and in Pd (6 loads per k-step), 16 bytes per lane
+// each, so the vector-memory operations of a wave and their order are Smpl's and so are both wait tables.  What moves is LDS
+// traffic inside a k-step: an even k-step reads one fragment per tile, an odd one three (its own two and the e4m3 strip of the
+// k-step before), and the Pd strip of an even k-step is copied out of its buffer - the buffer of k-step ks - 1 is the one k-step
+// ks loads Pd(ks + 2) into - before those loads are issued.  MFMA cycles per tile and SIMD: 2 x (7 x 24 x 16 + 3 x 24 x 32 +
+// 2 x 24 x 16 + 288 x 16) = 20.7 k against 25.3 k.
+struct SmplF8 : Smpl {
+    static constexpr int kF8Steps = kF8PoseSteps;
+    static_assert(kF8Steps % 2 == 0 && kF8Steps < kPoseSteps, "pairs of k-steps, and a last k-step in the f16 form");
+};
+
 // SMPL-X with 25-32 shape coefficients: 9 x 54 + NB + 2 = 513..520 features, one 32-deep k-step more.  Ring, fragments, products
 // and unit waits are SmplX's; the ring runs one k-step longer, and 17 % 3 == 2 hands the Pd buffers over from 2 and 0 (the body).
 struct SmplXWide {
     static constexpr int kPoseSteps = kStreamXWKSteps;
+    static constexpr int kF8Steps = 0;
     static constexpr int kXSlots = 4;                       // X(16) takes slot 0; the next tile's X(0) follows it behind the barrier of unit 0
     static constexpr bool pose_barrier(int ks) { return ks >= 1 && ks <= 15; }   // publishes X(ks + 1), frees the slot of X(ks - 1)
     static constexpr bool pose_x_fill(int ks) { return ks >= 1 && ks <= 13; }    // X(ks + 3) into that slot; X(16) is the last
@@ -290,6 +324,14 @@ __device__ __forceinline__ void stream_body(const StreamArgs a) {
     const unsigned lxa = lds0 + lx, lxb = lxa + 65536;               // (the 16-bit offset field reaches four slots)
     const int la = g * 256 + row * 16;                               // lane part of an A fragment address inside a piece
     const float inv_scale = 1.0f / kPdScale;
+    // SmplF8: the E8M0 scale bytes this lane supplies - lane group g scales block g of the K = 128 instruction, the blocks 0, 2 being
+    // X_hi8 . Pd_lo8 and 1, 3 X_lo8 . Pd_hi8 (k2b_lbs_fp8.h)
+    [[maybe_unused]] int sa = 0, sb = 0;
+    if constexpr (S::kF8Steps > 0) {
+        sa = e8m0((g & 1) ? kF8XLoExp : kF8XHiExp);
+        sb = e8m0((g & 1) ? a.pd8_hi_exp : a.pd8_lo_exp);
+        asm volatile("" : "+v"(sa), "+v"(sb));
+    }
 
     // ---- prologue: everything the first tile needs ------------------------------------------------------------------------
     half8 pb[3][3][2];                          // Pd buffers: k-step ks lives in buffer ks % 3
@@ -338,12 +380,56 @@ __device__ __forceinline__ void stream_body(const StreamArgs a) {
             };
             static_for<8>(tile);
         };
+        // SmplF8, k-steps 0..5: the fragment with the e4m3 strip of k-step ks - 1 (xo, beside xq), the three pair operands of Pd (b8)
+        // and the scale bytes of this lane's group (sa, sb).  An even k-step reads and multiplies X_hi alone; an odd one reads its
+        // own two fragments and the strip of the k-step before, and adds the pair's corrections with one K = 128 MFMA per coordinate.
+        [[maybe_unused]] half8 xo[2];
+        [[maybe_unused]] int8v b8[3];
+        auto xread8 = [&](auto ksc, auto fc, half8 (&dst)[2], half8& before) {
+            constexpr int ks = decltype(ksc)::value, f = decltype(fc)::value;
+            constexpr int tile_off = (f >> 1) * 2048 + (f & 1) * 256;
+            lread16<(ks & 3) * 16384 + tile_off>(dst[0], ks < 4 ? lxa : lxb);
+            if constexpr (ks & 1) {
+                lread16<(ks & 3) * 16384 + tile_off + 1024>(dst[1], ks < 4 ? lxa : lxb);
+                lread16<((ks - 1) & 3) * 16384 + tile_off + 1024>(before, ks - 1 < 4 ? lxa : lxb);
+            }
+        };
+        auto kstep8 = [&](auto ksc, const half8 (&pd)[3][2]) {
+            constexpr int ks = decltype(ksc)::value;
+            constexpr bool odd = ks & 1;
+            auto tile = [&](auto fc) {
+                constexpr int f = decltype(fc)::value;
+                half8 (&cur)[2] = xq[f & 1];
+                half8& before = xo[f & 1];
+                // the next tile's fragments: one (even k-step), three (odd), or the two of the last k-step's f16 form
+                if constexpr (f < 7) xread8(ksc, ic<f + 1>{}, xq[(f + 1) & 1], xo[(f + 1) & 1]);
+                else if constexpr (ks + 1 < S::kF8Steps) xread8(ic<ks + 1>{}, ic<0>{}, xq[0], xo[0]);
+                else xread(xq[0], ic<ks + 1>{}, ic<0>{});
+                constexpr int next = f < 7 ? (odd ? 3 : 1) : ks + 1 < S::kF8Steps ? (odd ? 1 : 3) : 2;
+                if constexpr (odd) lds_ready<next>(cur[0], cur[1], before); else lds_ready<next>(cur[0]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if constexpr (ks == 0) vp[f][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[0], pd[c][0], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                    else vp[f][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[0], pd[c][0], vp[f][c], 0, 0, 0);
+                }
+                if constexpr (odd) {
+                    const int8v a8 = f8_pair(before, cur[1]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) vp[f][c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8[c], vp[f][c], 0, 0, 0, sa, 0, sb);
+                }
+            };
+            static_for<8>(tile);
+        };
         // top of k-step ks: wait, barrier, fills and loads in the issue order of the description, then the 72 MFMAs
         auto step = [&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
             half8 (&cur)[3][2] = pb[ks % 3], (&ahead)[3][2] = pb[(ks + 2) % 3];
             K2B_SDIAG_STAMP(ks);
             K2B_PD_READY(S::pose_wait(ks), cur);
+            if constexpr (ks < S::kF8Steps && (ks & 1)) {   // the pair's Pd strips, before the loads below take the buffer of k-step ks - 1
+#pragma unroll
+                for (int c = 0; c < 3; ++c) b8[c] = f8_pair(ahead[c][1], cur[c][1]);
+            }
             if constexpr (S::pose_barrier(ks)) if (!(K2B_SX_SKIP & 8)) wg_barrier();
             if constexpr (S::pose_x_fill(ks) && !(K2B_SX_SKIP & 2)) issue_x(cfg, ks + S::kXSlots - 1);
             if constexpr (ks == KS - 1) {              // W fragments of this tile's vertices (needed behind the pose phase: their registers are free until here)
@@ -352,13 +438,13 @@ __device__ __forceinline__ void stream_body(const StreamArgs a) {
                 gload_frags<bias>(wf, lane16, wbase, std::make_integer_sequence<int, WF>{});
             }
             if constexpr (!(K2B_SX_SKIP & 4)) { if constexpr (ks + 2 < KS) load_pd(ahead, cvg, ks + 2); else load_pd(ahead, nvg, ks + 2 - KS); }
-            kstep(ksc, cur);
+            if constexpr (ks < S::kF8Steps) kstep8(ksc, cur); else kstep(ksc, cur);
         };
         // the next tile's k-steps 0 and 1 are loaded at the k-steps KS - 2 and KS - 1 into the buffers KS % 3 and (KS + 1) % 3; a
         // remainder 0 would put k-step 0 into buffer 0 itself and k-step 1 into 1: no hand-over, and nothing here is built for it
         static_assert(KS % 3 == 1 || KS % 3 == 2, "the next tile's k-steps 0 and 1 must end the tile in buffers 1, 2 or 2, 0");
         constexpr int kHand0 = KS % 3, kHand1 = (KS + 1) % 3;
-        xread(xq[0], ic<0>{}, ic<0>{});
+        if constexpr (S::kF8Steps > 0) xread8(ic<0>{}, ic<0>{}, xq[0], xo[0]); else xread(xq[0], ic<0>{}, ic<0>{});
         static_for<KS>(step);
         K2B_SDIAG_STAMP(S::kStampPoseEnd);
 #pragma unroll
@@ -501,12 +587,14 @@ hipError_t launch_stream(void (*kernel)(const StreamArgs), const StreamArgs& a_i
 }  // namespace
 
 __global__ __launch_bounds__(512) void k2b_lbs_stream_kernel(const StreamArgs a) { stream_body<Smpl>(a); }
+__global__ __launch_bounds__(512) void k2b_lbs_stream_f8_kernel(const StreamArgs a) { stream_body<SmplF8>(a); }
 __global__ __launch_bounds__(512) void k2b_lbs_stream_x_kernel(const StreamArgs a) { stream_body<SmplX>(a); }
 __global__ __launch_bounds__(512) void k2b_lbs_stream_xw_kernel(const StreamArgs a) { stream_body<SmplXWide>(a); }
 
 hipError_t launch_skin_stream(LbsRoute route, const StreamArgs& a, int num_cus, hipStream_t stream) {
     switch (route) {
-        case LbsRoute::stream: return launch_stream<Smpl>(k2b_lbs_stream_kernel, a, num_cus, stream);
+        case LbsRoute::stream:
+            return a.pose_fp8 ? launch_stream<SmplF8>(k2b_lbs_stream_f8_kernel, a, num_cus, stream) : launch_stream<Smpl>(k2b_lbs_stream_kernel, a, num_cus, stream);
         case LbsRoute::stream_x: return launch_stream<SmplX>(k2b_lbs_stream_x_kernel, a, num_cus, stream);
         case LbsRoute::stream_xw: return launch_stream<SmplXWide>(k2b_lbs_stream_xw_kernel, a, num_cus, stream);
         default: return hipErrorInvalidValue;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "k2b_layout.h"
+#include "k2b_lbs_fp8.h"
 #include "k2b_scan_plan.h"
 
 namespace k2b {
@@ -98,13 +99,46 @@ inline std::vector<int> tree_tab_with_prior(std::vector<int> tab, const Tree& t,
 struct VertexSetShape {
     int J, NB, P, KX;                        // joints, shape coefficients, pose features 9 (J - 1), 16-deep k-steps of the features
     int wfrags;                              // W fragments per 16-vertex tile of the model's stream kernel (3: 17-24 joints, 5: 49-56); 0: tile kernel
+    bool pose_fp8 = false;                   // wfrags 3 only (LbsRouteRecord::pose_fp8): the lo strips of the k-steps 0..5 of spd as e4m3
+    bool pd8_given = false;                  // pose_fp8: take the two scales below instead of choosing them from this set - a subset of the
+    int pd8_lo_exp = 0, pd8_hi_exp = 0;      // mesh (extra joints, landmark vertices) gets the mesh's codes, bit for bit
 };
 // B operands (f16 hi/lo, MFMA fragment order; k2b_lbs.hip, k2b_lbs_stream.hip), the images of the model's route alone: the tile
 // kernel reads pdh / pdl (Pd fragments [KX][3][v_tiles]) and w2; a stream kernel reads spd (pdh / pdl re-indexed) and sw.
 struct VertexSetImages {
     int v_tiles = 0, nv16 = 0;               // 32-vertex tiles; 16-vertex tiles of the stream images (whole 128-vertex groups)
     std::vector<k2b_half> pdh, pdl, w2, spd, sw;
+    int pd8_lo_exp = 0, pd8_hi_exp = 0;      // pose_fp8: the power-of-two scales of the e4m3 strips, Pd_lo8 = e4m3(Pd_lo / 2^lo_exp)
 };
+
+// The e4m3 strips of a stream image (k2b_lbs_fp8.h): for the k-steps 0..kF8PoseSteps - 1 the 1 KiB f16 lo piece of every
+// (k-step, 16-vertex tile, coordinate) is replaced by [lane group g][vertex row 16][16 bytes] with g 0, 1 = Pd_lo8 of the
+// features 0..15 and 16..31 of the k-step and g 2, 3 = Pd_hi8 of the same - the codes of the f16 terms the piece pair held, one
+// scale per term for the whole image, chosen from the term's largest magnitude unless given.  spd [k-step][nv16][3][hi | lo][512 halfs].
+inline void pose_fp8_strips(VertexSetImages& o, bool given, int lo_exp, int hi_exp) {
+    const size_t pairs = (size_t)kF8PoseSteps * o.nv16 * 3;
+    float max_lo = 0.f, max_hi = 0.f;
+    for (size_t p = 0; p < pairs; ++p)
+        for (int e = 0; e < 512; ++e) {
+            const float hi = (float)o.spd[p * 1024 + e], lo = (float)o.spd[p * 1024 + 512 + e];
+            max_hi = std::max(max_hi, hi < 0 ? -hi : hi);
+            max_lo = std::max(max_lo, lo < 0 ? -lo : lo);
+        }
+    o.pd8_lo_exp = given ? lo_exp : e4m3_scale_exp(max_lo);
+    o.pd8_hi_exp = given ? hi_exp : e4m3_scale_exp(max_hi);
+    for (size_t p = 0; p < pairs; ++p) {
+        k2b_half* hi = o.spd.data() + p * 1024;
+        uint8_t strip[1024];
+        for (int r = 0; r < 16; ++r)
+            for (int k = 0; k < 32; ++k) {
+                const int src = (((k >> 3) & 3) * 16 + r) * 8 + (k & 7);          // f16 operand order: lane = row + 16 k-group, 8 halfs
+                strip[((k >> 4) * 16 + r) * 16 + (k & 15)] = e4m3_encode_scaled((float)hi[512 + src], o.pd8_lo_exp);
+                strip[((2 + (k >> 4)) * 16 + r) * 16 + (k & 15)] = e4m3_encode_scaled((float)hi[src], o.pd8_hi_exp);
+            }
+        unsigned char* dst = reinterpret_cast<unsigned char*>(hi + 512);
+        for (int i = 0; i < 1024; ++i) dst[i] = strip[i];
+    }
+}
 // Vertex i of the set is row ids[i] of the constants (posedirs row stride 3 * V).  tag[i] = 1 + e when vertex i is the vertex of
 // output joint J + e (mesh set only), else 0; an empty tag: none.
 inline VertexSetImages vertex_set_images(const VertexSetShape& s, const std::vector<int>& ids, const std::vector<int>& tag, const float* v_template,
@@ -191,6 +225,7 @@ inline VertexSetImages vertex_set_images(const VertexSetShape& s, const std::vec
     }
     pdh.clear();
     pdl.clear();
+    if (three && s.pose_fp8) pose_fp8_strips(o, s.pd8_given, s.pd8_lo_exp, s.pd8_hi_exp);
     return o;
 }
 

@@ -1,0 +1,284 @@
+"""Host: the e4m3 correction operands of the SMPL stream kernel's pose phase (``csrc/k2b_lbs_fp8.h``, the strips of
+``k2b_model_tables.h``) through the development entries ``k2b_dev_e4m3_encode``, ``k2b_dev_lbs_x_fp8`` and
+``k2b_dev_lbs_pose_fp8_image`` (no device needed, outside include/k2b.h).
+
+* the encoder against an independent numpy e4m3fn encoder (nearest value of the 127 finite magnitudes, ties to the even code);
+* the packed Pd strips at the byte positions of the fragment layout, written out here a second time;
+* the error budget of ``X . Pd`` with the entry's own packed images, emulated in float64, on the synthetic model and three pose
+  regimes: at most 2.5e-6 m (half the project's 5e-6 gate) for the e4m3 form, 1e-7 for the three f16 products."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from keypoints2body_amd import native, synthetic
+
+F8_STEPS = 6            # 32-deep k-steps with e4m3 strips; k-step 6 keeps the f16 form
+PD_SCALE = 256.0
+X_HI_EXP, X_LO_EXP = -4, -15
+
+
+# ---- an independent encoder ---------------------------------------------------------------------------------------------------
+def _decode_table():
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, c & 7
+    mag = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8.0) * 2.0 ** (e.astype(np.float64) - 7))
+    mag[(e == 15) & (m == 7)] = np.nan
+    return np.where(c & 0x80, -mag, mag)
+
+
+def _np_encode(x):
+    """Nearest finite e4m3fn value, ties to the even code, saturating at +-448; NaN -> 0x7f | sign."""
+    x = np.asarray(x, dtype=np.float64)
+    mags = _decode_table()[:0x7f]                              # codes 0..0x7e: increasing magnitudes 0..448
+    a = np.minimum(np.abs(x), 448.0)
+    hi = np.clip(np.searchsorted(mags, a), 1, 0x7e)            # first code with magnitude >= a
+    lo = hi - 1
+    dlo, dhi = a - mags[lo], mags[hi] - a
+    code = np.where(dlo < dhi, lo, np.where(dhi < dlo, hi, np.where(lo % 2 == 0, lo, hi)))
+    code = np.where(np.isnan(x), 0x7f, code).astype(np.uint8)
+    return code | (np.signbit(x).astype(np.uint8) << 7)
+
+
+def _lib():
+    return native.load_library()
+
+
+def _encode(x, exp=0):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.size, dtype=np.uint8)
+    fn = _lib().k2b_dev_e4m3_encode
+    fn.restype = C.c_int
+    rc = fn(C.c_int64(x.size), x.ctypes.data_as(C.c_void_p), C.c_int32(exp), out.ctypes.data_as(C.c_void_p))
+    assert rc == 0
+    return out.reshape(x.shape)
+
+
+def test_encoder_reproduces_every_code():
+    dec = _decode_table()
+    finite = ~np.isnan(dec)
+    got = _encode(dec.astype(np.float32))
+    assert np.array_equal(got[finite], np.arange(256, dtype=np.uint8)[finite])
+    assert got[0x7f] == 0x7f and got[0xff] == 0xff            # NaN keeps its sign bit and stays NaN
+    assert _encode(np.float32(0.0)).item() == 0x00 and _encode(np.float32(-0.0)).item() == 0x80
+
+
+def test_encoder_matches_numpy_on_random_values_ties_subnormals_and_saturation():
+    rng = np.random.default_rng(1)
+    x = (2.0 ** rng.uniform(-12, 10, 100_000) * np.where(rng.random(100_000) < 0.5, -1, 1)).astype(np.float32)
+    assert np.array_equal(_encode(x), _np_encode(x))
+    dec = _decode_table()[:0x7f]
+    ties = ((dec[:-1] + dec[1:]) / 2).astype(np.float32)       # exact in fp32: midpoints of neighbours
+    edge = np.concatenate([ties, -ties, np.nextafter(ties, np.float32(0)), np.nextafter(ties, np.float32(1e9)),
+                           np.array([448, 449, 463.9, 464, 465, 480, 1e9, np.inf, -np.inf, 2.0 ** -10, 2.0 ** -11, 1.5 * 2.0 ** -10,
+                                     2.0 ** -9, 3 * 2.0 ** -10, 7.5 * 2.0 ** -9, 2.0 ** -6, 1e-30, -1e-30], dtype=np.float32)])
+    assert np.array_equal(_encode(edge), _np_encode(edge))
+    assert _encode(np.float32(1e9)).item() == 0x7e and _encode(np.float32(-np.inf)).item() == 0xfe
+    assert _encode(np.float32(2.0 ** -10)).item() == 0x00 and _encode(np.float32(3 * 2.0 ** -10)).item() == 0x02   # ties to even
+    for exp in (-15, -4, 0, 3):                                # the scaled form divides exactly
+        assert np.array_equal(_encode(x, exp), _np_encode(x.astype(np.float64) / 2.0 ** exp))
+    fn = _lib().k2b_dev_e4m3_scale_exp
+    fn.restype = C.c_int
+    for m, want in ((448.0, 0), (448.5, 1), (224.0, -1), (0.109, -12), (0.11, -11), (300.0, 0), (0.0, 0)):
+        assert fn(C.c_float(m)) == want, m
+
+
+# ---- the images -----------------------------------------------------------------------------------------------------------------
+_memo = {}
+
+
+def _consts():
+    if "c" not in _memo:
+        _memo["c"] = synthetic.make_body_model(0)
+    return _memo["c"]
+
+
+def _ids():
+    return np.sort(np.random.default_rng(2).choice(_consts().v_template.shape[0], 1000, replace=False)).astype(np.int32)
+
+
+def _image(pose_f16, ids=None, given=None):
+    """(spd as uint16, info = [pose_fp8, nv16, lo_exp, hi_exp]) of the vertex set `ids` of the synthetic model."""
+    c = _consts()
+    ids = np.ascontiguousarray(_ids() if ids is None else ids, dtype=np.int32)
+    V, J, NB = c.v_template.shape[0], c.parents.shape[0], c.shapedirs.shape[-1]
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    arrs = [f(c.v_template), f(c.shapedirs), f(c.posedirs), f(c.lbs_weights)]
+    fn = _lib().k2b_dev_lbs_pose_fp8_image
+    fn.restype = C.c_int
+    n, info = C.c_int64(0), np.zeros(4, dtype=np.int32)
+    gv = None if given is None else np.asarray(given, dtype=np.int32)
+    head = [C.c_int32(J), C.c_int32(NB), C.c_int32(V), C.c_int32(len(ids)), ids.ctypes.data_as(C.c_void_p)] + \
+           [a.ctypes.data_as(C.c_void_p) for a in arrs] + [C.c_int32(pose_f16), None if gv is None else gv.ctypes.data_as(C.c_void_p)]
+    assert fn(*head, None, C.byref(n), info.ctypes.data_as(C.c_void_p)) == 0
+    spd = np.zeros(n.value, dtype=np.uint16)
+    assert fn(*head, spd.ctypes.data_as(C.c_void_p), C.byref(n), info.ctypes.data_as(C.c_void_p)) == 0
+    return spd, info
+
+
+def _unpack(spd, info, n):
+    """The layout, a second time.  spd [k-step 7][16-vertex tile][coordinate 3][hi | lo] in 1 KiB pieces.  f16 piece: lane =
+    vertex row + 16 * (k >> 3) holds 8 halfs k & 7.  e4m3 piece (k-steps 0..5 of a pose_fp8 image, in place of lo): lane group g
+    (16 bytes per lane, lane = row + 16 g) = Pd_lo8[k 0..15], Pd_lo8[k 16..31], Pd_hi8[k 0..15], Pd_hi8[k 16..31].
+    Returns hi, lo (f16 terms as float64, lo NaN where the image has codes), lo8, hi8 (codes, 0 where none): [224][n][3]."""
+    fp8, nv16 = int(info[0]), int(info[1])
+    pieces = spd.reshape(7, nv16, 3, 2, 512)
+    halfs, raw = pieces.view(np.float16), pieces.view(np.uint8).reshape(7, nv16, 3, 2, 1024)
+    i = np.arange(n)
+    v16, r = i >> 4, i & 15
+    k = np.arange(224)
+    ks, kk = k >> 5, k & 31
+    at16 = ((kk >> 3)[:, None] * 16 + r[None, :]) * 8 + (kk & 7)[:, None]                      # [k][vertex]
+    hi = np.stack([halfs[ks[:, None], v16[None, :], c, 0, at16] for c in range(3)], axis=-1).astype(np.float64)
+    lo = np.stack([halfs[ks[:, None], v16[None, :], c, 1, at16] for c in range(3)], axis=-1).astype(np.float64)
+    lo8 = np.zeros((224, n, 3), dtype=np.uint8)
+    hi8 = np.zeros_like(lo8)
+    if fp8:
+        at_lo8 = ((kk >> 4)[:, None] * 16 + r[None, :]) * 16 + (kk & 15)[:, None]
+        at_hi8 = ((2 + (kk >> 4))[:, None] * 16 + r[None, :]) * 16 + (kk & 15)[:, None]
+        lo8 = np.stack([raw[ks[:, None], v16[None, :], c, 1, at_lo8] for c in range(3)], axis=-1)
+        hi8 = np.stack([raw[ks[:, None], v16[None, :], c, 1, at_hi8] for c in range(3)], axis=-1)
+        lo[: 32 * F8_STEPS] = np.nan
+        lo8[32 * F8_STEPS:] = 0
+        hi8[32 * F8_STEPS:] = 0
+    return hi, lo, lo8, hi8
+
+
+def test_pd_strips_hold_the_codes_of_the_f16_terms_at_the_layouts_positions():
+    ids = _ids()
+    n = len(ids)
+    spd16, info16 = _image(1)
+    spd8, info8 = _image(0)
+    assert info16[0] == 0 and info8[0] == 1 and info8[1] == info16[1] == (n + 127) // 128 * 8 and spd8.size == spd16.size
+    hi, lo, _, _ = _unpack(spd16, info16, n)
+    hi_b, lo_b, lo8, hi8 = _unpack(spd8, info8, n)
+    lo_exp, hi_exp = int(info8[2]), int(info8[3])
+    cut = 32 * F8_STEPS
+    assert np.array_equal(hi, hi_b) and np.array_equal(lo[cut:], lo_b[cut:])          # hi strips and k-step 6: the f16 image
+    # the constants themselves, split as the builder splits them
+    c = _consts()
+    pd = c.posedirs.reshape(207, -1, 3)[:, ids].astype(np.float32) * np.float32(PD_SCALE)
+    h = pd.astype(np.float16)
+    l = (pd - h.astype(np.float32)).astype(np.float16)
+    assert np.array_equal(hi[:207], h.astype(np.float64)) and np.array_equal(lo[:207], l.astype(np.float64))
+    # scales: the smallest at which the largest magnitude does not saturate
+    for e, term in ((lo_exp, lo[:cut]), (hi_exp, hi[:cut])):
+        m = np.abs(term).max()
+        assert m / 2.0 ** e <= 448.0 < m / 2.0 ** (e - 1)
+    assert np.array_equal(lo8[:cut], _np_encode(lo[:cut] / 2.0 ** lo_exp))
+    assert np.array_equal(hi8[:cut], _np_encode(hi[:cut] / 2.0 ** hi_exp))
+    dec = _decode_table()
+    assert np.abs(dec[hi8[:cut]] * 2.0 ** hi_exp - hi[:cut]).max() <= 2.0 ** -4 * np.abs(hi[:cut]).max()
+    # padding rows of the last 16-vertex tiles hold zero codes
+    raw = spd8.view(np.uint8).reshape(7, int(info8[1]), 3, 2, 64, 16)
+    assert not raw[:F8_STEPS, n // 16 + 1:, :, 1].any()
+    # a subset with the mesh's scales gets the mesh's codes
+    sub = ids[::7]
+    spd_s, info_s = _image(0, ids=sub, given=(lo_exp, hi_exp))
+    _, _, lo8_s, hi8_s = _unpack(spd_s, info_s, len(sub))
+    assert (info_s[2], info_s[3]) == (lo_exp, hi_exp) and np.array_equal(lo8_s, lo8[:, ::7]) and np.array_equal(hi8_s, hi8[:, ::7])
+
+
+# ---- error budget ---------------------------------------------------------------------------------------------------------------
+def _features(pose, betas):
+    """X [B][224] in float64 from float32 parameters: vec(R_j - I) of the 23 body joints (row-major), betas, 1, 1, zeros."""
+    B = pose.shape[0]
+    aa = pose.astype(np.float64).reshape(B, 23, 3)
+    th = np.linalg.norm(aa, axis=-1, keepdims=True)
+    ax = aa / np.maximum(th, 1e-300)
+    K = np.zeros((B, 23, 3, 3))
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -ax[..., 2], ax[..., 1], ax[..., 2]
+    K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -ax[..., 0], -ax[..., 1], ax[..., 0]
+    s, c1 = np.sin(th)[..., None], (1 - np.cos(th))[..., None]
+    RmI = s * K + c1 * (K @ K)
+    X = np.zeros((B, 224))
+    X[:, :207] = RmI.reshape(B, 207)
+    X[:, 207:217] = betas
+    X[:, 217:219] = 1.0
+    return X
+
+
+def _x_terms(X32):
+    x = np.ascontiguousarray(X32, dtype=np.float32).reshape(-1)
+    hi, lo = np.empty_like(x), np.empty_like(x)
+    hi8, lo8 = np.empty(x.size, dtype=np.uint8), np.empty(x.size, dtype=np.uint8)
+    fn = _lib().k2b_dev_lbs_x_fp8
+    fn.restype = C.c_int
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert fn(C.c_int64(x.size), p(x), p(hi), p(lo), p(hi8), p(lo8)) == 0
+    sh = X32.shape
+    return hi.reshape(sh).astype(np.float64), lo.reshape(sh).astype(np.float64), hi8.reshape(sh), lo8.reshape(sh)
+
+
+REGIMES = ("0.6 N(0,1)", "uniform +-pi", "20 rad")
+
+
+def _poses(regime, B=256):
+    rng = np.random.default_rng(REGIMES.index(regime))
+    if regime == "0.6 N(0,1)":
+        pose = 0.6 * rng.standard_normal((B, 69))
+    elif regime == "uniform +-pi":
+        pose = rng.uniform(-np.pi, np.pi, (B, 69))
+    else:
+        d = rng.standard_normal((B, 23, 3))
+        pose = (20.0 * d / np.linalg.norm(d, axis=-1, keepdims=True) * rng.uniform(0.9, 1.1, (B, 23, 1))).reshape(B, 69)
+    return pose.astype(np.float32), rng.uniform(-2.5, 2.5, (B, 10)).astype(np.float32)
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+def test_error_budget_of_x_pd_with_the_packed_images(regime):
+    """X . Pd (all 219 features: pose correctives, shape, template) for 256 frames x 1000 vertices x 3 coordinates in float64:
+    the hi product of the f16 terms, plus the corrections either as the two f16 products or - k-steps 0..5 of the e4m3 image -
+    from the decoded codes with their scales.  Bounds (issue): e4m3 form <= 2.5e-6 m = half the 5e-6 gate, twice what the
+    author's emulation read; three f16 products <= 1e-7 (it read 1e-8)."""
+    ids = _ids()
+    n = len(ids)
+    c = _consts()
+    pose, betas = _poses(regime)
+    X32 = _features(pose, betas).astype(np.float32)
+    Pd = np.zeros((224, n, 3))
+    Pd[:207] = c.posedirs.reshape(207, -1, 3)[:, ids]
+    Pd[207:217] = np.moveaxis(c.shapedirs[ids], -1, 0)
+    Pd[217] = c.v_template[ids]
+    want = np.einsum("bk,kvc->bvc", X32.astype(np.float64), Pd)
+    xh, xl, xh8, xl8 = _x_terms(X32)
+    dec = _decode_table()
+    cut = 32 * F8_STEPS
+    worst = {}
+    for name, f16 in (("f16", 1), ("e4m3", 0)):
+        spd, info = _image(f16)
+        hi, lo, lo8, hi8 = _unpack(spd, info, n)
+        acc = np.einsum("bk,kvc->bvc", xh, hi)
+        if f16:
+            acc += np.einsum("bk,kvc->bvc", xh, lo) + np.einsum("bk,kvc->bvc", xl, hi)
+        else:
+            acc += np.einsum("bk,kvc->bvc", xh[:, cut:], lo[cut:]) + np.einsum("bk,kvc->bvc", xl[:, cut:], hi[cut:])
+            a_hi, a_lo = dec[xh8[:, :cut]] * 2.0 ** X_HI_EXP, dec[xl8[:, :cut]] * 2.0 ** X_LO_EXP
+            b_lo, b_hi = dec[lo8[:cut]] * 2.0 ** int(info[2]), dec[hi8[:cut]] * 2.0 ** int(info[3])
+            acc += np.einsum("bk,kvc->bvc", a_hi, b_lo) + np.einsum("bk,kvc->bvc", a_lo, b_hi)
+        worst[name] = float(np.abs(acc / PD_SCALE - want).max())
+    print(f"{regime}: X.Pd error, three f16 products {worst['f16']:.2e} m, e4m3 corrections {worst['e4m3']:.2e} m")
+    assert worst["f16"] <= 1e-7, worst
+    assert worst["e4m3"] <= 2.5e-6, worst
+
+
+# ---- the stand-alone host program ---------------------------------------------------------------------------------------------
+def test_host_program_holds_encoder_route_and_images_to_their_definitions(tmp_path):
+    """``tests/host/lbs_pose_fp8_check.cpp``: encoder, route rule and the strips of 17-24 joints x 1-10 coefficients (mesh and the
+    21-vertex set), built with the address and undefined-behaviour sanitizers, as ``tests/test_lbs_plan_host.py``."""
+    import shutil
+    import subprocess
+    from pathlib import Path
+    repo = Path(__file__).resolve().parents[1]
+    cxx = next((c for c in ("/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++", "clang++") if shutil.which(c)), None)
+    assert cxx is not None, "the host check needs the clang++ of the HIP toolchain that builds libk2b.so"
+    exe = tmp_path / "lbs_pose_fp8_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", str(repo / "keypoints2body_amd" / "csrc"), str(repo / "tests" / "host" / "lbs_pose_fp8_check.cpp"), "-o", str(exe)], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    print(run.stdout + run.stderr)
+    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
+    lines = run.stdout.splitlines()
+    for section in ("encoder", "route", "images"):
+        assert f"{section}: ok" in lines, section
+    assert lines[-1] == "0 failures"
