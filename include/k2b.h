@@ -38,7 +38,7 @@
  *     updates params, m and v in place by definition.  (tests/test_gpu_caller_buffers.py)
  *   - frames are independent, non-finite inputs included: in every entry with a frame or
  *     sequence dimension (k2b_fit_world, k2b_fit_world_lbfgs, k2b_fit_sequence, k2b_fit_sequences,
- *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_multiview, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
+ *     k2b_fit_image, k2b_fit_image_sequences, k2b_fit_multiview, k2b_fit_multiview_sequences, k2b_fit_sequence_lbfgs, k2b_fit_sequences_lbfgs, k2b_shape_pass_lbfgs, k2b_lbs,
  *     k2b_lbs_backward, k2b_vertex_term, k2b_surface_term, k2b_surface_term_image) each output of a frame (in the chain
  *     entries and the shape pass: of a sequence; inside a chain a frame also never depends on
  *     a LATER frame) depends only on that frame's own inputs, bit for bit, even when another
@@ -51,8 +51,8 @@
  *     more elements of that same frame.  (tests/test_gpu_isolation.py)
  *   - a call does not depend on the calls before it: every output is, bit for bit, what the same call returns on freshly
  *     created handles, whatever batches (larger ones, non-finite ones, refused ones) its handles, its thread and its
- *     stream served before, and whatever the output buffers held; k2b_fit_multiview included, whose camera table travels in
- *     the kernel arguments and leaves nothing on a handle.  (tests/test_gpu_call_history.py, tests/test_gpu_multiview_fit.py;
+ *     stream served before, and whatever the output buffers held; k2b_fit_multiview and k2b_fit_multiview_sequences included,
+ *     whose camera table travels in the kernel arguments and leaves nothing on a handle.  (tests/test_gpu_call_history.py, tests/test_gpu_multiview_fit.py;
  *     DESIGN.md 4.4e.)
  */
 #ifndef K2B_H
@@ -188,7 +188,7 @@ typedef struct k2b_fit_config {
     int32_t prior_pose_dims;
     int32_t num_betas_prior;
     /* K2B_SINCE(1, 7).  Joint term in image space: 0 = off (the 3D term above, the default); 1 = perspective reprojection
-     * (k2b_fit_world, and the chains of k2b_fit_image_sequences).  The target buffer keeps its [B][K][3] layout; row k holds
+     * (k2b_fit_world, and the chains of k2b_fit_image_sequences; several cameras: k2b_fit_multiview, k2b_fit_multiview_sequences).  The target buffer keeps its [B][K][3] layout; row k holds
      * (u - cx, v - cy, ignored): pixel coordinates WITH THE PRINCIPAL POINT ALREADY SUBTRACTED by the caller (in float64, before the rounding to float32:
      * raw pixel coordinates of a few hundred lose more in that rounding than the gradient tests allow).  For
      * every targeted joint, with (X, Y, Z) = p_k + transl (transl = the camera translation, as in the camera-space fitter):
@@ -465,6 +465,47 @@ int k2b_fit_multiview(const k2b_model *model, const k2b_prior *prior, const k2b_
                       const float *transl_in, const float *preserve_pose, const float *transl_prior_target,
                       float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
                       float *loss_out, float *grad_out, void *stream) K2B_SINCE(1, 10);
+
+/* ---------------------------------------------------------------------------------
+ * k2b_fit_multiview_sequences (ABI 1.11) — warm-start chains over videos of a calibrated rig: k2b_fit_image_sequences' chain
+ * under the joint term of k2b_fit_multiview, S ragged videos side by side in ONE launch (S = 1: the single video).  Argument
+ * conventions as k2b_fit_image_sequences (packed rows, host lengths / offsets, *_in one row per sequence, loss_out may be
+ * NULL, followup_freeze_betas), plus the rig of k2b_fit_multiview.
+ *   cameras    HOST [C], ONE rig shared by all sequences and all frames, read during the call (by value in the kernel
+ *              arguments: nothing is uploaded for them and nothing synchronises; the slot table of the sequences goes up through
+ *              the calling thread's pinned staging, as for the other ragged entries)
+ *   keypoints  dev [sum T][C][K][3]: rows (u', v', ignored), pixels minus THAT camera's principal point
+ *   conf       dev [C][K], or [sum T][C][K] with cfg->conf_per_frame; NULL = ones
+ *   transl_*   the body's WORLD translation
+ * 1 <= num_views <= 8; cfg->projection must be 1; cfg->focal is not read.  Step 0 of a sequence is k2b_fit_multiview under
+ * `cfg`: cfg->num_iters iterations, no preserve term.  Step t > 0 starts from step t - 1's RESULT, preserves that result's
+ * body pose with cfg->pose_preserve_weight, runs followup_iters iterations with a fresh Adam state and, with
+ * followup_freeze_betas != 0, holds the shape as cfg->freeze_betas = 1 would (24-joint models hold all betas, SMPL-H / SMPL-X
+ * the first num_betas_prior coefficients - the expression stays free); cfg->freeze_betas itself applies to every step.  A
+ * sequence of length 1 is the first-frame fit; a sequence of length 0 writes nothing.  loss_out is every frame's
+ * last-iteration loss before its step, preserve term included.
+ * Guarantees (tests/test_gpu_multiview_chain.py):
+ *   - a sequence's rows are bit-identical to that sequence fitted alone, in any order and among any neighbours;
+ *   - they are bit-identical to a host loop of k2b_fit_multiview calls that hands each result on (frame t > 0: start and
+ *     preserve_pose = frame t - 1's result, followup_iters iterations, freeze_betas for the follow-up freeze);
+ *   - the views are summed in the order 0 .. C - 1;
+ *   - a non-finite keypoint stays in its own SEQUENCE: the frames before it are untouched, the frame itself reports a
+ *     non-finite loss, and the frames behind it in that sequence may be non-finite (a warm start inherits).
+ * Refused before anything is queued, outputs untouched: num_views outside 1..8, a non-finite camera field, a focal that is not
+ * finite and positive, projection != 1, cfg->transl_prior_weight != 0, bad lengths / offsets, bad followup_iters, 2^27 or more
+ * target rows (sum T x C x K) on a 24-joint model (K2B_ERR_INVALID_ARGUMENT); surface targets (a model index >= J), a 24-joint
+ * model without a scan plan or created under K2B_FIT_SCAN64=1 (K2B_ERR_UNSUPPORTED).  Adam only.
+ * ------------------------------------------------------------------------------- */
+int k2b_fit_multiview_sequences(const k2b_model *model, const k2b_prior *prior, const k2b_fit_config *cfg,
+                                int32_t num_sequences, const int32_t *lengths, const int32_t *offsets,
+                                int32_t followup_iters, int32_t followup_freeze_betas,
+                                int32_t num_views, const k2b_camera *cameras,
+                                int32_t num_targets, const int32_t *model_joint_index,
+                                const float *keypoints, const float *conf,
+                                const float *global_orient_in, const float *body_pose_in, const float *betas_in,
+                                const float *transl_in,
+                                float *global_orient_out, float *body_pose_out, float *betas_out, float *transl_out,
+                                float *loss_out, void *stream) K2B_SINCE(1, 11);
 
 /* ---------------------------------------------------------------------------------
  * k2b_shape_pass_lbfgs (ABI 1.3) — the shape pre-pass of many sequences together (reference core/shape.py:10-115,

@@ -1,8 +1,9 @@
-"""``optimize_params_frame_multiview`` / ``optimize_params_frames_multiview``: fit one frame, or T independent frames, of 2D
-keypoints seen by several calibrated cameras at once, executed on the HIP engine.
+"""``optimize_params_frame_multiview`` / ``optimize_params_frames_multiview`` / ``optimize_params_sequence_multiview`` /
+``optimize_params_sequences_multiview``: fit one frame, T independent frames, one video or many videos of 2D keypoints seen by
+several calibrated cameras at once, executed on the HIP engine.
 
 The reference has no counterpart (its ``api/frame.py:71-75`` raises for ``input_type="joints2d"``).  What is computed is defined
-in ``core/fitters/multiview.py`` and ``include/k2b.h`` (``k2b_fit_multiview``)."""
+in ``core/fitters/multiview.py`` and ``include/k2b.h`` (``k2b_fit_multiview``, ``k2b_fit_multiview_sequences``)."""
 from __future__ import annotations
 
 import dataclasses
@@ -11,13 +12,13 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ..core.config import FrameOptimizeConfig, ModelType, frame_config_from
+from ..core.config import FrameOptimizeConfig, ModelType, SequenceOptimizeConfig, frame_config_from, sequence_config_from
 from ..core.fitters.image_space import focal_pair
 from ..core.fitters.multiview import MAX_VIEWS, MultiViewFitter, check_rotation
 from ..core.joints.adapters import resolve_adapter
 from ..models.smpl_data import BodyModelFitResult, BodyModelParams
 from . import common
-from .sequence import _batched_results, _stack_starts
+from .sequence import SequenceBatch, _batched_results, _packed_batch, _stack_starts
 
 
 @dataclasses.dataclass(frozen=True)
@@ -87,7 +88,7 @@ def _fitter_and_starts(uv, cf, frame_cfg, body_model, model, init_params, count,
         raise NotImplementedError(f"the multi-view fit takes kinematic targets only (model indices below {model.num_joints})")
     fitter = MultiViewFitter(model, step_size=frame_cfg.step_size, num_iters=frame_cfg.num_iters, use_lbfgs=False,
                              joints_category=category, device=device, pose_prior_num_gaussians=frame_cfg.pose_prior_num_gaussians,
-                             pose_prior=pose_prior)
+                             pose_prior=pose_prior, num_iters_followup=frame_cfg.num_iters_followup)
     if init_params is None:
         starts = [common.default_start(model, body_model, category, "camera", None, mean_params, device)] * count
     else:
@@ -114,7 +115,8 @@ def optimize_params_frame_multiview(keypoints2d, *, cameras: Sequence[Camera], c
     triangulation of the four torso joints, each of which at least two views must see (else ``ValueError``).  The result's
     ``params.transl`` is the world translation; joints and vertices are in world space (``MultiViewFitter``).
 
-    A warm-start chain over multi-view videos is not built: ``optimize_params_frames_multiview`` fits independent frames."""
+    ``optimize_params_frames_multiview`` fits independent frames, ``optimize_params_sequence_multiview`` a video as a warm-start
+    chain."""
     if body_model not in common.SMPL_FAMILY:
         raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
     cams, uv, cf = _views(keypoints2d, conf, cameras, frames=False)
@@ -138,8 +140,8 @@ def optimize_params_frames_multiview(keypoints, *, cameras: Sequence[Camera], bo
     per-view confidence column, ``init_params`` None or one start per frame.  Two fit launches, one evaluate-only launch and one
     LBS call in total, whatever T; frame t of the result equals the frame entry on that frame bit for bit.
 
-    The frames do not warm-start one another: a chain over multi-view videos (each frame from its predecessor's result, with the
-    preserve term) is not built."""
+    The frames do not warm-start one another: ``optimize_params_sequence_multiview`` runs the chain over a video (each frame from
+    its predecessor's result, with the preserve term)."""
     if body_model not in common.SMPL_FAMILY:
         raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
     cams, uv, cf = _views(keypoints, None, cameras, frames=True)
@@ -160,3 +162,85 @@ def optimize_params_frames_multiview(keypoints, *, cameras: Sequence[Camera], bo
                                                 pose_preserve_weight=frame_cfg.pose_preserve_weight,
                                                 freeze_betas=frame_cfg.freeze_betas, per_frame_conf=True)
     return _batched_results(fitter, out, joints, verts, loss, starts[0], T)
+
+
+def _fit_videos(videos, cameras, body_model, model, config, init_params, joint_layout, target_model_indices, sigma, joint_loss_weight,
+                device, pose_prior, mean_params, want_vertices=True):
+    """The shared body of the two video entry points: ``(fitter, one start per video, params, joints, vertices, loss, lengths)``
+    with the results packed over all frames.  Every refusal of the arguments comes before any device call."""
+    if body_model not in common.SMPL_FAMILY:
+        raise ValueError(f"Unsupported body_model for 2D keypoints: {body_model}")
+    seq_cfg = sequence_config_from(config) if config is not None else SequenceOptimizeConfig(frame=FrameOptimizeConfig(use_lbfgs=False))
+    frame_cfg = seq_cfg.frame
+    if frame_cfg.use_lbfgs:
+        raise NotImplementedError("the multi-view fit runs Adam only: pass a config with use_lbfgs=False")
+    S = len(videos)
+    if init_params is not None and (not isinstance(init_params, (list, tuple)) or len(init_params) != S):
+        raise ValueError("init_params must be None or a list with one start per sequence")
+    cams, uvs, cfs = None, [], []
+    for v in videos:
+        cams, uv, cf = _views(v, None, cameras, frames=True)
+        uvs.append(uv)
+        cfs.append(cf)
+    if len({u.shape[2] for u in uvs}) != 1:
+        raise ValueError("every sequence must have the same number of keypoints")
+    if seq_cfg.limit_frames is not None and seq_cfg.limit_frames > 0:
+        uvs, cfs = [u[: seq_cfg.limit_frames] for u in uvs], [c[: seq_cfg.limit_frames] for c in cfs]
+    uv, cf = np.concatenate(uvs, axis=0), np.concatenate(cfs, axis=0)
+    lengths = np.asarray([u.shape[0] for u in uvs], dtype=np.int32)
+    device = common.resolve_device(device)
+    fitter, starts, uv, cf = _fitter_and_starts(uv, cf, frame_cfg, body_model, model, init_params, S, joint_layout, target_model_indices,
+                                                device, pose_prior, mean_params)
+    kw = dict(target_model_indices=target_model_indices, sigma=sigma, joint_loss_weight=joint_loss_weight, want_vertices=want_vertices,
+              pose_preserve_weight=frame_cfg.pose_preserve_weight, freeze_betas=frame_cfg.freeze_betas)
+    if seq_cfg.use_previous_frame_init or len(uv) == 0:
+        out, joints, verts, loss = fitter.fit_sequences(_stack_starts(starts, device), uv, lengths, cams, cf, **kw)
+    else:                                       # independent frames: both stages for every frame, each from its video's start
+        rows = _stack_starts([starts[s] for s in range(S) for _ in range(int(lengths[s]))], device)
+        out, joints, verts, loss = fitter.fit_batch(rows, uv, cams, cf, seq_ind=0, per_frame_conf=True, **kw)
+    return fitter, starts, out, joints, verts, loss, lengths
+
+
+def optimize_params_sequence_multiview(keypoints, *, cameras: Sequence[Camera], body_model: ModelType = "smpl", model=None,
+                                       config: Optional[SequenceOptimizeConfig | dict] = None,
+                                       init_params: Optional[BodyModelParams] = None, joint_layout: Optional[str] = None,
+                                       target_model_indices=None, sigma: float = 100.0, joint_loss_weight: float = 1.0, device=None,
+                                       pose_prior=None, mean_params: Optional[tuple] = None) -> list[BodyModelFitResult]:
+    """Fit a video of a calibrated rig, ``keypoints`` (T,C,K,2) pixels or (T,C,K,3) with a per-frame, per-view confidence column,
+    as ONE warm-start chain on the device: the triangulated start and stage 1 for the first frame, then one
+    ``k2b_fit_multiview_sequences`` launch for all frames and one LBS call; results in temporal order, frame 0's parameters equal
+    to ``optimize_params_frame_multiview`` on that frame.  ``cameras``: the rig, fixed over the video.
+
+    ``config`` is a ``SequenceOptimizeConfig`` or dict (without one: Adam, the defaults): ``frame.num_iters`` iterations for
+    stage 1 and for the first frame, ``frame.num_iters_followup`` for every later frame, ``frame.step_size``,
+    ``frame.pose_preserve_weight``, ``frame.freeze_betas`` (the frames after the first hold the first frame's shape);
+    ``frame.use_lbfgs=True`` raises ``NotImplementedError``.  ``use_shape_optimization`` is IGNORED: the first frame estimates the
+    shape.  With ``use_previous_frame_init=False`` every frame is an independent two-stage fit from the video's start
+    (``MultiViewFitter.fit_batch``, as ``optimize_params_frames_multiview``).  ``limit_frames`` applies.  A dict of blocks, or a
+    model index at or above the joint count, raises ``NotImplementedError`` (kinematic targets only).  The other arguments are
+    ``optimize_params_frame_multiview``'s.  Each result's ``loss`` is the chain's own: the loss of the frame's last iteration
+    before its step, preserve term included (``MultiViewFitter.fit_sequences``), not the frame entry's re-evaluated loss."""
+    fitter, starts, out, joints, verts, loss, lengths = _fit_videos(
+        [keypoints], cameras, body_model, model, config, None if init_params is None else [init_params], joint_layout,
+        target_model_indices, sigma, joint_loss_weight, device, pose_prior, mean_params)
+    return _batched_results(fitter, out, joints, verts, loss, starts[0], int(lengths[0]))
+
+
+def optimize_params_sequences_multiview(keypoints_seqs, *, cameras: Sequence[Camera], body_model: ModelType = "smpl", model=None,
+                                        config: Optional[SequenceOptimizeConfig | dict] = None, init_params: Optional[list] = None,
+                                        joint_layout: Optional[str] = None, target_model_indices=None, sigma: float = 100.0,
+                                        joint_loss_weight: float = 1.0, device=None, pose_prior=None,
+                                        mean_params: Optional[tuple] = None) -> SequenceBatch:
+    """``optimize_params_sequence_multiview`` for many videos of different lengths recorded by ONE rig, side by side: stage 1 for
+    all first frames in one launch, all chains in ONE ``k2b_fit_multiview_sequences`` launch; a packed ``SequenceBatch`` whose
+    sequence s equals the single call on it bit for bit.  ``init_params``: None or one start (one row) per video; ``config`` and
+    everything else as ``optimize_params_sequence_multiview``."""
+    if not isinstance(keypoints_seqs, (list, tuple)):
+        raise TypeError("keypoints_seqs must be a list of sequences")
+    if len(keypoints_seqs) == 0:
+        raise ValueError("keypoints_seqs is empty")
+    fitter, starts, out, joints, _, loss, lengths = _fit_videos(
+        list(keypoints_seqs), cameras, body_model, model, config, init_params, joint_layout, target_model_indices, sigma,
+        joint_loss_weight, device, pose_prior, mean_params, want_vertices=False)
+    from ..native import ragged_offsets
+    return _packed_batch(fitter, out, joints, loss, lengths, ragged_offsets(lengths), starts)

@@ -24,6 +24,11 @@ It is modelled on ``ImageSpaceFitter``; what several views change:
 * result: ``transl`` is the WORLD translation, joints and vertices come from the final forward with it applied (as the world
   fitter returns them), ``loss`` is stage 2 re-evaluated at the result without the preserve term (one evaluate-only launch).
 
+Videos (``fit_sequences``): S ragged videos of one rig as warm-start chains - the triangulated start and stage 1 for the S first
+frames as one launch, then the whole of stage 2 for every frame of every video as ONE launch (``k2b_fit_multiview_sequences``): a
+video's first frame is stage 2 as above, every later frame starts from its predecessor's result, preserves that result's body pose
+and, with ``freeze_betas``, holds the shape the first frame estimated.
+
 Adam only (``use_lbfgs=True`` raises), kinematic targets only (a model index at or above the joint count raises
 ``NotImplementedError``: the multi-view term is not built into the surface kernels).
 """
@@ -35,8 +40,9 @@ import numpy as np
 import torch
 
 from ... import native
-from ...models.smpl_data import BodyModelFitResult, SMPLData
+from ...models.smpl_data import BodyModelFitResult, SMPLData, select_rows
 from ...prior import MaxMixturePrior
+from ..config import FrameOptimizeConfig
 from .common import TORSO_IDX, FitterBase, stage1_config, stage2_config
 from .image_space import centred_keypoints, check_torso_targets, focal_pair
 
@@ -120,7 +126,8 @@ class MultiViewFitter(FitterBase):
     """Per-frame optimizer against the 2D keypoints of several calibrated cameras, executed on one MI355X."""
 
     def __init__(self, smpl_model, step_size=1e-2, num_iters=100, use_lbfgs=False, joints_category="AMASS", device=None,
-                 pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None):
+                 pose_prior_num_gaussians=8, pose_prior: Optional[MaxMixturePrior] = None,
+                 num_iters_followup=FrameOptimizeConfig.num_iters_followup):
         if use_lbfgs:
             raise NotImplementedError("MultiViewFitter runs Adam only: the device L-BFGS entries refuse the projected joint term; "
                                       "pass use_lbfgs=False")
@@ -128,6 +135,7 @@ class MultiViewFitter(FitterBase):
         if self.smpl.num_joints not in (24, 52, 55):
             raise NotImplementedError(f"a body model with {self.smpl.num_joints} joints: the fit kernels are built for 24, 52 and 55")
         self.num_iters = num_iters
+        self.num_iters_followup = num_iters_followup      # iterations of a video's frames after its first (fit_sequences)
         self._joint_basis = None
 
     def stage_configs(self, seq_ind=0, sigma=100.0, joint_loss_weight=1.0, pose_preserve_weight=5.0, freeze_betas=True):
@@ -168,6 +176,23 @@ class MultiViewFitter(FitterBase):
         joints, vertices, per-frame loss)``.  `keypoints2d` (B, C, K, 2) in pixels, per view in the order of this fitter's joint
         category or of `target_model_indices`; `cameras` C objects with ``rotation``, ``translation``, ``focal``,
         ``principal_point``; `conf` (C, K) or, with `per_frame_conf`, (B, C, K)."""
+        table, model_idx, targets_d, cf_d, torso_tgt, torso_on, (go, bp, be), transl0 = self._prepare(
+            init_params, keypoints2d, None, cameras, conf, target_model_indices, per_frame_conf)
+        cfg1, cfg2, _ = self.stage_configs(seq_ind, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas)
+        s1 = self._fit_views(cfg1, table, TORSO_IDX, torso_tgt, torso_on, dict(global_orient=go, body_pose=bp, betas=be, transl=transl0))
+        s2 = self._fit_views(cfg2, table, model_idx, targets_d, cf_d, s1)
+        out = {k: s2[k] for k in native.PARAM_KEYS}
+        # the loss at the result: stage 2's terms without the preserve term, one evaluate-only launch
+        cfg2.num_iters, cfg2.step_size, cfg2.pose_preserve_weight = 1, 0.0, 0.0
+        out["loss"] = self._fit_views(cfg2, table, model_idx, targets_d, cf_d, out)["loss"]
+        self.last_init_transl = transl0
+        return self._result(out, run_forward, want_vertices)
+
+    def _prepare(self, init_params, keypoints2d, first_rows, cameras, conf, target_model_indices, per_frame_conf):
+        """What both stages read: ``(camera table, model joint per target, centred targets, confidences, stage 1's torso targets
+        and which of them are seen, start rows, triangulated initial translation)``, everything before the first device call.
+        `first_rows` (None: every frame) names the frames the start rows belong to: a video's first frames, which alone get an
+        initial translation and stage 1."""
         R, t, focal, pp = camera_arrays(cameras)
         kp = keypoints2d.detach().cpu().numpy() if isinstance(keypoints2d, torch.Tensor) else np.asarray(keypoints2d)
         if kp.ndim != 4 or kp.shape[1] != len(R) or kp.shape[3] != 2:
@@ -192,12 +217,16 @@ class MultiViewFitter(FitterBase):
         torso_cols = [model_idx.index(j) for j in TORSO_IDX]
 
         # initial translation: the triangulated torso against the model's (host, float64)
-        torso_uv = targets[:, :, torso_cols, :2].astype(np.float64)
+        firsts = targets if first_rows is None else targets[np.asarray(first_rows, dtype=np.int64)]
+        torso_uv = firsts[:, :, torso_cols, :2].astype(np.float64)
         torso_cf = None if cf is None else cf[..., torso_cols]
-        usable = np.ones((B, C, 4), dtype=bool) if torso_cf is None else np.broadcast_to(torso_cf != 0, (B, C, 4))
+        if torso_cf is not None and first_rows is not None and per_frame_conf:
+            torso_cf = torso_cf[np.asarray(first_rows, dtype=np.int64)]
+        n_first = firsts.shape[0]                                     # the frames that get a start: all, or the videos' first
+        usable = np.ones((n_first, C, 4), dtype=bool) if torso_cf is None else np.broadcast_to(torso_cf != 0, (n_first, C, 4))
         world = triangulate_dlt(torso_uv, usable, R, t, focal)
         go, bp, be = self._start_rows(init_params)
-        if not all(s.shape[0] == B for s in (go, bp, be)):
+        if not all(s.shape[0] == n_first for s in (go, bp, be)):
             raise ValueError("init_params and keypoints2d disagree on the number of frames")
         mean4 = lambda a: (a[:, 0] + a[:, 1] + a[:, 2] + a[:, 3]) / 4.0
         transl0 = torch.from_numpy((mean4(world) - mean4(self._start_torso(go, bp, be))).astype(np.float32)).to(self.device)
@@ -205,15 +234,47 @@ class MultiViewFitter(FitterBase):
         table = native.camera_table(list(zip(R, t, focal)))
         dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
         targets_d, cf_d = dev(targets), dev(cf)
-        torso_tgt = dev(targets[:, :, torso_cols])
+        torso_tgt = dev(firsts[:, :, torso_cols])
         torso_on = None if torso_cf is None else dev((torso_cf != 0).astype(np.float32))                    # seen: 1, not seen: out
-        cfg1, cfg2, _ = self.stage_configs(seq_ind, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas)
+        return table, model_idx, targets_d, cf_d, torso_tgt, torso_on, (go, bp, be), transl0
+
+    def fit_sequences(self, init_params: SMPLData, keypoints2d, lengths, cameras: Sequence, conf=None, target_model_indices=None,
+                      sigma: float = 100.0, joint_loss_weight: float = 1.0, pose_preserve_weight: float = 5.0, freeze_betas: bool = True,
+                      want_vertices: bool = True, run_forward: bool = True):
+        """S videos of one rig as warm-start chains: `init_params` one start row per video, `keypoints2d` packed (sum T, C, K, 2)
+        pixels, `lengths` (S,) frames per video (0: an empty one, whose start row is not read), `cameras` the rig shared by all
+        videos and frames, `conf` None, (C, K) or one table per frame (sum T, C, K).  Two fit launches whatever S and T: the
+        triangulated translation of the S first frames and stage 1 over them exactly as ``fit_batch`` runs it, then ONE
+        ``k2b_fit_multiview_sequences`` launch under stage 2's configuration of ``stage_configs(seq_ind=0)``: a video's first
+        frame gets ``num_iters`` iterations and no preserve term (so its parameters equal ``fit_batch``'s on that frame alone),
+        every later frame starts from its predecessor's result, preserves that result's body pose with `pose_preserve_weight`,
+        runs ``num_iters_followup`` iterations with a fresh optimiser and, with `freeze_betas`, holds the shape (SMPL-H / SMPL-X:
+        the betas; the expression stays free).
+
+        Returns ``fit_batch``'s ``(params, joints, vertices, loss)`` over the sum T packed rows.  ``loss`` is the chain's own: a
+        frame's loss at its LAST iteration, before that iteration's step, preserve term included - the convention of the other
+        chains - and not ``fit_frame``'s loss re-evaluated at the result."""
+        L = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if (L < 0).any():
+            raise ValueError("lengths must not be negative")
+        n = int(np.shape(keypoints2d)[0])
+        if int(L.sum()) != n:
+            raise ValueError(f"lengths sum to {int(L.sum())}, keypoints2d has {n} frames")
+        live = np.flatnonzero(L > 0)
+        offsets = np.concatenate(([0], np.cumsum(L)[:-1])) if L.size else L
+        per_frame = conf is not None and torch.as_tensor(conf).dim() == 3
+        if live.size == 0:                                            # no frame at all: zero rows of the right widths
+            camera_arrays(cameras)
+            return self._result(native._fit_outputs(self.smpl.native, (0,)), run_forward, want_vertices)
+        table, model_idx, targets_d, cf_d, torso_tgt, torso_on, (go, bp, be), transl0 = self._prepare(
+            select_rows(init_params, live, L.size), keypoints2d, offsets[live], cameras, conf, target_model_indices, per_frame)
+        cfg1, cfg2, _ = self.stage_configs(0, sigma, joint_loss_weight, pose_preserve_weight, freeze_betas)
+        cfg2.pose_preserve_weight = float(pose_preserve_weight)       # (the chain leaves it out of a video's first frame itself)
+        cfg2.conf_per_frame = int(per_frame)
         s1 = self._fit_views(cfg1, table, TORSO_IDX, torso_tgt, torso_on, dict(global_orient=go, body_pose=bp, betas=be, transl=transl0))
-        s2 = self._fit_views(cfg2, table, model_idx, targets_d, cf_d, s1)
-        out = {k: s2[k] for k in native.PARAM_KEYS}
-        # the loss at the result: stage 2's terms without the preserve term, one evaluate-only launch
-        cfg2.num_iters, cfg2.step_size, cfg2.pose_preserve_weight = 1, 0.0, 0.0
-        out["loss"] = self._fit_views(cfg2, table, model_idx, targets_d, cf_d, out)["loss"]
+        out = native.fit_multiview_sequences(self.smpl.native, self.pose_prior.native, cfg2, int(self.num_iters_followup), bool(freeze_betas),
+                                             table, model_idx, L[live], targets_d, cf_d, s1["global_orient"], s1["body_pose"], s1["betas"],
+                                             s1["transl"])
         self.last_init_transl = transl0
         return self._result(out, run_forward, want_vertices)
 

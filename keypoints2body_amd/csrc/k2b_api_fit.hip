@@ -237,7 +237,7 @@ int fit_fused(k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cf
     if (!t.vsel.empty())
         return fit_world_vertex_joints(model, cfg, a, a.tr_prior, 0, t, c.stream,
                                        [&](const k2b::FitArgs& e) { return k2b::launch_fit_world(e, c.stream); });
-    HIP_TRY(k2b::launch_fit_world(a, c.stream));
+    HIP_TRY(k2b::launch_fit_world(a, c.stream, c.chain.frames));
     return K2B_OK;
 }
 
@@ -266,7 +266,8 @@ int fit_frames(k2b::rules::Entry entry, const k2b_model* model, const k2b_prior*
 // Many warm-start sequences of different lengths side by side (the Adam branch): every sequence is k2b_fit_sequence's chain,
 // packed frames [sum T][...], ONE launch (the fused kernel for 24-joint models, the tree kernel for SMPL-H / SMPL-X).  A
 // sequence's result does not depend on the others, on their number or on their order.  k2b_fit_sequences fits 3D targets;
-// k2b_fit_image_sequences (ABI 1.8) is the same chain under the projected joint term, whose follow-up frames may hold the shape.
+// k2b_fit_image_sequences (ABI 1.8) is the same chain under the projected joint term, whose follow-up frames may hold the shape;
+// k2b_fit_multiview_sequences (ABI 1.11) that chain under the multi-view term (FitCall::num_views, cameras set by the entry).
 int fit_ragged_chain(k2b::rules::Entry entry, const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
                      const int32_t* lengths, const int32_t* offsets, int32_t followup_iters, bool freeze_shape, FitCall c) {
     k2b::rules::Facts facts;
@@ -283,6 +284,7 @@ int fit_ragged_chain(k2b::rules::Entry entry, const k2b_model* model, const k2b_
     c.B = slots.slots;
     c.chain.len = slots.max_len > 1 ? slots.max_len : 2; c.chain.iters = followup_iters; c.chain.meta = meta;
     c.chain.freeze_shape = freeze_shape;
+    c.chain.frames = (long long)offsets[num_sequences - 1] + lengths[num_sequences - 1];
     return fit_world_impl(model, prior, cfg, c);
 }
 
@@ -406,6 +408,19 @@ int k2b_fit_multiview(const k2b_model* model, const k2b_prior* prior, const k2b_
     return fit_frames(Entry::fit_multiview, model, prior, cfg, {B, K, model_joint_index, keypoints, conf, {go_in, bp_in, be_in, tr_in}, preserve,
                                                                 tr_prior, {go_out, bp_out, be_out, tr_out}, loss_out, grad_out, stream},
                       num_views, cameras);
+}
+
+// Warm-start chains over videos of a calibrated rig (ABI 1.11): k2b_fit_image_sequences' chain with FitCall::num_views set.
+int k2b_fit_multiview_sequences(const k2b_model* model, const k2b_prior* prior, const k2b_fit_config* cfg, int32_t num_sequences,
+                                const int32_t* lengths, const int32_t* offsets, int32_t followup_iters, int32_t followup_freeze_betas,
+                                int32_t num_views, const k2b_camera* cameras, int32_t K, const int32_t* model_joint_index,
+                                const float* keypoints, const float* conf, const float* go_in, const float* bp_in, const float* be_in,
+                                const float* tr_in, float* go_out, float* bp_out, float* be_out, float* tr_out, float* loss_out,
+                                void* stream) {
+    FitCall c = fit_call(0, K, model_joint_index, keypoints, conf, {go_in, bp_in, be_in, tr_in}, {go_out, bp_out, be_out, tr_out}, loss_out, stream);
+    c.num_views = num_views; c.cameras = cameras;
+    return fit_ragged_chain(Entry::fit_multiview_sequences, model, prior, cfg, num_sequences, lengths, offsets, followup_iters,
+                            followup_freeze_betas != 0, c);
 }
 
 int k2b_sequence_order(int32_t num_sequences, const int32_t* lengths, const int32_t* offsets, int32_t* order_out, int32_t* num_slots) {

@@ -71,7 +71,7 @@ int device_cus() {
 
 extern "C" {
 
-uint32_t k2b_version(void) { return (1u << 16) | 10u; }
+uint32_t k2b_version(void) { return (1u << 16) | 11u; }
 const char* k2b_last_error(void) { return g_err.c_str(); }
 
 uint32_t k2b_fit_config_size(void) { return (uint32_t)sizeof(k2b_fit_config); }

@@ -212,13 +212,18 @@ __device__ __forceinline__ float frame_loss(float lanes, float c_y, float best, 
 // NBTF = NBT, or NBT | kProjForm for the joint term's projected form (block e of the tree pass: the perspective reprojection
 // residual of k2b_fit_config::projection; fp32 scans only).  The form rides in the first argument, not in a fourth one, so that
 // the 3D instantiations keep their symbol names: their code objects can be compared with those of any earlier build.
+// NBT | kViewsForm is the multi-view form of k2b_fit_multiview, NBT | kViewsForm | kViewsChainForm that form inside the warm-start
+// chains of k2b_fit_multiview_sequences (split shape only): an instantiation of its own, so that the one for independent frames
+// stays the code it was.
 template <int NBTF, int MODE, bool SCAN64>
 __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel(const FitArgs a) {
     constexpr int NBT = NBTF & kFormMask;
     constexpr bool PROJ = (NBTF & kProjForm) != 0;
     constexpr bool VIEWS = (NBTF & kViewsForm) != 0;         // NBT | kViewsForm: the reprojection summed over FitArgs::view (k2b_fit_multiview)
     static_assert(!(PROJ && SCAN64), "the projected form is built for the fp32 scans");
+    constexpr bool VCHAIN = (NBTF & kViewsChainForm) != 0;   // ... | kViewsChainForm: that form in a warm-start chain (k2b_fit_multiview_sequences)
     static_assert(!(VIEWS && (SCAN64 || PROJ)), "the multi-view form is a form of its own, built for the fp32 scans");
+    static_assert(!VCHAIN || (VIEWS && MODE == MODE_SPLIT), "chains live in the split shape");
     constexpr bool SPLIT = Shape<MODE>::SPLIT, PAIR = Shape<MODE>::PAIR;
     constexpr int NROW = Shape<MODE>::NROW, CPW = Shape<MODE>::CPW;
     constexpr bool WIDE16 = Shape<MODE>::NWAVES == 16;       // four waves per SIMD: 128 registers per lane
@@ -618,6 +623,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
         asm volatile("" ::"v"(bh0), "v"(bh1), "v"(bl0), "v"(bl1));
     };
 
+    // several views in a chain (VCHAIN): the frame whose target rows the pass reads, row c_off + c_vstep of the launch (wave-uniform,
+    // set by the tree waves' step loop; a slot whose sequence has ended stays on its last frame: it writes nothing and reads inside
+    // its own rows)
+    int c_vstep = 0;
     auto tree_pass = [&](bool last) __attribute__((always_inline)) {
         // ---- b/d. tree-layout reads, J(beta), Rodrigues ---------------------------------------------
         const Vec3 th = {xs_t[thoff], xs_t[thoff + 1], xs_t[thoff + 2]};
@@ -692,7 +701,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
             //  pointers: launch_fit_world keeps a launch's rows below 2^27.)
             int vl = lane;
             asm volatile("" : "+v"(vl));
-            const unsigned ft = (unsigned)(PAIR ? ((vl >> 5) ? f[FW - 1] : f[0]) : f[0]);
+            const unsigned ft = (unsigned)(PAIR ? ((vl >> 5) ? f[FW - 1] : f[0]) : (VCHAIN ? c_off + c_vstep : f[0]));   // (a chain: this step's frame)
             const unsigned row = ft * (unsigned)(a.num_views * a.num_targets) + (tk >= 0 ? tk : 0);
             for (int c = 0; c < a.num_views; ++c) {
                 const FitView& vw = a.view[c];
@@ -1045,7 +1054,10 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                     la.max_eval = la.max_iter * 5 / 4;
                 }
             }
-            if (!PAIR && step > 0 && step < c_len && tk >= 0) {   // targets of this step's frame (row off + step of the slot's sequence)
+            // (several views in a chain keep nothing of the targets in registers: the pass reads this step's rows itself, below.  The
+            //  branch is VCHAIN's alone, so that the multi-view instantiations for independent frames stay the code they were.)
+            if constexpr (VCHAIN) c_vstep = step < c_len ? step : c_len - 1;
+            else if (!PAIR && step > 0 && step < c_len && tk >= 0) {   // targets of this step's frame (row off + step of the slot's sequence)
                 const size_t ft = (size_t)c_off + step;
                 const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
                 tgt = {y[0], y[1], y[2]};
@@ -1386,7 +1398,7 @@ __global__ __launch_bounds__(Shape<MODE>::NWAVES * 64) void k2b_fit_world_kernel
                 pr0[0] = x0[0];
                 if (bodyB) { pr1[0] = x1[0]; refB[0] = x1[0]; }
                 m0[0] = v0[0] = m1[0] = v1[0] = 0.f;
-                if constexpr (PROJ) {   // a video's shape is its first frame's: the follow-up steps hold the shape group (FitArgs::chain_freeze_shape)
+                if constexpr (PROJ || VCHAIN) {  // a video's shape is its first frame's: the follow-up steps hold the shape group (FitArgs::chain_freeze_shape)
                     if (a.chain_freeze_shape) optB = optB && !betaB;
                 }
             }
@@ -1541,6 +1553,14 @@ static void launch_shape(const FitLaunch& l, const FitArgs& a, hipStream_t strea
     const dim3 grid(l.grid), block(l.block_threads);
     if constexpr (MODE != MODE_SPLIT_LBFGS) {
         if (a.num_views > 0) {
+            if constexpr (MODE == MODE_SPLIT) {
+                if (a.chain_len > 1) {
+                    constexpr int VC = kViewsForm | kViewsChainForm;
+                    if (l.NBT == 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10 | VC, MODE, false>), grid, block, 0, stream, a);
+                    else hipLaunchKernelGGL((k2b_fit_world_kernel<16 | VC, MODE, false>), grid, block, 0, stream, a);
+                    return;
+                }
+            }
             if (l.NBT == 10) hipLaunchKernelGGL((k2b_fit_world_kernel<10 | kViewsForm, MODE, false>), grid, block, 0, stream, a);
             else hipLaunchKernelGGL((k2b_fit_world_kernel<16 | kViewsForm, MODE, false>), grid, block, 0, stream, a);
             return;
@@ -1561,18 +1581,21 @@ static void launch_shape(const FitLaunch& l, const FitArgs& a, hipStream_t strea
 }
 
 // executes plan_fit_world (k2b_launch_plan.h: shapes, frames per workgroup, the split of a batch beyond one full-width launch)
-hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream) {
+hipError_t launch_fit_world(const FitArgs& a_in, hipStream_t stream, long long chain_frames) {
     const FitPlan plan = plan_fit_world(a_in.num_frames, a_in.num_cus, a_in.num_betas, a_in.scan64 != 0, a_in.force_shape, a_in.lb_mode,
                                         a_in.chain_len);
     if (!plan.ok) return hipErrorInvalidValue;       // lb_mode and the batch disagree: the caller asks lbfgs_scheme_for first
     // the projected term is instantiated for fp32 scans and Adam only (the entries refuse the rest by name)
     if (a_in.projection && (a_in.scan64 || a_in.lb_mode != LbMode::none)) return hipErrorInvalidValue;
-    // the multi-view term likewise, for independent frames
-    if (a_in.num_views != 0 && (a_in.num_views < 0 || a_in.num_views > kMaxViews || a_in.scan64 || a_in.lb_mode != LbMode::none || a_in.chain_len > 1))
+    // the multi-view term likewise
+    if (a_in.num_views != 0 && (a_in.num_views < 0 || a_in.num_views > kMaxViews || a_in.scan64 || a_in.lb_mode != LbMode::none))
         return hipErrorInvalidValue;
-    // (a lane addresses its views' target rows by a 32-bit index behind its launch's base: checked before the first launch)
-    for (int i = 0; a_in.num_views > 0 && i < plan.num_launches; ++i)
-        if ((size_t)plan.launch[i].num_frames * a_in.num_views * a_in.num_targets >= ((size_t)1 << 27)) return hipErrorInvalidValue;
+    // (a lane addresses its views' target rows by a 32-bit index behind its launch's base: checked before the first launch.  A
+    //  chain is one launch whose rows are those of all its frames, chain_frames of them, not of its slots.)
+    for (int i = 0; a_in.num_views > 0 && i < plan.num_launches; ++i) {
+        const size_t frames = a_in.chain_len > 1 ? (size_t)chain_frames : (size_t)plan.launch[i].num_frames;
+        if (frames * a_in.num_views * a_in.num_targets >= ((size_t)1 << 27)) return hipErrorInvalidValue;
+    }
     for (int i = 0; i < plan.num_launches; ++i) {
         const FitLaunch& l = plan.launch[i];
         FitArgs a = frame_range(a_in, l.first_frame, l.num_frames);

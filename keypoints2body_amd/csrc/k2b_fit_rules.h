@@ -1,4 +1,4 @@
-// k2b_fit_rules.h — what each of the ten fit entries of the C ABI (include/k2b.h) refuses, as pure functions: given who is calling
+// k2b_fit_rules.h — what each of the eleven fit entries of the C ABI (include/k2b.h) refuses, as pure functions: given who is calling
 // and what they pass, is the call accepted, and if not, with which code and which message.  The ONE statement of those rules
 // (DESIGN.md 4.9): every entry fills the facts of its handles and the description of its call, asks judge() once, before anything
 // is allocated, built or queued, and hands a refusal to fail(); the set-up behind it (k2b_api_fit.hip, k2b_api_lbfgs.hip) checks
@@ -26,16 +26,20 @@ namespace rules {
 
 enum class Entry {
     fit_world, fit_sequence, fit_sequences, fit_image, fit_image_sequences, fit_multiview,
-    fit_world_lbfgs, fit_sequence_lbfgs, fit_sequences_lbfgs, shape_pass_lbfgs
+    fit_world_lbfgs, fit_sequence_lbfgs, fit_sequences_lbfgs, shape_pass_lbfgs,
+    fit_multiview_sequences      // (appended: the values of the first ten are recorded in tests and golden files)
 };
-constexpr int kNumEntries = 10;
+constexpr int kNumEntries = 11;
 constexpr const char* entry_name(Entry e) {
     constexpr const char* names[kNumEntries] = {"k2b_fit_world", "k2b_fit_sequence", "k2b_fit_sequences", "k2b_fit_image", "k2b_fit_image_sequences",
                                                 "k2b_fit_multiview", "k2b_fit_world_lbfgs", "k2b_fit_sequence_lbfgs", "k2b_fit_sequences_lbfgs",
-                                                "k2b_shape_pass_lbfgs"};
+                                                "k2b_shape_pass_lbfgs", "k2b_fit_multiview_sequences"};
     return names[(int)e];
 }
-constexpr bool is_lbfgs(Entry e) { return e >= Entry::fit_world_lbfgs; }
+constexpr bool is_lbfgs(Entry e) {
+    return e == Entry::fit_world_lbfgs || e == Entry::fit_sequence_lbfgs || e == Entry::fit_sequences_lbfgs || e == Entry::shape_pass_lbfgs;
+}
+constexpr bool is_multiview(Entry e) { return e == Entry::fit_multiview || e == Entry::fit_multiview_sequences; }
 
 // What the rules read from the two handles.  (k2b_host.h fills it from k2b_model and k2b_prior.)
 struct Facts {
@@ -71,7 +75,7 @@ struct Call {
     const int32_t *lengths = nullptr, *offsets = nullptr;
     int max_iter = 0, history_size = 0;       // the L-BFGS entries (max_iter: first_iters in a chain)
     double lr = 0.0;
-    int num_views = 0;                        // k2b_fit_multiview
+    int num_views = 0;                        // k2b_fit_multiview, k2b_fit_multiview_sequences
     const k2b_camera* cameras = nullptr;
     int num_frames = 0, root_joint = 0, num_free_betas = 0;         // the shape pass
 };
@@ -144,8 +148,8 @@ inline int check_handles(const char* who, const Call& c, Verdict& v) {
     if (!c.facts || !c.cfg) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
     return K2B_OK;
 }
-// k2b_fit_config::projection is built into k2b_fit_world's Adam loop, k2b_fit_image, k2b_fit_image_sequences' chain and
-// k2b_fit_multiview: the other chain entries and the L-BFGS entries refuse it by name
+// k2b_fit_config::projection is built into k2b_fit_world's Adam loop, k2b_fit_image, k2b_fit_image_sequences' chain,
+// k2b_fit_multiview and k2b_fit_multiview_sequences' chain: the other chain entries and the L-BFGS entries refuse it by name
 inline int refuse_projection(const char* who, const Call& c, Verdict& v) {
     if (c.cfg && c.cfg->projection != 0)
         return v.refuse(K2B_ERR_UNSUPPORTED, "%s: the projected joint term (projection=%d) is built into k2b_fit_world only", who, c.cfg->projection);
@@ -216,9 +220,9 @@ inline int shared_path(const Call& c, const Shared& s, Verdict& v) {
     if (chain && !iters_ok(s.chain_iters, kMaxAdamIters)) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_sequence: followup_iters=%d", s.chain_iters);
     if (chain && (s.preserve || s.tr_prior || s.grad_out || cfg.transl_prior_weight != 0.0f))
         return v.refuse(K2B_ERR_UNSUPPORTED, "k2b_fit_sequence: no explicit preserve pose, translation prior or gradient output in a chain");
-    // k2b_fit_config::projection: its values, and what the projected joint term is not built into.  (k2b_fit_multiview has checked
-    // its own form of it - cfg->focal is not read there; the L-BFGS entries have refused it by name.)
-    if (c.entry != Entry::fit_multiview && cfg.projection != 0) {
+    // k2b_fit_config::projection: its values, and what the projected joint term is not built into.  (The multi-view entries have
+    // checked their own form of it - cfg->focal is not read there; the L-BFGS entries have refused it by name.)
+    if (!is_multiview(c.entry) && cfg.projection != 0) {
         if (cfg.projection != 1) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "k2b_fit_world: projection=%d must be 0 or 1", cfg.projection);
         if (check_focal("k2b_fit_world", cfg.focal, v)) return v.code;
         if ((chain && c.entry != Entry::fit_image_sequences) || is_lbfgs(c.entry))
@@ -367,14 +371,13 @@ inline int judge_fit_image(const Call& c, Verdict& v) {
     return shared_path(c, frames_of(c), v);
 }
 
-inline int judge_fit_multiview(const Call& c, Verdict& v) {
-    const char* who = entry_name(c.entry);
-    // (what concerns the views alone comes first and follows no handle)
+// what concerns the views alone: it comes first and follows no handle (`other`: where 3D targets go)
+inline int check_views(const char* who, const char* other, const Call& c, Verdict& v) {
     if (!c.cfg) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: model, prior and cfg are required", who);
     if (c.num_views < 1 || c.num_views > kMaxViews)
         return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: num_views=%d must be 1..%d", who, c.num_views, kMaxViews);
     if (!c.cameras) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: cameras is NULL", who);
-    if (require_projection(who, "k2b_fit_world", c, v)) return v.code;
+    if (require_projection(who, other, c, v)) return v.code;
     for (int i = 0; i < c.num_views; ++i) {
         const k2b_camera& cam = c.cameras[i];
         for (int e = 0; e < 12; ++e)
@@ -383,15 +386,49 @@ inline int judge_fit_multiview(const Call& c, Verdict& v) {
                                 e < 9 ? e : e - 9);
         if (check_focal(who, cam.focal, v)) return v.code;
     }
-    if (check_handles(who, c, v)) return v.code;
+    return K2B_OK;
+}
+// the multi-view term fits kinematic joints, on the tree kernel or on the fused kernel's fp32 scans
+inline int check_view_targets(const char* who, const Call& c, Verdict& v) {
     if (check_targets(who, c, v)) return v.code;
     if (!kinematic_only(c.facts->J, c.K, c.index))
         return v.refuse(K2B_ERR_UNSUPPORTED, "%s: surface targets (vertex-selected joints, landmarks) are not built into the multi-view "
                         "term: model indices below %d only", who, c.facts->J);
-    if (check_scan_plan(who, c, v)) return v.code;
+    return check_scan_plan(who, c, v);
+}
+
+inline int judge_fit_multiview(const Call& c, Verdict& v) {
+    const char* who = entry_name(c.entry);
+    if (check_views(who, "k2b_fit_world", c, v)) return v.code;
+    if (check_handles(who, c, v)) return v.code;
+    if (check_view_targets(who, c, v)) return v.code;
     if (c.B > 0 && (int64_t)c.B * c.num_views * c.K > ((int64_t)1 << 40))
         return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: %d x %d x %d target rows", who, c.B, c.num_views, c.K);
     return shared_path(c, frames_of(c), v);
+}
+
+// k2b_fit_multiview_sequences: k2b_fit_image_sequences' chain under k2b_fit_multiview's joint term - the table of sequences, the
+// views, then what the chain entries check, in their order
+inline int judge_fit_multiview_sequences(const Call& c, Verdict& v) {
+    const char* who = entry_name(c.entry);
+    if (check_ragged(who, c.num_sequences, c.lengths, c.offsets, v)) return v.code;
+    if (check_views(who, "k2b_fit_sequences", c, v)) return v.code;
+    if (check_handles(who, c, v)) return v.code;
+    if (!iters_ok(c.followup_iters, kMaxAdamIters)) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: followup_iters=%d", who, c.followup_iters);
+    if (!iters_ok(c.cfg->num_iters, kMaxAdamIters)) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: num_iters=%d", who, c.cfg->num_iters);
+    if (c.cfg->transl_prior_weight != 0.0f) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: transl_prior_weight must be 0 in a chain", who);
+    if (check_view_targets(who, c, v)) return v.code;
+    const RaggedSlots r = ragged_order(c.num_sequences, c.lengths, c.offsets);
+    if (r.slots == 0) return v.accept_nothing();
+    if (c.targets_null || c.params_null) return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: NULL parameter / target buffer", who);
+    // (the fused kernel's lanes address the target rows of the one launch by a 32-bit index: k2b_fit.hip)
+    const int64_t frames = (int64_t)c.offsets[c.num_sequences - 1] + c.lengths[c.num_sequences - 1];
+    if (fused_eligibility(*c.facts, *c.cfg).fused && frames * c.num_views * c.K >= ((int64_t)1 << 27))
+        return v.refuse(K2B_ERR_INVALID_ARGUMENT, "%s: %lld x %d x %d target rows (fewer than 2^27 in one call)", who, (long long)frames, c.num_views,
+                        c.K);
+    Shared s = frames_of(c);
+    s.B = r.slots; s.chain_len = r.max_len > 1 ? r.max_len : 2; s.chain_iters = c.followup_iters;
+    return shared_path(c, s, v);
 }
 
 // The closure of the L-BFGS entries is the shared path's evaluate-only launch on frames that are already in the output arrays,
@@ -474,6 +511,7 @@ inline int judge(const Call& c, Verdict& v) {
     case Entry::fit_sequence_lbfgs: return judge_fit_sequence_lbfgs(c, v);
     case Entry::fit_sequences_lbfgs: return judge_fit_sequences_lbfgs(c, v);
     case Entry::shape_pass_lbfgs: return judge_shape_pass_lbfgs(c, v);
+    case Entry::fit_multiview_sequences: return judge_fit_multiview_sequences(c, v);
     }
     return v.refuse(K2B_ERR_INVALID_ARGUMENT, "unknown fit entry");
 }

@@ -44,13 +44,13 @@ __device__ __forceinline__ double shfl64(double v, int src) { return bperm64(src
 
 // NSF = NS, the capacity for shape coefficients (betas | expression): 16, 20 or 32, or NS | kProjForm for the joint term's projected
 // form (k2b_fit_config::projection; as in k2b_fit.hip the form rides in the first argument, so that the 3D instantiations keep
-// their symbol names); CHAIN: warm-start chains (the projected ones also read FitTreeArgs::chain_freeze_shape)
+// their symbol names); CHAIN: warm-start chains (the projected and the multi-view ones also read FitTreeArgs::chain_freeze_shape)
 template <int NSF, bool CHAIN>
 __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs a) {
     constexpr int NS = NSF & kFormMask;
     constexpr bool PROJ = (NSF & kProjForm) != 0;
     constexpr bool VIEWS = (NSF & kViewsForm) != 0;          // NS | kViewsForm: the reprojection summed over FitTreeArgs::view (k2b_fit_multiview)
-    static_assert(!(VIEWS && (PROJ || CHAIN)), "the multi-view form is a form of its own, for independent frames");
+    static_assert(!(VIEWS && PROJ), "the multi-view form is a form of its own");
     extern __shared__ __attribute__((aligned(16))) float tlds[];
     // [8][16][64] half8 A fragments (128 KiB) | [M][64] h | [M][64] b | [M][64] mu | [TW][64] theta_v fp32 |
     // [TW][hi 64 | lo 64] theta_v f16 | [TW][M][64] y' | [TW][M] q | [M] constants | [M] 1 / scale
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     const float* vw_c = nullptr;
     if constexpr (VIEWS) {
         if (tk >= 0) {
-            const size_t row = (size_t)c_off * a.num_views * a.num_targets + tk;
+            const size_t row = (size_t)c_off * a.num_views * a.num_targets + tk;      // (a chain: its first frame; the steps move on from it)
             vw_y = a.j3d + row * 3;
             if (a.conf) vw_c = a.conf + (a.conf_per_frame ? row : (size_t)tk);
         }
@@ -253,6 +253,12 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
     for (int step = 0; step < chain; ++step) {
     const int nit = step == 0 ? a.num_iters : a.chain_iters;
     if (CHAIN && step > 0) {
+        if constexpr (VIEWS) {                   // this step's frame: one frame of [view][target] rows further (an ended sequence stays)
+            if (tk >= 0 && step < c_len) {
+                vw_y += (size_t)a.num_views * a.num_targets * 3;
+                if (vw_c && a.conf_per_frame) vw_c += (size_t)a.num_views * a.num_targets;
+            }
+        } else
         if (tk >= 0 && step < c_len) {           // targets of this step's frame (row off + step of the wave's sequence)
             const size_t ft = (size_t)c_off + step;
             const float* y = a.j3d + (ft * a.num_targets + tk) * 3;
@@ -268,7 +274,7 @@ __global__ __launch_bounds__(64 * TW) void k2b_fit_tree_kernel(const FitTreeArgs
 #pragma unroll
         for (int c = 0; c < 3; ++c) mth[c] = vth[c] = 0.f;
         msh = vsh = mtr = vtr = 0.f;
-        if constexpr (PROJ) {                    // a video's shape is its first frame's: the follow-up steps hold it (the expression stays free)
+        if constexpr (PROJ || VIEWS) {           // a video's shape is its first frame's: the follow-up steps hold it (the expression stays free)
             if (a.chain_freeze_shape) opt_sh = opt_sh && lane >= a.num_betas_prior;
         }
     }
@@ -567,7 +573,7 @@ hipError_t launch_tree(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, h
 }
 template <int NS>
 hipError_t launch_tree_ns(const FitTreePlan& p, size_t lds, const FitTreeArgs& a, hipStream_t stream) {
-    if (a.num_views > 0) return p.chain ? hipErrorInvalidValue : launch_tree<NS | kViewsForm, false>(p, lds, a, stream);
+    if (a.num_views > 0) return p.chain ? launch_tree<NS | kViewsForm, true>(p, lds, a, stream) : launch_tree<NS | kViewsForm, false>(p, lds, a, stream);
     if (a.projection) return p.chain ? launch_tree<NS | kProjForm, true>(p, lds, a, stream) : launch_tree<NS | kProjForm, false>(p, lds, a, stream);
     return p.chain ? launch_tree<NS, true>(p, lds, a, stream) : launch_tree<NS, false>(p, lds, a, stream);
 }

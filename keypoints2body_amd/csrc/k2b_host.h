@@ -219,12 +219,13 @@ struct FitCall {
     float *loss_out = nullptr, *grad_out = nullptr;
     hipStream_t stream = nullptr;
     // warm-start chain (len > 1): frames per sequence, follow-up iterations, ragged slot table (FitArgs::chain_meta);
-    // freeze_shape (k2b_fit_image_sequences): the steps > 0 hold the shape (FitArgs::chain_freeze_shape)
-    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool freeze_shape = false; } chain;
+    // freeze_shape (k2b_fit_image_sequences, k2b_fit_multiview_sequences): the steps > 0 hold the shape (FitArgs::chain_freeze_shape);
+    // frames: the frames of all sequences of a ragged chain (launch_fit_world's bound on the views' target rows)
+    struct Chain { int len = 1, iters = 0; const int* meta = nullptr; bool freeze_shape = false; long long frames = 0; } chain;
     // the L-BFGS step inside the fused launch (FitArgs::lb_mode, lbv, lb_chain_max_iter)
     struct Lbfgs { int mode = LbMode::none; const LbfgsArgs* args = nullptr; int chain_max_iter = 0; } lbfgs;
-    // k2b_fit_multiview: the joint term summed over num_views calibrated cameras (HOST table; targets [B][views][K][3], conf
-    // [views][K] or [B][views][K]); cfg->focal is not read then
+    // k2b_fit_multiview, k2b_fit_multiview_sequences: the joint term summed over num_views calibrated cameras (HOST table; targets
+    // [B][views][K][3], conf [views][K] or [B][views][K], B the frames of all sequences in a chain); cfg->focal is not read then
     int num_views = 0;
     const k2b_camera* cameras = nullptr;
 };

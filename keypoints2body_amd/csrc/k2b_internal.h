@@ -20,6 +20,10 @@ constexpr int kProjForm = 256;
 // A third form (k2b_fit_multiview): the reprojection residual summed over up to kMaxViews calibrated cameras, a run-time loop over
 // FitArgs::view inside the joint term.  It rides in the first template argument as kProjForm does (never together with it).
 constexpr int kViewsForm = 512;
+// The multi-view form inside a warm-start chain (k2b_fit_multiview_sequences): a bit of the fused kernel's first template argument
+// beside kViewsForm, split shape only - the instantiations for independent frames stay the code they were.  (The tree kernel has
+// its CHAIN parameter.)
+constexpr int kViewsChainForm = 1024;
 constexpr int kFormMask = kProjForm - 1;      // the capacity under the form bits
 // one camera of a multi-view call as the kernels read it (k2b.h, k2b_camera): q = r (p + transl) + t, pixels = (fx q_x, fy q_y) / q_z
 struct FitView { float r[9], t[3], fx, fy; };
@@ -106,7 +110,8 @@ struct FitArgs {
     FitView view[kMaxViews];
 };
 
-hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream);
+// chain_frames: the frames of all sequences of a chain (chain_len > 1) whose slots come from chain_meta, read with num_views > 0 only
+hipError_t launch_fit_world(const FitArgs& a, hipStream_t stream, long long chain_frames = 0);
 
 // Kernel arguments of the fused fit for large trees (k2b_fit_tree.hip: 25..64 joints, SMPL-H / SMPL-X).
 struct FitTreeArgs {

@@ -115,6 +115,8 @@ _PROTOTYPES = (
     ("k2b_surface_term_image", C.c_int, (_vp, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _vp) + (_vp,) * 6 + _STREAM),
     ("k2b_camera_size", C.c_uint32, ()),
     ("k2b_fit_multiview", C.c_int, _FIT_HEAD + (_i32, _i32, C.POINTER(CameraC)) + _FIT_IN + (_vp, _vp) + _FIT_OUT + (_vp,) + _STREAM),
+    ("k2b_fit_multiview_sequences", C.c_int,
+     _FIT_HEAD + (_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(CameraC)) + _FIT_IN + _FIT_OUT + _STREAM),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in _PROTOTYPES)
 
@@ -549,18 +551,19 @@ def ragged_offsets(lengths) -> np.ndarray:
     return out
 
 
-def _fit_sequences_call(name, model, prior, cfg, followup, model_joint_index, lengths, offsets, j3d, *params, tail=()):
+def _fit_sequences_call(name, model, prior, cfg, followup, model_joint_index, lengths, offsets, j3d, *params, tail=(), views=0):
     """Shared body of the ragged entries: host int32 lengths / offsets checked against the packed frames, then the fit call
-    with (S, lengths, offsets, *`followup`) in front."""
+    with (S, lengths, offsets, *`followup`) in front.  `views` > 0: the packed frames are (sum T, views, K, 3)."""
     L = _host_i32(np.asarray(lengths).reshape(-1))
     O = ragged_offsets(L) if offsets is None else _host_i32(np.asarray(offsets).reshape(-1))
     S, N = int(L.shape[0]), int(j3d.shape[0])
-    idx = _joint_index(model_joint_index, int(j3d.shape[1]))
+    idx = _joint_index(model_joint_index, int(j3d.shape[2 if views else 1]))
     if O.shape != (S,):
         raise ValueError(f"offsets has {O.shape[0]} entries for {S} sequences")
     if S and int(L.astype(np.int64).sum()) != N and (L >= 0).all():
         raise ValueError(f"lengths sum to {int(L.astype(np.int64).sum())}, j3d has {N} frames")
-    return _fit_call(name, model, prior, cfg, (S, _np_ptr(L), _np_ptr(O), *followup), idx, (N,), S, j3d, *params, tail=tail)
+    return _fit_call(name, model, prior, cfg, (S, _np_ptr(L), _np_ptr(O), *followup), idx, (N, views) if views else (N,), S, j3d, *params,
+                     tail=tail, out_lead=(N,) if views else None)
 
 
 def fit_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int,
@@ -582,6 +585,24 @@ def fit_image_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC,
     ``fit_sequences``."""
     return _fit_sequences_call("k2b_fit_image_sequences", model, prior, cfg, (int(followup_iters), int(bool(followup_freeze_betas))),
                                model_joint_index, lengths, offsets, keypoints, conf, global_orient, body_pose, betas, transl)
+
+
+def fit_multiview_sequences(model: NativeModel, prior: NativePrior, cfg: FitConfigC, followup_iters: int, followup_freeze_betas: bool,
+                            cameras, model_joint_index: Sequence[int], lengths, keypoints: torch.Tensor, conf: Optional[torch.Tensor],
+                            global_orient: torch.Tensor, body_pose: torch.Tensor, betas: torch.Tensor, transl: torch.Tensor, offsets=None):
+    """Warm-start chains over videos of a calibrated rig (``k2b_fit_multiview_sequences``, ONE launch): ``fit_image_sequences``
+    under the joint term of ``fit_multiview``.  `cameras` a ``CameraC`` array (``camera_table``) or rows for one, shared by all
+    sequences and frames; ``keypoints`` packed (sum T, C, K, 3) rows ``(u - cx_c, v - cy_c, ignored)``; `conf` (C, K) or, with
+    ``cfg.conf_per_frame``, (sum T, C, K); ``transl`` is the body's world translation.  Returns the dict of ``fit_sequences``."""
+    table = cameras if isinstance(cameras, C.Array) else camera_table(cameras)
+    if keypoints.dim() != 4:
+        raise ValueError(f"keypoints must be (sum T, C, K, 3), got {tuple(keypoints.shape)}")
+    V = int(keypoints.shape[1])
+    if V != len(table):
+        raise ValueError(f"keypoints has {V} views for {len(table)} cameras")
+    return _fit_sequences_call("k2b_fit_multiview_sequences", model, prior, cfg,
+                               (int(followup_iters), int(bool(followup_freeze_betas)), V, table), model_joint_index, lengths, offsets,
+                               keypoints, conf, global_orient, body_pose, betas, transl, views=V)
 
 
 def fit_sequences_lbfgs(model: NativeModel, prior: NativePrior, cfg: FitConfigC, first_iters: int, followup_iters: int,

@@ -41,7 +41,7 @@ def main(parent_path, branch_path):
         if k not in parent:
             f = branch[k]
             print("NEW    ", k, "VGPRs", f["VGPRs"], "SGPRs", f["TotalSGPRs"], "scratch", f["ScratchSize [bytes/lane]"], "LDS", f["LDS Size [bytes/block]"],
-                  "occupancy", f["Occupancy [waves/SIMD]"])
+                  "occupancy", f["Occupancy [waves/SIMD]"], "VGPR spills", f["VGPRs Spill"], "SGPR spills", f["SGPRs Spill"])
     return 1 if differ else 0
 
 
