@@ -396,6 +396,21 @@ int k2b_dev_lbs_pose_fp8_image(int32_t J, int32_t NB, int32_t V, int32_t n, cons
     return 0;
 }
 
+// Development entry, outside include/k2b.h: the first `halfs` halfs of the model's X workspace (hi and lo pieces, frag_elem order
+// with the padded frame count of the call that wrote them) as it stands after the last k2b_lbs call, for the GPU tests that hold
+// the e4m3 form to its own operands.  Synchronises the device first.  Returns 0, -1 for a NULL argument or a size above the workspace.
+int k2b_dev_lbs_read_x(const k2b_model* model_c, uint16_t* xh, uint16_t* xl, int64_t halfs) {
+    k2b_model* m = const_cast<k2b_model*>(model_c);
+    if (!m || !xh || !xl || halfs < 0) return -1;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if ((uint64_t)halfs > (uint64_t)k2b::lbs_workspace(m->lbs, m->ws_bpad, 0).x_halfs) return -1;
+    if (halfs == 0) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(xh, m->wsXh.get(), (size_t)halfs * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(xl, m->wsXl.get(), (size_t)halfs * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 void k2b_model_destroy(k2b_model* m) {
     if (!m) return;
     (void)hipDeviceSynchronize();

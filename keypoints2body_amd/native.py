@@ -338,6 +338,17 @@ class NativeModel(_Handle):
         _launch("k2b_lbs", dev, self._h, B, *params, _ptr(joints), _ptr(verts))
         return joints, verts
 
+    def dev_read_x(self, halfs: int):
+        """Development entry ``k2b_dev_lbs_read_x`` (outside include/k2b.h): the first `halfs` halfs of the X workspace, hi and lo
+        pieces as two uint16 arrays, as the last ``lbs`` call left them.  Synchronises the device."""
+        fn = load_library().k2b_dev_lbs_read_x
+        fn.restype, fn.argtypes = C.c_int, [_vp, _vp, _vp, _i64]
+        xh, xl = np.empty(int(halfs), dtype=np.uint16), np.empty(int(halfs), dtype=np.uint16)
+        with torch.cuda.device(self.device):
+            if fn(self._h, _np_ptr(xh), _np_ptr(xl), int(halfs)) != 0:
+                raise ValueError(f"k2b_dev_lbs_read_x: {halfs} halfs refused (NULL argument, size above the workspace, or a HIP error)")
+        return xh, xl
+
     def lbs_backward(self, global_orient, body_pose, betas, transl, grad_joints, grad_vertices, want=(True, True, True, True)):
         """Vector-Jacobian product of ``lbs``: the gradients of (global_orient, body_pose, betas, transl) for the cotangents
         `grad_joints` (B,J+E+L,3) and / or `grad_vertices` (B,V,3) (either may be None, not both); an entry of `want` that is

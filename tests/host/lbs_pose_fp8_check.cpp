@@ -1,5 +1,5 @@
 // Host check of the e4m3 pose-correction operands (csrc/k2b_lbs_fp8.h, pose_fp8_strips of k2b_model_tables.h) and of the route
-// rule that selects them (lbs_route of k2b_lbs_plan.h), against definitions written out a second time: 17-24 joints x 1-10 shape
+// rule that selects them (lbs_route of k2b_lbs_plan.h), against definitions written out a second time: 17-24 joints x 1-24 shape
 // coefficients, the mesh and a 21-vertex subset of it.  No HIP; built with the address and undefined-behaviour sanitizers.
 #include <cmath>
 #include <cstdint>
@@ -149,7 +149,7 @@ int main() {
     std::mt19937 rng(9);
     int images = 0;
     for (int J = 17; J <= 24; ++J)
-        for (int NB = 1; NB <= 10; ++NB) {
+        for (int NB = 1; NB <= 24; ++NB) {                // (the route allows 1-24 coefficients with 23 joints, 1-15 with 24)
             const LbsRouteRecord r = lbs_route(J, NB, true, false);
             if (!r.pose_fp8) continue;
             const int V = 150 + 7 * NB;                    // two 128-vertex groups, the second partial
@@ -161,7 +161,7 @@ int main() {
             check_image(J, NB, V, sub, true, lo, hi, rng, &lo2, &hi2);      // the 21-vertex operand set of the joints-only call
             ++images;
         }
-    CHECK(images == 20, "%d models with the e4m3 form", images);
+    CHECK(images == 24 + 15, "%d models with the e4m3 form", images);
     printf("images: %s\n", failures == before ? "ok" : "FAILED");
     printf("%d failures\n", failures);
     return failures ? 1 : 0;

@@ -66,6 +66,7 @@ TABLE = (
     (23, 10, 210, 14, "stream"),       # one idle joint lane
     (20, 32, 205, 14, "stream"),       # stream kernel with capacity 32
     (24, 15, 224, 14, "stream"),       # every k column of the stream kernel in use
+    (23, 24, 224, 14, "stream"),       # the only e4m3 layout with capacity 32 (pose set-up <32, 3, true>); last k-step exactly full
     (24, 16, 225, 16, "tile"),         # its boundary partner; backward row with NB = 16
     (24, 17, 226, 16, "tile"),         # capacity 32; the backward's row switch; vertex_term<64, 32>
     (24, 32, 241, 16, "tile"),

@@ -11,7 +11,7 @@ def test_every_row_agrees_with_the_route_rule():
     for J, NB, feats, kx, route in L.TABLE:
         assert feats == 9 * (J - 1) + NB + 2, (J, NB)
         assert L.expected_route(J, NB) == (feats, kx, route), (J, NB, L.expected_route(J, NB))
-    assert len(set(L.LAYOUTS)) == len(L.TABLE) == 16
+    assert len(set(L.LAYOUTS)) == len(L.TABLE) == 17
 
 
 def test_the_route_constants_are_the_ones_the_table_was_written_for():
@@ -52,7 +52,8 @@ def test_the_table_covers_every_branch():
     assert 23 in {J for J, _ in rows} and 56 in {J for J, _ in rows}   # an idle joint lane; no padded joint in the last group
     for sub in (L.FAR_LAYOUTS, L.STREAM_LAYOUTS, L.REPEAT_LAYOUTS, L.BACKWARD_LAYOUTS, L.BACKWARD_ALL_COTANGENTS, (L.LANDMARK_LAYOUT,)):
         assert set(sub) <= set(rows), sub
-    assert len(L.STREAM_LAYOUTS) == 11
+    assert len(L.STREAM_LAYOUTS) == 12
+    assert rows[(23, 24)] == (224, 14, "stream")                         # capacity 32 on the e4m3 form (pose set-up <32, 3, true>), last k-step full
     assert set(L.BACKWARD_LAYOUTS) == {(17, 1), (21, 11), (24, 16), (24, 17), (49, 1), (55, 24), (56, 15), (56, 32)}
 
 

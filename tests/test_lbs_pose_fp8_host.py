@@ -11,47 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from keypoints2body_amd import native, synthetic
-
-F8_STEPS = 6            # 32-deep k-steps with e4m3 strips; k-step 6 keeps the f16 form
-PD_SCALE = 256.0
-X_HI_EXP, X_LO_EXP = -4, -15
-
-
-# ---- an independent encoder ---------------------------------------------------------------------------------------------------
-def _decode_table():
-    c = np.arange(256)
-    e, m = (c >> 3) & 15, c & 7
-    mag = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8.0) * 2.0 ** (e.astype(np.float64) - 7))
-    mag[(e == 15) & (m == 7)] = np.nan
-    return np.where(c & 0x80, -mag, mag)
-
-
-def _np_encode(x):
-    """Nearest finite e4m3fn value, ties to the even code, saturating at +-448; NaN -> 0x7f | sign."""
-    x = np.asarray(x, dtype=np.float64)
-    mags = _decode_table()[:0x7f]                              # codes 0..0x7e: increasing magnitudes 0..448
-    a = np.minimum(np.abs(x), 448.0)
-    hi = np.clip(np.searchsorted(mags, a), 1, 0x7e)            # first code with magnitude >= a
-    lo = hi - 1
-    dlo, dhi = a - mags[lo], mags[hi] - a
-    code = np.where(dlo < dhi, lo, np.where(dhi < dlo, hi, np.where(lo % 2 == 0, lo, hi)))
-    code = np.where(np.isnan(x), 0x7f, code).astype(np.uint8)
-    return code | (np.signbit(x).astype(np.uint8) << 7)
-
-
-def _lib():
-    return native.load_library()
-
-
-def _encode(x, exp=0):
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    out = np.empty(x.size, dtype=np.uint8)
-    fn = _lib().k2b_dev_e4m3_encode
-    fn.restype = C.c_int
-    rc = fn(C.c_int64(x.size), x.ctypes.data_as(C.c_void_p), C.c_int32(exp), out.ctypes.data_as(C.c_void_p))
-    assert rc == 0
-    return out.reshape(x.shape)
+from tests.lbs_pose_fp8_common import (F8_STEPS, PD_SCALE, _consts, _decode_table, _encode, _features, _ids, _image, _lib, _np_encode,
+                                       _unpack, _x_terms, emulate)
 
 
 def test_encoder_reproduces_every_code():
@@ -84,66 +45,6 @@ def test_encoder_matches_numpy_on_random_values_ties_subnormals_and_saturation()
 
 
 # ---- the images -----------------------------------------------------------------------------------------------------------------
-_memo = {}
-
-
-def _consts():
-    if "c" not in _memo:
-        _memo["c"] = synthetic.make_body_model(0)
-    return _memo["c"]
-
-
-def _ids():
-    return np.sort(np.random.default_rng(2).choice(_consts().v_template.shape[0], 1000, replace=False)).astype(np.int32)
-
-
-def _image(pose_f16, ids=None, given=None):
-    """(spd as uint16, info = [pose_fp8, nv16, lo_exp, hi_exp]) of the vertex set `ids` of the synthetic model."""
-    c = _consts()
-    ids = np.ascontiguousarray(_ids() if ids is None else ids, dtype=np.int32)
-    V, J, NB = c.v_template.shape[0], c.parents.shape[0], c.shapedirs.shape[-1]
-    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    arrs = [f(c.v_template), f(c.shapedirs), f(c.posedirs), f(c.lbs_weights)]
-    fn = _lib().k2b_dev_lbs_pose_fp8_image
-    fn.restype = C.c_int
-    n, info = C.c_int64(0), np.zeros(4, dtype=np.int32)
-    gv = None if given is None else np.asarray(given, dtype=np.int32)
-    head = [C.c_int32(J), C.c_int32(NB), C.c_int32(V), C.c_int32(len(ids)), ids.ctypes.data_as(C.c_void_p)] + \
-           [a.ctypes.data_as(C.c_void_p) for a in arrs] + [C.c_int32(pose_f16), None if gv is None else gv.ctypes.data_as(C.c_void_p)]
-    assert fn(*head, None, C.byref(n), info.ctypes.data_as(C.c_void_p)) == 0
-    spd = np.zeros(n.value, dtype=np.uint16)
-    assert fn(*head, spd.ctypes.data_as(C.c_void_p), C.byref(n), info.ctypes.data_as(C.c_void_p)) == 0
-    return spd, info
-
-
-def _unpack(spd, info, n):
-    """The layout, a second time.  spd [k-step 7][16-vertex tile][coordinate 3][hi | lo] in 1 KiB pieces.  f16 piece: lane =
-    vertex row + 16 * (k >> 3) holds 8 halfs k & 7.  e4m3 piece (k-steps 0..5 of a pose_fp8 image, in place of lo): lane group g
-    (16 bytes per lane, lane = row + 16 g) = Pd_lo8[k 0..15], Pd_lo8[k 16..31], Pd_hi8[k 0..15], Pd_hi8[k 16..31].
-    Returns hi, lo (f16 terms as float64, lo NaN where the image has codes), lo8, hi8 (codes, 0 where none): [224][n][3]."""
-    fp8, nv16 = int(info[0]), int(info[1])
-    pieces = spd.reshape(7, nv16, 3, 2, 512)
-    halfs, raw = pieces.view(np.float16), pieces.view(np.uint8).reshape(7, nv16, 3, 2, 1024)
-    i = np.arange(n)
-    v16, r = i >> 4, i & 15
-    k = np.arange(224)
-    ks, kk = k >> 5, k & 31
-    at16 = ((kk >> 3)[:, None] * 16 + r[None, :]) * 8 + (kk & 7)[:, None]                      # [k][vertex]
-    hi = np.stack([halfs[ks[:, None], v16[None, :], c, 0, at16] for c in range(3)], axis=-1).astype(np.float64)
-    lo = np.stack([halfs[ks[:, None], v16[None, :], c, 1, at16] for c in range(3)], axis=-1).astype(np.float64)
-    lo8 = np.zeros((224, n, 3), dtype=np.uint8)
-    hi8 = np.zeros_like(lo8)
-    if fp8:
-        at_lo8 = ((kk >> 4)[:, None] * 16 + r[None, :]) * 16 + (kk & 15)[:, None]
-        at_hi8 = ((2 + (kk >> 4))[:, None] * 16 + r[None, :]) * 16 + (kk & 15)[:, None]
-        lo8 = np.stack([raw[ks[:, None], v16[None, :], c, 1, at_lo8] for c in range(3)], axis=-1)
-        hi8 = np.stack([raw[ks[:, None], v16[None, :], c, 1, at_hi8] for c in range(3)], axis=-1)
-        lo[: 32 * F8_STEPS] = np.nan
-        lo8[32 * F8_STEPS:] = 0
-        hi8[32 * F8_STEPS:] = 0
-    return hi, lo, lo8, hi8
-
-
 def test_pd_strips_hold_the_codes_of_the_f16_terms_at_the_layouts_positions():
     ids = _ids()
     n = len(ids)
@@ -180,36 +81,6 @@ def test_pd_strips_hold_the_codes_of_the_f16_terms_at_the_layouts_positions():
 
 
 # ---- error budget ---------------------------------------------------------------------------------------------------------------
-def _features(pose, betas):
-    """X [B][224] in float64 from float32 parameters: vec(R_j - I) of the 23 body joints (row-major), betas, 1, 1, zeros."""
-    B = pose.shape[0]
-    aa = pose.astype(np.float64).reshape(B, 23, 3)
-    th = np.linalg.norm(aa, axis=-1, keepdims=True)
-    ax = aa / np.maximum(th, 1e-300)
-    K = np.zeros((B, 23, 3, 3))
-    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -ax[..., 2], ax[..., 1], ax[..., 2]
-    K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -ax[..., 0], -ax[..., 1], ax[..., 0]
-    s, c1 = np.sin(th)[..., None], (1 - np.cos(th))[..., None]
-    RmI = s * K + c1 * (K @ K)
-    X = np.zeros((B, 224))
-    X[:, :207] = RmI.reshape(B, 207)
-    X[:, 207:217] = betas
-    X[:, 217:219] = 1.0
-    return X
-
-
-def _x_terms(X32):
-    x = np.ascontiguousarray(X32, dtype=np.float32).reshape(-1)
-    hi, lo = np.empty_like(x), np.empty_like(x)
-    hi8, lo8 = np.empty(x.size, dtype=np.uint8), np.empty(x.size, dtype=np.uint8)
-    fn = _lib().k2b_dev_lbs_x_fp8
-    fn.restype = C.c_int
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    assert fn(C.c_int64(x.size), p(x), p(hi), p(lo), p(hi8), p(lo8)) == 0
-    sh = X32.shape
-    return hi.reshape(sh).astype(np.float64), lo.reshape(sh).astype(np.float64), hi8.reshape(sh), lo8.reshape(sh)
-
-
 REGIMES = ("0.6 N(0,1)", "uniform +-pi", "20 rad")
 
 
@@ -241,22 +112,12 @@ def test_error_budget_of_x_pd_with_the_packed_images(regime):
     Pd[207:217] = np.moveaxis(c.shapedirs[ids], -1, 0)
     Pd[217] = c.v_template[ids]
     want = np.einsum("bk,kvc->bvc", X32.astype(np.float64), Pd)
-    xh, xl, xh8, xl8 = _x_terms(X32)
-    dec = _decode_table()
-    cut = 32 * F8_STEPS
+    x_ops = _x_terms(X32)
     worst = {}
     for name, f16 in (("f16", 1), ("e4m3", 0)):
         spd, info = _image(f16)
-        hi, lo, lo8, hi8 = _unpack(spd, info, n)
-        acc = np.einsum("bk,kvc->bvc", xh, hi)
-        if f16:
-            acc += np.einsum("bk,kvc->bvc", xh, lo) + np.einsum("bk,kvc->bvc", xl, hi)
-        else:
-            acc += np.einsum("bk,kvc->bvc", xh[:, cut:], lo[cut:]) + np.einsum("bk,kvc->bvc", xl[:, cut:], hi[cut:])
-            a_hi, a_lo = dec[xh8[:, :cut]] * 2.0 ** X_HI_EXP, dec[xl8[:, :cut]] * 2.0 ** X_LO_EXP
-            b_lo, b_hi = dec[lo8[:cut]] * 2.0 ** int(info[2]), dec[hi8[:cut]] * 2.0 ** int(info[3])
-            acc += np.einsum("bk,kvc->bvc", a_hi, b_lo) + np.einsum("bk,kvc->bvc", a_lo, b_hi)
-        worst[name] = float(np.abs(acc / PD_SCALE - want).max())
+        got = emulate(x_ops, _unpack(spd, info, n), (info[2], info[3]), fp8=not f16)
+        worst[name] = float(np.abs(got - want).max())
     print(f"{regime}: X.Pd error, three f16 products {worst['f16']:.2e} m, e4m3 corrections {worst['e4m3']:.2e} m")
     assert worst["f16"] <= 1e-7, worst
     assert worst["e4m3"] <= 2.5e-6, worst
@@ -264,7 +125,7 @@ def test_error_budget_of_x_pd_with_the_packed_images(regime):
 
 # ---- the stand-alone host program ---------------------------------------------------------------------------------------------
 def test_host_program_holds_encoder_route_and_images_to_their_definitions(tmp_path):
-    """``tests/host/lbs_pose_fp8_check.cpp``: encoder, route rule and the strips of 17-24 joints x 1-10 coefficients (mesh and the
+    """``tests/host/lbs_pose_fp8_check.cpp``: encoder, route rule and the strips of 17-24 joints x 1-24 coefficients (mesh and the
     21-vertex set), built with the address and undefined-behaviour sanitizers, as ``tests/test_lbs_plan_host.py``."""
     import shutil
     import subprocess
